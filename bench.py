@@ -4,6 +4,8 @@
     python bench.py --gpus N --steps K --warmup W
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
+    `--dump-outputs DIR` also writes what the last timed step returned as DIR/<name>.npy (seeded inputs: runs compare)
+
 Timing: W warm-up steps, then EXACTLY K steps between barrier + synchronize (the contract's region; nothing but the steps is
 enqueued, the library's stage events are off), then the same K steps once more with the events on for the roofline / stage keys.
 
@@ -102,6 +104,31 @@ def fixture_parity(pred, size):
     err = float((got - want).abs().max())
     return {"fixture": f"tests/golden/{name}.npz", "frames": n, "stride": st, "max_abs_err": err, "tolerance": PARITY_TOL,
             "ok": bool(err <= PARITY_TOL)}
+
+
+DUMP_BUDGET = 60 << 20     # data bytes of --dump-outputs, all ranks: with .npy headers and frame indices under 64 MB
+
+
+def dump_outputs(path, outputs, suffix, budget):
+    """--dump-outputs: every array of `outputs` (frames first) as float32 `path/<name><suffix>.npy`.  Beyond `budget` bytes in all, a
+    fixed seeded sample of frames is written instead, and the sampled frame indices as float64 `<name>_frames<suffix>.npy`."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in sorted(outputs.items())}
+    total = sum(a.nbytes for a in arrays.values())
+    record = {"dir": path, "arrays": {}}
+    for k, a in arrays.items():
+        n, frame_bytes = a.shape[0], a[:1].nbytes
+        keep = min(n, int(budget * a.nbytes / total) // frame_bytes) if total > budget else n
+        if keep < 1:
+            raise SystemExit(f"bench.py: one frame of '{k}' ({frame_bytes} bytes) exceeds the --dump-outputs budget")
+        if keep < n:
+            idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+            a = a[idx]
+            np.save(os.path.join(path, f"{k}_frames{suffix}.npy"), idx.astype(np.float64))
+        np.save(os.path.join(path, f"{k}{suffix}.npy"), a)
+        record["arrays"][k + suffix] = {"shape": list(a.shape), "frames_of": n}
+    return record
 
 
 def knob_record(eng, frames, extra_plans=None):
@@ -272,7 +299,14 @@ def main():
                     help="after the contract's timed region: capture one step into a HIP graph and time `--steps` replays (extra key "
                          "`graph`).  Used by tools/gpu_profile.sh: under rocprofv3 the host's per-launch cost delays the second "
                          "chain's launches by ~1.8 ms, a replayed graph keeps the two chains' kernels together as an unprofiled run does")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (float32 `prediction` of this rank's frames) as DIR/<name>.npy, "
+                         "at most 64 MB in all (a seeded sample of frames beyond that, indices in "
+                         "DIR/<name>_frames.npy); with N > 1 every rank writes <name>.rank<r>.npy.  Inputs are seeded: two builds "
+                         "run with the same arguments can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.batch is None:
         args.batch = 16 if args.size <= 256 else 8
 
@@ -399,10 +433,16 @@ def main():
     # the contract's timed region: exactly K steps, nothing else enqueued (the library's stage events stay OFF here)
     fence()
     t0 = time.perf_counter()
+    last = None
     for _ in range(args.steps):
-        step()
+        last = None     # drop the previous step's outputs before the next one allocates, as when they are discarded
+        last = step()
     fence()
     dt = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, last, "" if world == 1 else f".rank{rank}", DUMP_BUDGET // world)
+    del last
     # the same K steps again with the library's HIP events on (stage boundaries, every bottleneck launch, every chain's bottleneck
     # window): the roofline / stage keys come from this second region (the events cost ~0.3 % of a step)
     eng.profile(True)
@@ -845,6 +885,8 @@ def main():
         line["e2e_clip"] = e2e
         if graph_leg is not None:
             line["graph"] = graph_leg
+        if dumped is not None:
+            line["dump_outputs"] = dumped
         if world == 1 and args.cpu_frames > 0:
             line["cpu_baseline"] = cpu_baseline(cfg, sd, S, args.cpu_frames)
             line["gpu_over_cpu"] = round(fps / line["cpu_baseline"]["value"], 1)

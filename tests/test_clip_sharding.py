@@ -1,6 +1,7 @@
 """N>1 path on CPU: two gloo processes run eamm_amd.clip.animate_clip with a stand-in backend that
 computes frames with the oracle.  Checks the protocol of the multi-GPU clip pipeline: one broadcast
 of the source cache from rank 0, key points broadcast, contiguous shards, optional gather."""
+import contextlib
 import os
 import socket
 
@@ -14,6 +15,20 @@ from eamm_amd.clip import animate_clip, shard_bounds
 from eamm_amd.config import tiny_config
 from eamm_amd.weights import synthetic_keypoints, synthetic_source, synthetic_state_dict
 from oracle import eamm_oracle as orc
+
+WORKER_THREADS = 2   # torch threads of every rank below
+
+
+@contextlib.contextmanager
+def worker_threads():
+    """The single-process reference runs with the ranks' thread count: ATen splits CPU reductions by thread, which moves float32
+    results by ~1e-6 (16 threads against 2), so with the host's own count the comparisons would not isolate the sharding."""
+    n = torch.get_num_threads()
+    torch.set_num_threads(WORKER_THREADS)
+    try:
+        yield
+    finally:
+        torch.set_num_threads(n)
 
 
 class OracleBackend:
@@ -93,7 +108,7 @@ class CountedCollectives:
 def _worker(rank, world, port, total, batch, tmp):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
-    torch.set_num_threads(2)
+    torch.set_num_threads(WORKER_THREADS)
     cfg = tiny_config()
     sd = synthetic_state_dict(cfg, seed=1234)
     be = OracleBackend(cfg, sd, batch, 64)
@@ -132,8 +147,9 @@ def test_n_rank_clip_equals_single_process(tmp_path, total, world):
     cfg = tiny_config()
     sd = synthetic_state_dict(cfg, seed=1234)
     be = OracleBackend(cfg, sd, batch, 64)
-    ref, span = animate_clip(be, synthetic_source(64, seed=1), synthetic_keypoints(1, 10, seed=0),
-                             synthetic_keypoints(total, 10, seed=2), 64, 64)
+    with worker_threads():
+        ref, span = animate_clip(be, synthetic_source(64, seed=1), synthetic_keypoints(1, 10, seed=0),
+                                 synthetic_keypoints(total, 10, seed=2), 64, 64)
     assert span == (0, total)
     got = np.concatenate([np.load(tmp_path / f"shard{r}.npy") for r in range(world)], axis=0)
     assert got.shape == tuple(ref.shape)
@@ -163,7 +179,7 @@ def _chain_parts():
 def _chain_worker(rank, world, port, tmp):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
-    torch.set_num_threads(2)
+    torch.set_num_threads(WORKER_THREADS)
     from eamm_amd import animate_from_features
     cfg, sd, kp, tail, kpa, src, feats = _chain_parts()
     be = OracleBackend(cfg, sd, 2, 64)
@@ -192,8 +208,9 @@ def test_n_rank_end_to_end_chain_shards_the_front_end_too(tmp_path, world):
     mp.spawn(_chain_worker, args=(world, port, str(tmp_path)), nprocs=world, join=True)
     cfg, sd, kp, tail, kpa, src, feats = _chain_parts()
     emo = {"value": 0.02 * torch.ones(7, 3, 2), "jacobian": 0.01 * torch.ones(7, 3, 2, 2)}
-    ref, span, kps = animate_from_features(None, kp, tail, kpa, src, feats, emo_driving=emo, backend=OracleBackend(cfg, sd, 2, 64),
-                                           uint8=False, to_host=True, front_batch=3, return_keypoints=True)
+    with worker_threads():
+        ref, span, kps = animate_from_features(None, kp, tail, kpa, src, feats, emo_driving=emo, backend=OracleBackend(cfg, sd, 2, 64),
+                                               uint8=False, to_host=True, front_batch=3, return_keypoints=True)
     assert span == (0, 7) and ref.shape == (7, 3, 64, 64)
     got = np.concatenate([np.load(tmp_path / f"chain{r}.npy") for r in range(world)])
     for r in range(world):     # every rank ended up with the whole clip's normalised key points

@@ -233,3 +233,18 @@ def test_bench_refuses_a_wrong_results_knob():
     assert d["knobs"]["library"] == {"EAMM_PASS_CHAINS": 1} and d["knobs"]["ignored"] == ["EAMM_FINAL_FUSED_MIN_ROWS"]
     assert d["knobs"]["plan"]["pass_chains"] == 1 and d["knobs"]["plan"]["bottleneck_chains"] == 2 and d["parity_check"]["ok"] is True
     assert d["knobs"]["plan"]["final"] == "col7q fused"
+
+
+def test_bench_dump_outputs_are_the_timed_steps_outputs(tmp_path):
+    """--dump-outputs DIR: the last timed step's `prediction` (this rank's 16 frames, float32) lands in DIR/prediction.npy,
+    and its first frames are the committed reference fixture's (the timed launches use the fixture's seeds)."""
+    import numpy as np
+    d = run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--cpu-frames", "0", "--clip-frames", "0", "--train-pairs", "0",
+             "--e2e-frames", "0", "--latency-frames", "0", "--no-all-outputs", "--dump-outputs", str(tmp_path / "out")])
+    assert d["steps"] == 3 and d["dump_outputs"]["arrays"] == {"prediction": {"shape": [16, 3, 256, 256], "frames_of": 16}}
+    assert sorted(os.listdir(tmp_path / "out")) == ["prediction.npy"]
+    pred = np.load(tmp_path / "out" / "prediction.npy")
+    assert pred.dtype == np.float32 and pred.shape == (16, 3, 256, 256) and np.isfinite(pred).all()
+    z = np.load(os.path.join(ROOT, "tests", "golden", "full256_clip2.npz"))
+    st, want = int(z["prediction_stride"]), z["prediction"]
+    assert float(np.abs(pred[:want.shape[0], :, ::st, ::st] - want).max()) <= 1e-4
