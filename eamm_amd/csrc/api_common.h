@@ -122,162 +122,211 @@ const HostTensor* find(const CtxBase* c, const std::string& key) {
     return it == c->sd.end() ? nullptr : &it->second;
 }
 
-// conv (+ optional BatchNorm folded behind it) -> packed device layer.
-// y = ((conv(x) + b) - mean) * gamma / sqrt(var + eps) + beta   (sync_batchnorm/batchnorm.py:48-53, eps 1e-5)
+// y = ((conv(x) + b) - mean) * gamma / sqrt(var + eps) + beta   (sync_batchnorm/batchnorm.py:48-53, eps 1e-5): eval-mode
+// BatchNorm (key prefix `norm`, may be empty) folded into per-channel scale and bias (fp64) of the convolution `conv`
+int fold_norm(CtxBase* c, const std::string& conv, const std::string& norm, int Cout, std::vector<double>* scale,
+              std::vector<double>* bias) {
+    const HostTensor* bt = find(c, conv + ".bias");
+    if (!bt || (int)bt->numel() != Cout) return fail(c, EAMM_ERR_KEY, "%s.bias missing or mis-shaped", conv.c_str());
+    scale->assign(Cout, 1.0);
+    bias->resize(Cout);
+    for (int o = 0; o < Cout; ++o) (*bias)[o] = bt->data[o];
+    if (norm.empty()) return EAMM_OK;
+    const HostTensor *g = find(c, norm + ".weight"), *be = find(c, norm + ".bias"), *mu = find(c, norm + ".running_mean"),
+                     *var = find(c, norm + ".running_var");
+    if (!g || !be || !mu || !var || (int)g->numel() != Cout || (int)be->numel() != Cout || (int)mu->numel() != Cout ||
+        (int)var->numel() != Cout)
+        return fail(c, EAMM_ERR_KEY, "BatchNorm entries of %s missing or mis-shaped", norm.c_str());
+    for (int o = 0; o < Cout; ++o) {
+        const double s = (double)g->data[o] / std::sqrt((double)var->data[o] + 1e-5);
+        (*scale)[o] = s;
+        (*bias)[o] = ((*bias)[o] - (double)mu->data[o]) * s + (double)be->data[o];
+    }
+    return EAMM_OK;
+}
+
+// A convolution with its BatchNorm folded in, on the host: weights [Cout][Cin][kh][kw] (MODE_PHASES: four explicit 2x2
+// phase filters [4][Cout][Cin][4]), bias [Cout].  What every packer below takes.
+struct HostConv {
+    int Cout = 0, Cin = 0, kh = 0, kw = 0;
+    std::vector<float> w, b;
+};
+
 struct FoldSpec {
     std::string conv;            // key prefix holding .weight / .bias
     std::string norm;            // key prefix holding BatchNorm stats, or empty
 };
 
-enum LayerMode { MODE_PLAIN = 0, MODE_PHASE = 1, MODE_ROWSPLIT = 2 };
-
-// MODE_PLAIN: ks x ks convolution.  MODE_PHASE: ks must be 3; the layer consumes the low-resolution input of an
-// UpBlock2d and evaluates "nearest x2 + 3x3" as four 2x2 phase filters.  MODE_ROWSPLIT: ks x 1 convolution with
-// N = (dx, co) -- the horizontal taps become output channels, gathered afterwards by final_shift_sum; the bias is
-// returned in *row_bias instead of being applied by the convolution.
-int build_layer(CtxBase* c, const std::vector<FoldSpec>& parts, int ks, int C0_real, int C0_packed, int C1_real,
-                int C1_packed, ConvLayer* L, LayerMode mode = MODE_PLAIN, std::vector<float>* row_bias = nullptr,
-                int dma_cfg = 0, float** w_swizzled = nullptr, int w_swizzled_bn = 0) {
-    // `parts` are stacked along Cout (the flow head stacks mask + occlusion into one convolution)
-    const int Cin = C0_real + C1_real;
-    const int T = ks * ks;
-    int Cout = 0;
+// The ks x ks convolutions `parts` (Cin inputs each), BatchNorm folded, stacked along Cout (the flow head stacks mask +
+// occlusion into one convolution, the key-point detector kp + jacobian)
+int fold_conv(CtxBase* c, const std::vector<FoldSpec>& parts, int ks, int Cin, HostConv* f) {
+    f->Cin = Cin;
+    f->kh = f->kw = ks;
+    f->Cout = 0;
     for (auto& ps : parts) {
         const HostTensor* wt = find(c, ps.conv + ".weight");
         if (!wt || wt->shape.size() != 4 || wt->shape[1] != Cin || wt->shape[2] != ks || wt->shape[3] != ks)
             return fail(c, EAMM_ERR_KEY, "state_dict entry %s.weight missing or mis-shaped (expected [*,%d,%d,%d])",
                         ps.conv.c_str(), Cin, ks, ks);
-        Cout += (int)wt->shape[0];
+        f->Cout += (int)wt->shape[0];
     }
-    std::vector<float> wf((size_t)Cout * Cin * T), bf(Cout);
+    const size_t per = (size_t)Cin * ks * ks;
+    f->w.resize((size_t)f->Cout * per);
+    f->b.resize(f->Cout);
     int o0 = 0;
     for (auto& ps : parts) {
         const HostTensor* wt = find(c, ps.conv + ".weight");
-        const HostTensor* bt = find(c, ps.conv + ".bias");
         const int co = (int)wt->shape[0];
-        if (!bt || (int)bt->numel() != co) return fail(c, EAMM_ERR_KEY, "%s.bias missing or mis-shaped", ps.conv.c_str());
-        const HostTensor *g = nullptr, *be = nullptr, *mu = nullptr, *var = nullptr;
-        if (!ps.norm.empty()) {
-            g = find(c, ps.norm + ".weight");
-            be = find(c, ps.norm + ".bias");
-            mu = find(c, ps.norm + ".running_mean");
-            var = find(c, ps.norm + ".running_var");
-            if (!g || !be || !mu || !var || (int)g->numel() != co || (int)be->numel() != co ||
-                (int)mu->numel() != co || (int)var->numel() != co)
-                return fail(c, EAMM_ERR_KEY, "BatchNorm entries of %s missing or mis-shaped", ps.norm.c_str());
-        }
+        std::vector<double> s, b;
+        if (int rc = fold_norm(c, ps.conv, ps.norm, co, &s, &b)) return rc;
         for (int o = 0; o < co; ++o) {
-            double s = 1.0, shift = 0.0, b = bt->data[o];
-            if (g) {
-                s = (double)g->data[o] / std::sqrt((double)var->data[o] + 1e-5);
-                b = (b - (double)mu->data[o]) * s + (double)be->data[o];
-            }
-            (void)shift;
-            bf[o0 + o] = (float)b;
-            const float* src = wt->data.data() + (size_t)o * Cin * T;
-            float* dst = wf.data() + (size_t)(o0 + o) * Cin * T;
-            for (size_t i = 0; i < (size_t)Cin * T; ++i) dst[i] = (float)((double)src[i] * s);
+            f->b[o0 + o] = (float)b[o];
+            for (size_t i = 0; i < per; ++i) f->w[(o0 + o) * per + i] = (float)((double)wt->data[o * per + i] * s[o]);
         }
         o0 += co;
     }
-    const int cin_packed = C0_packed + C1_packed;
-    std::vector<int> map(cin_packed, -1);
+    return EAMM_OK;
+}
+
+// MODE_ROWSPLIT: the ks x ks filter as a ks x 1 one with N = (dx, co), w'[dx*Cout+co][c][dy] = w[co][c][dy][dx] -- the
+// horizontal taps become output channels, gathered afterwards (final_shift_sum, the column-patch kernels).  The bias moves
+// out (returned: the gather applies it); the new one is zero.
+std::vector<float> to_rowsplit(HostConv* f) {
+    const int ks = f->kh, Cout = f->Cout, Cin = f->Cin;
+    std::vector<float> wr((size_t)ks * Cout * Cin * ks);
+    for (int dx = 0; dx < ks; ++dx)
+        for (int co = 0; co < Cout; ++co)
+            for (int ci = 0; ci < Cin; ++ci)
+                for (int dy = 0; dy < ks; ++dy)
+                    wr[((size_t)(dx * Cout + co) * Cin + ci) * ks + dy] = f->w[((size_t)co * Cin + ci) * ks * ks + dy * ks + dx];
+    f->w.swap(wr);
+    f->Cout = ks * Cout;
+    f->kw = 1;
+    std::vector<float> row_bias(f->Cout, 0.f);
+    f->b.swap(row_bias);
+    return row_bias;
+}
+
+// Packed input channel -> channel of the filter: the C0_real + C1_real inputs of a concatenation [in0 | in1] whose halves
+// are stored C0_packed / C1_packed wide (-1: a zero padding channel)
+std::vector<int> channel_map(int C0_real, int C0_packed, int C1_real, int C1_packed) {
+    std::vector<int> map(C0_packed + C1_packed, -1);
     for (int i = 0; i < C0_real; ++i) map[i] = i;
     for (int i = 0; i < C1_real; ++i) map[C0_packed + i] = C0_real + i;
-    int kh = ks, kw = ks;
-    if (mode == MODE_ROWSPLIT) {
-        // w'[dx*Cout+co][c][dy] = w[co][c][dy][dx]
-        std::vector<float> wr((size_t)ks * Cout * Cin * ks);
-        for (int dx = 0; dx < ks; ++dx)
-            for (int co = 0; co < Cout; ++co)
-                for (int ci = 0; ci < Cin; ++ci)
-                    for (int dy = 0; dy < ks; ++dy)
-                        wr[((size_t)(dx * Cout + co) * Cin + ci) * ks + dy] = wf[((size_t)co * Cin + ci) * T + dy * ks + dx];
-        if (row_bias) *row_bias = bf;
-        wf.swap(wr);
-        Cout = ks * Cout;
-        bf.assign(Cout, 0.f);
-        kw = 1;
-    }
-    if (mode == MODE_PHASE && ks != 3) return fail(c, EAMM_ERR_ARG, "phase mode needs a 3x3 convolution");
-    L->kh = kh;
-    L->kw = kw;
-    L->phase = mode == MODE_PHASE;
+    return map;
+}
+
+enum LayerMode { MODE_PLAIN = 0, MODE_PHASE = 1, MODE_ROWSPLIT = 2, MODE_PHASES = 3 };
+
+// bias zero-padded to n floats -> device
+int upload_bias(CtxBase* c, float** dst, const std::vector<float>& b, size_t n) {
+    std::vector<float> pad(n, 0.f);
+    std::copy(b.begin(), b.end(), pad.begin());
+    return upload(c, dst, pad);
+}
+
+// Weights image of the implicit-GEMM kernels for an N tile of BN (swizzle: the LDS-DMA layout).  map: null, or
+// channel_map()'s cin_packed entries.  MODE_PHASE collapses a 3x3 filter into the four 2x2 phase filters of "nearest x2 +
+// 3x3"; MODE_PHASES takes those four filters as they are.
+int upload_conv_image(CtxBase* c, float** dst, const HostConv& f, const int* map, int cin_packed, int BN, LayerMode mode,
+                      bool swizzle) {
+    const bool phase = mode == MODE_PHASE || mode == MODE_PHASES;
+    std::vector<float> packed(conv_packed_elems(phase ? 4 : f.kh * f.kw, cin_packed, f.Cout, BN, phase ? 4 : 1));
+    if (mode == MODE_PHASES)
+        conv_pack_phases_host(f.w.data(), f.Cout, f.Cin, map, cin_packed, BN, swizzle, packed.data());
+    else
+        conv_pack_host(f.w.data(), f.Cout, f.Cin, f.kh, f.kw, map, cin_packed, BN, phase, swizzle, packed.data());
+    return upload(c, dst, packed);
+}
+
+// -> ConvLayer: the register-staged 128 x BN kernel (BN 0: conv_tile_n's), or (dma_cfg > 0) an LDS-DMA tile (conv_dma_tile)
+int pack_conv(CtxBase* c, const HostConv& f, const int* map, int C0_packed, int C1_packed, LayerMode mode, int dma_cfg,
+              ConvLayer* L, int BN = 0) {
+    const bool phase = mode == MODE_PHASE || mode == MODE_PHASES;
+    L->kh = f.kh;
+    L->kw = f.kw;
+    L->phase = phase;
     L->C0 = C0_packed;
     L->C1 = C1_packed;
-    L->Cout = Cout;
+    L->Cout = f.Cout;
     L->BM = 128;
-    L->BN = conv_tile_n(Cout);
+    L->BN = BN ? BN : conv_tile_n(f.Cout);
     L->dma_cfg = dma_cfg;
     if (dma_cfg > 0 && !conv_dma_tile(dma_cfg, &L->BM, &L->BN)) return fail(c, EAMM_ERR_ARG, "unknown dma tile %d", dma_cfg);
-    L->ntiles = (Cout + L->BN - 1) / L->BN;
-    const int taps = L->phase ? 4 : kh * kw;
-    L->nchunks = taps * (cin_packed / CONV_BK);
-    std::vector<float> packed(conv_packed_elems(taps, cin_packed, Cout, L->BN, L->phase ? 4 : 1));
-    conv_pack_host(wf.data(), Cout, Cin, kh, kw, map.data(), cin_packed, L->BN, L->phase, dma_cfg > 0, packed.data());
-    std::vector<float> bias_pad((size_t)L->ntiles * L->BN, 0.f);
-    std::copy(bf.begin(), bf.end(), bias_pad.begin());
-    int rc = upload(c, &L->w, packed);
-    if (rc) return rc;
-    if (w_swizzled) {   // second image of the same weights in the LDS-DMA (XOR-swizzled) layout
-        const int sbn = w_swizzled_bn ? w_swizzled_bn : L->BN;   // N tile of the swizzled image (the consumer kernel's)
-        std::vector<float> ps(conv_packed_elems(taps, cin_packed, Cout, sbn, L->phase ? 4 : 1));
-        conv_pack_host(wf.data(), Cout, Cin, kh, kw, map.data(), cin_packed, sbn, L->phase, true, ps.data());
-        if ((rc = upload(c, w_swizzled, ps))) return rc;
-    }
-    return upload(c, &L->bias, bias_pad);
+    L->ntiles = (f.Cout + L->BN - 1) / L->BN;
+    L->nchunks = (phase ? 4 : f.kh * f.kw) * ((C0_packed + C1_packed) / CONV_BK);
+    if (int rc = upload_conv_image(c, &L->w, f, map, C0_packed + C1_packed, L->BN, mode, dma_cfg > 0)) return rc;
+    return upload_bias(c, &L->bias, f.b, (size_t)L->ntiles * L->BN);
 }
 
-// UpBlock2d conv + BatchNorm -> spatial-patch packing (same fold as build_layer, phase filters pre-summed on the host)
-int build_patch(CtxBase* c, const std::string& conv, const std::string& norm, int C0_real, int C0_packed, int C1_real,
-                int C1_packed, PatchLayer* P) {
-    const int Cin = C0_real + C1_real;
-    const HostTensor *wt = find(c, conv + ".weight"), *bt = find(c, conv + ".bias");
-    const HostTensor *g = find(c, norm + ".weight"), *be = find(c, norm + ".bias"), *mu = find(c, norm + ".running_mean"),
-                     *var = find(c, norm + ".running_var");
-    if (!wt || !bt || !g || !be || !mu || !var || wt->shape.size() != 4 || wt->shape[1] != Cin || wt->shape[2] != 3)
-        return fail(c, EAMM_ERR_KEY, "%s mis-shaped for the patch kernel", conv.c_str());
-    const int Cout = (int)wt->shape[0];
-    std::vector<float> wf(wt->data), bf(Cout);
-    for (int o = 0; o < Cout; ++o) {
-        const double sc = (double)g->data[o] / std::sqrt((double)var->data[o] + 1e-5);
-        bf[o] = (float)(((double)bt->data[o] - (double)mu->data[o]) * sc + (double)be->data[o]);
-        for (size_t i = 0; i < (size_t)Cin * 9; ++i) wf[(size_t)o * Cin * 9 + i] = (float)((double)wt->data[(size_t)o * Cin * 9 + i] * sc);
-    }
+// -> PatchLayer: the spatial-patch kernel of the UpBlock2d convolution (3x3), polyphase or collapsed-phase form
+int pack_patch(CtxBase* c, const HostConv& f, const int* map, int C0_packed, int C1_packed, bool poly, PatchLayer* P) {
     const int cin_packed = C0_packed + C1_packed;
-    std::vector<int> map(cin_packed, -1);
-    for (int i = 0; i < C0_real; ++i) map[i] = i;
-    for (int i = 0; i < C1_real; ++i) map[C0_packed + i] = C0_real + i;
     P->C0 = C0_packed;
     P->C1 = C1_packed;
-    P->Cout = Cout;
-    std::vector<float> bias_pad((size_t)((Cout + 63) / 64) * 64, 0.f);
-    std::copy(bf.begin(), bf.end(), bias_pad.begin());
-    int rc = 0;
-    if (c->patch_poly) {
-        std::vector<float> pp(patch_poly_packed_elems(cin_packed, Cout));
-        patch_poly_pack_host(wf.data(), Cout, Cin, map.data(), cin_packed, pp.data());
-        if ((rc = upload(c, &P->w_poly, pp))) return rc;
-    } else {
-        std::vector<float> packed(patch_packed_elems(cin_packed, Cout));
-        patch_pack_host(wf.data(), Cout, Cin, map.data(), cin_packed, packed.data());
-        if ((rc = upload(c, &P->w, packed))) return rc;
-    }
-    return upload(c, &P->bias, bias_pad);
+    P->Cout = f.Cout;
+    std::vector<float> packed(poly ? patch_poly_packed_elems(cin_packed, f.Cout) : patch_packed_elems(cin_packed, f.Cout));
+    if (poly)
+        patch_poly_pack_host(f.w.data(), f.Cout, f.Cin, map, cin_packed, packed.data());
+    else
+        patch_pack_host(f.w.data(), f.Cout, f.Cin, map, cin_packed, packed.data());
+    if (int rc = upload(c, poly ? &P->w_poly : &P->w, packed)) return rc;
+    return upload_bias(c, &P->bias, f.b, (size_t)((f.Cout + 63) / 64) * 64);
 }
 
+// -> WinoLayer: Winograd-domain weights U = G g G^T of a 3x3 convolution, F(2x2,3x3) (tile 2) or F(4x4,3x3) (tile 4)
+int pack_wino(CtxBase* c, const HostConv& f, int tile, WinoLayer* L) {
+    L->Cin = f.Cin;
+    L->Cout = f.Cout;
+    L->tile = tile;
+    L->BN = tile == 4 ? 64 : 128;
+    L->ntiles = (f.Cout + L->BN - 1) / L->BN;
+    std::vector<float> packed(tile == 4 ? wino4_packed_elems(f.Cout, f.Cin, L->BN) : wino_packed_elems(f.Cout, f.Cin, L->BN));
+    if (tile == 4)
+        wino4_pack_host(f.w.data(), f.Cout, f.Cin, L->BN, packed.data());
+    else
+        wino_pack_host(f.w.data(), f.Cout, f.Cin, L->BN, packed.data());
+    if (int rc = upload(c, &L->u, packed)) return rc;
+    return upload_bias(c, &L->bias, f.b, (size_t)L->ntiles * L->BN);
+}
+
+// conv (+ optional BatchNorm folded behind it) -> packed device layer.
+// MODE_PLAIN: ks x ks convolution.  MODE_ROWSPLIT: ks x 1 convolution with N = (dx, co) (to_rowsplit); the bias is
+// returned in *row_bias instead of being applied by the convolution.  w_swizzled: a second image of the same weights in
+// the LDS-DMA (XOR-swizzled) layout for an N tile of w_swizzled_bn (0: the layer's), the consumer kernel's.
+int build_layer(CtxBase* c, const std::vector<FoldSpec>& parts, int ks, int C0_real, int C0_packed, int C1_real,
+                int C1_packed, ConvLayer* L, LayerMode mode = MODE_PLAIN, std::vector<float>* row_bias = nullptr,
+                int dma_cfg = 0, float** w_swizzled = nullptr, int w_swizzled_bn = 0) {
+    if (mode != MODE_PLAIN && mode != MODE_ROWSPLIT) return fail(c, EAMM_ERR_ARG, "build_layer: plain or row-split layers only");
+    HostConv f;
+    if (int rc = fold_conv(c, parts, ks, C0_real + C1_real, &f)) return rc;
+    if (mode == MODE_ROWSPLIT) {
+        std::vector<float> rb = to_rowsplit(&f);
+        if (row_bias) row_bias->swap(rb);
+    }
+    const std::vector<int> map = channel_map(C0_real, C0_packed, C1_real, C1_packed);
+    if (int rc = pack_conv(c, f, map.data(), C0_packed, C1_packed, MODE_PLAIN, dma_cfg, L)) return rc;
+    if (!w_swizzled) return EAMM_OK;
+    return upload_conv_image(c, w_swizzled, f, map.data(), C0_packed + C1_packed, w_swizzled_bn ? w_swizzled_bn : L->BN,
+                             MODE_PLAIN, true);
+}
+
+// A 3x3 layer (MODE_PLAIN, or MODE_PHASE: the layer consumes the low-resolution input of an UpBlock2d and evaluates
+// "nearest x2 + 3x3" as four 2x2 phase filters) packed for every kernel that may run it (pick(), launch_up())
 int build_set(CtxBase* c, const std::vector<FoldSpec>& parts, int C0_real, int C0_packed, int C1_real, int C1_packed,
               LayerSet* S, LayerMode mode) {
-    int rc = build_layer(c, parts, 3, C0_real, C0_packed, C1_real, C1_packed, &S->base, mode);
+    HostConv f;
+    int rc = fold_conv(c, parts, 3, C0_real + C1_real, &f);
     if (rc) return rc;
+    const std::vector<int> map = channel_map(C0_real, C0_packed, C1_real, C1_packed);
+    if ((rc = pack_conv(c, f, map.data(), C0_packed, C1_packed, mode, 0, &S->base))) return rc;
     const int Cout = S->base.Cout;
     int cfg = 0;
     if (Cout % 256 == 0) cfg = c->dma_cfg_n256;
     else if (Cout % 128 == 0) cfg = c->dma_cfg_n128;
     else if (Cout == 64) cfg = c->dma_cfg_n64;
     if (cfg > 0 && c->dma_min_m >= 0) {
-        rc = build_layer(c, parts, 3, C0_real, C0_packed, C1_real, C1_packed, &S->dma, mode, nullptr, cfg);
-        if (rc) return rc;
+        if ((rc = pack_conv(c, f, map.data(), C0_packed, C1_packed, mode, cfg, &S->dma))) return rc;
         S->has_dma = true;
         if (S->dma.BN == 128 && c->skinny_max_m > 0) {   // same packed weights, small-M tiles (conv_dma_tile ids 4, 5)
             S->skinny32 = S->dma;
@@ -289,91 +338,49 @@ int build_set(CtxBase* c, const std::vector<FoldSpec>& parts, int C0_real, int C
             S->has_skinny = true;
         }
         if (Cout % 256 == 0 && cfg != 1 && c->big_min_m >= 0) {
-            rc = build_layer(c, parts, 3, C0_real, C0_packed, C1_real, C1_packed, &S->big, mode, nullptr, 1);
-            if (rc) return rc;
+            if ((rc = pack_conv(c, f, map.data(), C0_packed, C1_packed, mode, 1, &S->big))) return rc;
             S->has_big = true;
         }
     }
     if (mode == MODE_PHASE && parts.size() == 1 && !parts[0].norm.empty() && (Cout & 3) == 0 && c->patch_min_blocks >= 0) {
-        rc = build_patch(c, parts[0].conv, parts[0].norm, C0_real, C0_packed, C1_real, C1_packed, &S->patch);
-        if (rc) return rc;
+        if ((rc = pack_patch(c, f, map.data(), C0_packed, C1_packed, c->patch_poly != 0, &S->patch))) return rc;
         S->has_patch = true;
     }
     return 0;
 }
 
+// the largest split-K slab any of the set's kernels asks for at M pixels
+size_t set_partial_elems(const LayerSet& S, size_t M) {
+    size_t n = conv_plan(S.base, (int)M).partial_elems;
+    if (S.has_dma) n = std::max(n, conv_plan(S.dma, (int)M).partial_elems);
+    if (S.has_big) n = std::max(n, conv_plan(S.big, (int)M).partial_elems);
+    if (S.has_skinny) n = std::max({n, conv_plan(S.skinny32, (int)M).partial_elems, conv_plan(S.skinny64, (int)M).partial_elems});
+    return n;
+}
 
-
-// Tile choice per launch (measured on MI355X, profiles/r01_convbench_*): M is the per-phase pixel count.
-// conv (+ folded BatchNorm) -> Winograd-domain weights U = G g G^T
+// conv (+ folded BatchNorm) of C -> C channels -> Winograd-domain weights (pack_wino)
 int build_wino(CtxBase* c, const std::string& conv, const std::string& norm, int C, WinoLayer* L, int tile = 2) {
-    const HostTensor *wt = find(c, conv + ".weight"), *bt = find(c, conv + ".bias");
-    if (!wt || !bt || wt->shape.size() != 4 || wt->shape[0] != C || wt->shape[1] != C || wt->shape[2] != 3)
-        return fail(c, EAMM_ERR_KEY, "%s mis-shaped for the Winograd path", conv.c_str());
-    std::vector<float> wf(wt->data), bf(bt->data);
-    if (!norm.empty()) {
-        const HostTensor *g = find(c, norm + ".weight"), *be = find(c, norm + ".bias"),
-                         *mu = find(c, norm + ".running_mean"), *var = find(c, norm + ".running_var");
-        if (!g || !be || !mu || !var) return fail(c, EAMM_ERR_KEY, "BatchNorm entries of %s missing", norm.c_str());
-        for (int o = 0; o < C; ++o) {
-            const double sc = (double)g->data[o] / std::sqrt((double)var->data[o] + 1e-5);
-            bf[o] = (float)(((double)bt->data[o] - (double)mu->data[o]) * sc + (double)be->data[o]);
-            for (size_t i = 0; i < (size_t)C * 9; ++i) wf[(size_t)o * C * 9 + i] = (float)((double)wt->data[(size_t)o * C * 9 + i] * sc);
-        }
-    }
-    L->Cin = C;
-    L->Cout = C;
-    L->tile = tile;
-    L->BN = tile == 4 ? 64 : 128;
-    L->ntiles = (C + L->BN - 1) / L->BN;
-    std::vector<float> packed(tile == 4 ? wino4_packed_elems(C, C, L->BN) : wino_packed_elems(C, C, L->BN));
-    if (tile == 4)
-        wino4_pack_host(wf.data(), C, C, L->BN, packed.data());
-    else
-        wino_pack_host(wf.data(), C, C, L->BN, packed.data());
-    std::vector<float> bias_pad((size_t)L->ntiles * L->BN, 0.f);
-    std::copy(bf.begin(), bf.end(), bias_pad.begin());
-    int rc = upload(c, &L->u, packed);
-    if (rc) return rc;
-    return upload(c, &L->bias, bias_pad);
+    HostConv f;
+    if (int rc = fold_conv(c, {{conv, norm}}, 3, C, &f)) return rc;
+    if (f.Cout != C) return fail(c, EAMM_ERR_KEY, "%s mis-shaped for the Winograd path", conv.c_str());
+    return pack_wino(c, f, tile, L);
 }
 
 // F(4x4,3x3) packing of a convolution whose input and output widths differ (hourglass DownBlock2d: conv -> BatchNorm
 // folded; reference modules/util.py:903-921); input channels Cin_real sit first in a Cin_packed-wide activation
 int build_wino4_rect(CtxBase* c, const std::string& conv, const std::string& norm, int Cin_real, int Cin_packed, WinoLayer* L) {
-    const HostTensor *wt = find(c, conv + ".weight"), *bt = find(c, conv + ".bias");
-    if (!wt || !bt || wt->shape.size() != 4 || wt->shape[1] != Cin_real || wt->shape[2] != 3 || wt->shape[3] != 3 ||
-        Cin_packed < Cin_real || Cin_packed % 64)
-        return fail(c, EAMM_ERR_KEY, "%s mis-shaped for the Winograd path", conv.c_str());
-    const int Cout = (int)wt->shape[0];
-    std::vector<float> wf((size_t)Cout * Cin_packed * 9, 0.f), bf(bt->data);
-    const HostTensor *g = nullptr, *be = nullptr, *mu = nullptr, *var = nullptr;
-    if (!norm.empty()) {
-        g = find(c, norm + ".weight"); be = find(c, norm + ".bias");
-        mu = find(c, norm + ".running_mean"); var = find(c, norm + ".running_var");
-        if (!g || !be || !mu || !var) return fail(c, EAMM_ERR_KEY, "BatchNorm entries of %s missing", norm.c_str());
-    }
-    for (int o = 0; o < Cout; ++o) {
-        const double sc = g ? (double)g->data[o] / std::sqrt((double)var->data[o] + 1e-5) : 1.0;
-        if (g) bf[o] = (float)(((double)bt->data[o] - (double)mu->data[o]) * sc + (double)be->data[o]);
-        for (int ci = 0; ci < Cin_real; ++ci)
-            for (int k = 0; k < 9; ++k)
-                wf[((size_t)o * Cin_packed + ci) * 9 + k] = (float)((double)wt->data[((size_t)o * Cin_real + ci) * 9 + k] * sc);
-    }
-    L->Cin = Cin_packed;
-    L->Cout = Cout;
-    L->tile = 4;
-    L->BN = 64;
-    L->ntiles = (Cout + L->BN - 1) / L->BN;
-    std::vector<float> packed(wino4_packed_elems(Cout, Cin_packed, L->BN));
-    wino4_pack_host(wf.data(), Cout, Cin_packed, L->BN, packed.data());
-    std::vector<float> bias_pad((size_t)L->ntiles * L->BN, 0.f);
-    std::copy(bf.begin(), bf.end(), bias_pad.begin());
-    int rc = upload(c, &L->u, packed);
-    if (rc) return rc;
-    return upload(c, &L->bias, bias_pad);
+    if (Cin_packed < Cin_real || Cin_packed % 64) return fail(c, EAMM_ERR_KEY, "%s mis-shaped for the Winograd path", conv.c_str());
+    HostConv f;
+    if (int rc = fold_conv(c, {{conv, norm}}, 3, Cin_real, &f)) return rc;
+    HostConv p = f;   // zero filters on the padding channels
+    p.Cin = Cin_packed;
+    p.w.assign((size_t)f.Cout * Cin_packed * 9, 0.f);
+    for (int o = 0; o < f.Cout; ++o)
+        std::copy_n(f.w.begin() + (size_t)o * Cin_real * 9, (size_t)Cin_real * 9, p.w.begin() + (size_t)o * Cin_packed * 9);
+    return pack_wino(c, p, 4, L);
 }
 
+// Tile choice per launch (measured on MI355X, profiles/r01_convbench_*): M is the per-phase pixel count.
 const ConvLayer& pick(const CtxBase* c, const LayerSet& S, size_t M) {
     // skinny GEMMs (deep hourglass levels at small batches): the weight stream is the cost, so tiles without padding rows
     if (S.has_skinny && M <= (size_t)c->skinny_max_m) return M <= 32 ? S.skinny32 : S.skinny64;

@@ -202,6 +202,208 @@ int pad_state_dict(eamm_ctx* c) {
     return 0;
 }
 
+// ---- operator entries (eamm_op_*) ------------------------------------------------------------------
+
+// `iters` back-to-back run()s between two HIP events on `s`; *avg_ms gets their mean only when every step succeeded
+template <typename Run>
+hipError_t time_launches(hipStream_t s, int iters, float* avg_ms, Run run) {
+    if (iters <= 0 || !avg_ms) return hipSuccess;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipError_t e = hipEventCreate(&e0);
+    if (e == hipSuccess) e = hipEventCreate(&e1);
+    if (e == hipSuccess) e = hipEventRecord(e0, s);
+    for (int i = 0; i < iters && e == hipSuccess; ++i) e = run();
+    if (e == hipSuccess) e = hipEventRecord(e1, s);
+    if (e == hipSuccess) e = hipEventSynchronize(e1);
+    float ms = 0.f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+    if (e == hipSuccess) *avg_ms = ms / iters;
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    return e;
+}
+
+// An operator call's temporary device buffers (dev_alloc / upload): freed on every path, once the caller's stream is done
+// with them.  Errors land in `err`; the entry hands them on to eamm_last_error(NULL).
+struct OpBuffers : CtxBase {
+    hipStream_t s;
+    OpBuffers(int dev, hipStream_t st) : s(st) { device = dev; }
+    ~OpBuffers() {
+        if (owned.empty()) return;
+        (void)hipStreamSynchronize(s);
+        for (void* p : owned) (void)hipFree(p);
+    }
+};
+
+struct ConvOp {   // eamm_op_conv's arguments
+    const float *in0, *in1;
+    int C0, C1, B, Hin, Win, up;
+    const float *w, *b;
+    int Cout, kh, kw, act, pool;
+    const float* resid;
+    int splitk, tile_n;
+    float* out;
+    int iters;
+    float* avg_ms;
+    hipStream_t s;
+};
+
+// the caller's OIHW filter [Cout][Cin][kh][kw] (BatchNorm folded) and, with_bias, its bias [Cout]
+HostConv op_weights(const ConvOp& a, int Cin, bool with_bias = true) {
+    HostConv f;
+    f.Cout = a.Cout;
+    f.Cin = Cin;
+    f.kh = a.kh;
+    f.kw = a.kw;
+    f.w.assign(a.w, a.w + (size_t)a.Cout * Cin * a.kh * a.kw);
+    if (with_bias) f.b.assign(a.b, a.b + a.Cout);
+    return f;
+}
+
+// 4002: the final layer whole (7x7, 3 output channels, bias, sigmoid -> NCHW) on the fused column-patch kernel, with the
+// row-split weights of the engine's final_w_swz
+int op_conv_final(OpBuffers* t, const ConvOp& a) {
+    if (a.kh != 7 || a.kw != 7 || a.Cout != 3 || a.act != 2 || a.up || a.pool || a.resid || a.C1 || a.C0 % 32 || a.C0 > 64 || a.C0 < 32)
+        return fail(t, EAMM_ERR_ARG, "eamm_op_conv: unsupported fused final-layer configuration");
+    HostConv f = op_weights(a, a.C0);
+    const std::vector<float> bias = to_rowsplit(&f);
+    float *w = nullptr, *b = nullptr;
+    int rc = upload_conv_image(t, &w, f, nullptr, a.C0, conv_tile_n(f.Cout), MODE_PLAIN, true);
+    if (rc || (rc = upload(t, &b, bias))) return rc;
+    auto fused_final = [&]() { return conv_col7_fused_launch(a.in0, a.C0, a.B, a.Hin, a.Win, w, b, a.out, a.s); };
+    HIP_TRY(t, fused_final());
+    HIP_TRY(t, time_launches(a.s, a.iters, a.avg_ms, fused_final));
+    return EAMM_OK;
+}
+
+// column-patch kernels of the 7x1 convolutions: 4000 final layer (Cout = the 32-float pixel stride, weights resident), 4001
+// flow head (two inputs, Cout = 96, streamed weights); the weights come row-split, no bias (the gather kernels add it)
+int op_conv_col7(OpBuffers* t, const ConvOp& a) {
+    const bool streamed = a.tile_n == 4001;
+    const int bn = streamed ? 96 : 32;
+    if (a.kh != 7 || a.kw != 1 || a.up || a.pool || a.resid || a.splitk > 1 || a.Cout != bn || a.act != 0 || a.C0 % 32 || a.C1 % 32 ||
+        (!streamed && (a.C1 || a.C0 > 64)))
+        return fail(t, EAMM_ERR_ARG, "eamm_op_conv: unsupported column-patch configuration");
+    float* w = nullptr;
+    if (int rc = upload_conv_image(t, &w, op_weights(a, a.C0 + a.C1, false), nullptr, a.C0 + a.C1, bn, MODE_PLAIN, true)) return rc;
+    auto col7 = [&]() {
+        return streamed ? conv_col7s_launch(a.in0, a.C0, a.in1, a.C1, a.B, a.Hin, a.Win, w, 3, a.out, 96, a.s)
+                        : conv_col7_launch(a.in0, a.C0, a.B, a.Hin, a.Win, w, a.out, a.s);
+    };
+    HIP_TRY(t, col7());
+    HIP_TRY(t, time_launches(a.s, a.iters, a.avg_ms, col7));
+    return EAMM_OK;
+}
+
+// spatial-patch kernels of the up-convolution: 3000 collapsed-phase form, 3003 polyphase minimal-filtering form (splitk > 1:
+// its channel reduction over that many workgroups)
+int op_conv_patch(OpBuffers* t, const ConvOp& a) {
+    const bool pp = a.tile_n == 3003;
+    const int psplit = a.splitk > 1 ? a.splitk : 1;
+    if (a.kh != 3 || a.kw != 3 || !a.up || a.pool || a.resid || (a.Cout & 3) || (psplit > 1 && (!pp || ((a.C0 + a.C1) / 32) % psplit)))
+        return fail(t, EAMM_ERR_ARG, "eamm_op_conv: unsupported patch-kernel configuration");
+    PatchLayer P;
+    float* ppart = nullptr;
+    const size_t ppart_elems = psplit > 1 ? (size_t)psplit * a.B * 4 * a.Hin * a.Win * a.Cout : 0;
+    int rc = pack_patch(t, op_weights(a, a.C0 + a.C1), nullptr, a.C0, a.C1, pp, &P);
+    if (rc || (psplit > 1 && (rc = dev_alloc(t, &ppart, ppart_elems)))) return rc;
+    auto patch = [&]() {
+        return pp ? patch_poly_launch(P, a.in0, a.in1, a.B, a.Hin, a.Win, a.act, a.out, a.s, psplit, ppart, ppart_elems)
+                  : patch_phase_launch(P, a.in0, a.in1, a.B, a.Hin, a.Win, a.act, a.out, a.s);
+    };
+    HIP_TRY(t, patch());
+    HIP_TRY(t, time_launches(a.s, a.iters, a.avg_ms, patch));
+    return EAMM_OK;
+}
+
+// Winograd: input transform + GEMM; 2000 + variant F(2x2,3x3), 2100 + variant F(4x4,3x3), 2150 + groups (2, 3, 6, 12):
+// F(4x4,3x3) with the transform-point rows split over workgroups + output-transform kernel
+int op_conv_wino(OpBuffers* t, const ConvOp& a) {
+    const bool w4 = a.tile_n >= 2100;
+    const int w4_groups = a.tile_n >= 2150 ? a.tile_n - 2150 : 1;
+    if (a.kh != 3 || a.kw != 3 || a.up || (a.pool && (w4_groups == 1 || a.resid)) || a.C1 || a.splitk > 1 || a.C0 % 64 || (a.Cout & 3) ||
+        (w4 && ((a.Hin & 3) || (a.Win & 3))))
+        return fail(t, EAMM_ERR_ARG, "eamm_op_conv: unsupported Winograd configuration");
+    WinoLayer W;
+    float *V = nullptr, *Zb = nullptr;
+    int rc = pack_wino(t, op_weights(a, a.C0), w4 ? 4 : 2, &W);
+    if (rc || (rc = dev_alloc(t, &V, (size_t)16 * a.B * (a.Hin / 2) * (a.Win / 2) * a.C0))) return rc;
+    // (+ 4: 16 bytes of slack)
+    if ((rc = dev_alloc(t, &Zb, (size_t)(w4_groups == 12 ? 48 : 24) * a.B * ((a.Hin + 3) / 4) * ((a.Win + 3) / 4) * a.Cout + 4))) return rc;
+    // timing-mode knob: EAMM_OP_WINO_PART = 1 times the input transform alone, 2 the GEMM alone
+    const int part = env_int("EAMM_OP_WINO_PART", 0);
+    bool timing = false;
+    auto winograd = [&]() {
+        const bool tr = !timing || part != 2, gm = !timing || part != 1;
+        hipError_t e = hipSuccess;
+        if (w4) {
+            if (tr) e = wino4_transform_launch(a.in0, nullptr, nullptr, a.B, a.Hin, a.Win, a.C0, V, a.s);
+            if (e != hipSuccess || !gm) return e;
+            return wino4_gemm_launch(W, V, a.B, a.Hin, a.Win, a.act, a.resid, a.out, a.s, w4_groups > 1 ? 0 : a.tile_n - 2100, w4_groups,
+                                     Zb, a.pool);
+        }
+        if (tr) e = wino_transform_launch(a.in0, nullptr, nullptr, a.B, a.Hin, a.Win, a.C0, V, a.s);
+        if (e != hipSuccess || !gm) return e;
+        return wino_gemm_launch(W, V, a.B, a.Hin, a.Win, a.act, a.resid, a.out, a.s, a.tile_n - 2000);
+    };
+    HIP_TRY(t, winograd());
+    timing = true;
+    HIP_TRY(t, time_launches(a.s, a.iters, a.avg_ms, winograd));
+    return EAMM_OK;
+}
+
+// the implicit GEMM: tile_n 0 automatic, 32 / 64 / 128 the register-staged 128 x tile_n kernel, 1000 + id an LDS-DMA tile
+int op_conv_gemm(OpBuffers* t, const ConvOp& a) {
+    const int dma_cfg = a.tile_n > 1000 ? a.tile_n - 1000 : 0;
+    int BM = 0, BN = a.tile_n > 0 ? a.tile_n : conv_tile_n(a.Cout);
+    if (dma_cfg) {
+        if (!conv_dma_tile(dma_cfg, &BM, &BN) || a.kw == 1 || a.kh == 7) return fail(t, EAMM_ERR_ARG, "unknown / unsupported dma tile");
+    } else if (BN != 32 && BN != 64 && BN != 128) {
+        return fail(t, EAMM_ERR_ARG, "tile_n must be 32/64/128 or 1000+dma id");
+    }
+    ConvLayer L;
+    int rc = pack_conv(t, op_weights(a, a.C0 + a.C1), nullptr, a.C0, a.C1, a.up ? MODE_PHASE : MODE_PLAIN, dma_cfg, &L, dma_cfg ? 0 : BN);
+    if (rc) return rc;
+    ConvIO io{};
+    io.in0 = a.in0;
+    io.in1 = a.C1 ? a.in1 : nullptr;
+    io.B = a.B;
+    io.Hin = a.Hin;
+    io.Win = a.Win;
+    io.act = a.act;
+    io.pool = a.pool;
+    io.resid = a.resid;
+    io.out = a.out;
+    io.partial_cap = conv_plan(L, a.B * a.Hin * a.Win, a.splitk).partial_elems;
+    if (io.partial_cap && (rc = dev_alloc(t, &io.partial, io.partial_cap))) return rc;
+    auto gemm = [&]() { return conv_launch(L, io, a.s, a.splitk); };
+    HIP_TRY(t, gemm());
+    HIP_TRY(t, time_launches(a.s, a.iters, a.avg_ms, gemm));
+    return EAMM_OK;
+}
+
+// eamm_op_conv: the family of tile_n (include/eamm_hip.h), then the caller's stream drained
+int op_conv_run(OpBuffers* t, const ConvOp& a) {
+    int rc;
+    if (a.tile_n == 4002) rc = op_conv_final(t, a);
+    else if (a.tile_n == 4000 || a.tile_n == 4001) rc = op_conv_col7(t, a);
+    else if (a.tile_n == 3000 || a.tile_n == 3003) rc = op_conv_patch(t, a);
+    else if (a.tile_n >= 2000 && a.tile_n < 2200) rc = op_conv_wino(t, a);
+    else rc = op_conv_gemm(t, a);
+    if (rc) return rc;
+    HIP_TRY(t, hipStreamSynchronize(a.s));
+    return EAMM_OK;
+}
+
+// The preamble and return of an eamm_op_* entry: argument check, the device made current for the call, the caller's stream
+#define OP_ENTRY(cond, msg)                                                                      \
+    if (cond) return fail(nullptr, EAMM_ERR_ARG, msg);                                           \
+    DeviceGuard guard(device);                                                                   \
+    if (guard.status != hipSuccess) return fail(nullptr, EAMM_ERR_HIP, "hipSetDevice failed");   \
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream_)
+#define OP_DONE(e, name) \
+    return (e) == hipSuccess ? EAMM_OK : fail(nullptr, EAMM_ERR_HIP, name " failed: %s", hipGetErrorString(e))
+
 }  // namespace
 
 // -------------------------------------------------------------------------------------------------
@@ -424,22 +626,14 @@ int eamm_finalize_weights(eamm_ctx* c) {
     }
     // generator encoder
     if ((rc = build_layer(c, {{"first.conv", nm("first.norm")}}, 7, c->Cpl, c->Csrc, 0, 0, &c->first))) return rc;
-    if (c->first7 && c->Cpl == 3 && first7_supported(c->down_c[0])) {   // K = 147 (196 with the zero rows) instead of 49 x 32
-        const HostTensor *wt = find(c, "first.conv.weight"), *bt = find(c, "first.conv.bias"), *gm = find(c, "first.norm.weight"),
-                         *be = find(c, "first.norm.bias"), *mu = find(c, "first.norm.running_mean"), *vr = find(c, "first.norm.running_var");
-        const int co = c->down_c[0];
-        if (wt && bt && gm && be && mu && vr && wt->shape.size() == 4 && wt->shape[0] == co && wt->shape[1] == 3 &&
-            wt->shape[2] == 7 && wt->shape[3] == 7) {
-            std::vector<float> wf(wt->data), bf(co), packed((size_t)196 * co);
-            for (int o = 0; o < co; ++o) {
-                const double sc = (double)gm->data[o] / std::sqrt((double)vr->data[o] + 1e-5);
-                bf[o] = (float)(((double)bt->data[o] - (double)mu->data[o]) * sc + (double)be->data[o]);
-                for (int i = 0; i < 147; ++i) wf[(size_t)o * 147 + i] = (float)((double)wt->data[(size_t)o * 147 + i] * sc);
-            }
-            first7_pack_host(wf.data(), co, packed.data());
-            if ((rc = upload(c, &c->first7_w, packed))) return rc;
-            if ((rc = upload(c, &c->first7_bias, bf))) return rc;
-        }
+    // K = 147 (196 with the zero rows) instead of 49 x 32; a first layer of another width keeps the generic kernel
+    if (c->first7 && c->Cpl == 3 && first7_supported(c->down_c[0]) && c->first.Cout == c->down_c[0]) {
+        HostConv f;   // (build_layer has just checked these keys: first7 is off in training mode, where nm() drops the norm)
+        if ((rc = fold_conv(c, {{"first.conv", "first.norm"}}, 7, 3, &f))) return rc;
+        std::vector<float> packed((size_t)196 * f.Cout);
+        first7_pack_host(f.w.data(), f.Cout, packed.data());
+        if ((rc = upload(c, &c->first7_w, packed))) return rc;
+        if ((rc = upload(c, &c->first7_bias, f.b))) return rc;
     }
     c->down.resize(c->nd);
     for (int i = 0; i < c->nd; ++i) {
@@ -474,6 +668,8 @@ int eamm_finalize_weights(eamm_ctx* c) {
         if ((int)gm->numel() != c->Cb || (int)bt->numel() != c->Cb || (int)mu->numel() != c->Cb ||
             (int)vr->numel() != c->Cb)
             return fail(c, EAMM_ERR_KEY, "%s.norm1 mis-shaped", r.c_str());
+        // (not fold_norm with a zero conv bias: (0 - mu) * s + beta is +0 where beta - mu * s is -0, for mu = +0 and
+        // beta = -0; everywhere else the two agree bit for bit)
         std::vector<float> s(c->Cb), t(c->Cb);
         for (int ch = 0; ch < c->Cb; ++ch) {
             const double sc = (double)gm->data[ch] / std::sqrt((double)vr->data[ch] + 1e-5);
@@ -616,15 +812,7 @@ int eamm_finalize_weights(eamm_ctx* c) {
     {
         size_t need = 0;
         auto upd1 = [&](const ConvLayer& L, size_t M) { need = std::max(need, conv_plan(L, (int)M).partial_elems); };
-        auto upd = [&](const LayerSet& S, size_t M) {
-            upd1(S.base, M);
-            if (S.has_dma) upd1(S.dma, M);
-            if (S.has_big) upd1(S.big, M);
-            if (S.has_skinny) {
-                upd1(S.skinny32, M);
-                upd1(S.skinny64, M);
-            }
-        };
+        auto upd = [&](const LayerSet& S, size_t M) { need = std::max(need, set_partial_elems(S, M)); };
         for (size_t f = 1; f <= S; ++f) {
             upd1(c->first, f * HW);
             for (int i = 0; i < c->nd; ++i) upd(c->down[i], f * (HW >> (2 * i)));
@@ -1550,336 +1738,40 @@ int eamm_op_conv(int device, const float* in0, int C0, const float* in1, int C1,
                  const float* w_host, const float* b_host, int Cout, int kh, int kw, int act, int pool,
                  const float* resid, int splitk, int tile_n, float* out, int iters, float* avg_ms, void* stream_) {
     const bool shape_ok = (kh == 3 && kw == 3) || (kh == 7 && kw == 7) || (kh == 7 && kw == 1);
-    if (!in0 || !w_host || !b_host || !out || !shape_ok || C0 % CONV_BK || C1 % CONV_BK || (up && (kh != 3 || kw != 3)))
-        return fail(nullptr, EAMM_ERR_ARG, "eamm_op_conv: bad argument");
-    DeviceGuard guard(device);
-    if (guard.status != hipSuccess) return fail(nullptr, EAMM_ERR_HIP, "hipSetDevice failed");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream_);
-    if (tile_n == 4002) {   // the final layer whole: 7x7, 3 output channels, bias, sigmoid -> NCHW, on the fused column-patch kernel
-        if (kh != 7 || kw != 7 || Cout != 3 || act != 2 || up || pool || resid || C1 || C0 % 32 || C0 > 64 || C0 < 32)
-            return fail(nullptr, EAMM_ERR_ARG, "eamm_op_conv: unsupported fused final-layer configuration");
-        std::vector<float> wr((size_t)21 * C0 * 7), packed(conv_packed_elems(7, C0, 21, 32, 1));
-        for (int dx = 0; dx < 7; ++dx)          // w'[dx*3+co][c][dy] = w[co][c][dy][dx]  (MODE_ROWSPLIT of build_layer)
-            for (int co = 0; co < 3; ++co)
-                for (int ci = 0; ci < C0; ++ci)
-                    for (int dy = 0; dy < 7; ++dy)
-                        wr[((size_t)(dx * 3 + co) * C0 + ci) * 7 + dy] = w_host[((size_t)co * C0 + ci) * 49 + dy * 7 + dx];
-        conv_pack_host(wr.data(), 21, C0, 7, 1, nullptr, C0, 32, false, true, packed.data());
-        float *wd = nullptr, *bd = nullptr;
-        hipError_t e = hipMalloc((void**)&wd, packed.size() * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc((void**)&bd, 3 * sizeof(float));
-        if (e == hipSuccess) e = hipMemcpy(wd, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(bd, b_host, 3 * sizeof(float), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = conv_col7_fused_launch(in0, C0, B, Hin, Win, wd, bd, out, s);
-        if (e == hipSuccess && iters > 0 && avg_ms) {
-            hipEvent_t e0, e1;
-            (void)hipEventCreate(&e0);
-            (void)hipEventCreate(&e1);
-            (void)hipEventRecord(e0, s);
-            for (int i = 0; i < iters && e == hipSuccess; ++i) e = conv_col7_fused_launch(in0, C0, B, Hin, Win, wd, bd, out, s);
-            (void)hipEventRecord(e1, s);
-            (void)hipEventSynchronize(e1);
-            float ms = 0.f;
-            (void)hipEventElapsedTime(&ms, e0, e1);
-            *avg_ms = ms / iters;
-            (void)hipEventDestroy(e0);
-            (void)hipEventDestroy(e1);
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (wd) (void)hipFree(wd);
-        if (bd) (void)hipFree(bd);
-        return e == hipSuccess ? EAMM_OK : fail(nullptr, EAMM_ERR_HIP, "fused final layer failed: %s", hipGetErrorString(e));
-    }
-    if (tile_n == 4000 || tile_n == 4001) {  // column-patch kernels of the 7x1 convolutions: 4000 final layer (Cout = the 32-float
-        // pixel stride, weights resident), 4001 flow head (two inputs, Cout = 96, streamed weights); no bias (the gather kernels add it)
-        const bool streamed = tile_n == 4001;
-        const int bn = streamed ? 96 : 32;
-        if (kh != 7 || kw != 1 || up || pool || resid || splitk > 1 || Cout != bn || act != 0 || C0 % 32 || C1 % 32 ||
-            (!streamed && (C1 || C0 > 64)))
-            return fail(nullptr, EAMM_ERR_ARG, "eamm_op_conv: unsupported column-patch configuration");
-        std::vector<float> packed(conv_packed_elems(7, C0 + C1, bn, bn, 1));
-        conv_pack_host(w_host, bn, C0 + C1, 7, 1, nullptr, C0 + C1, bn, false, true, packed.data());
-        float* wd = nullptr;
-        int rc = EAMM_OK;
-        auto bad = [&](hipError_t e, const char* what) {
-            if (e != hipSuccess) rc = fail(nullptr, EAMM_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
-            return e != hipSuccess;
-        };
-        if (!bad(hipMalloc((void**)&wd, packed.size() * sizeof(float)), "hipMalloc") &&
-            !bad(hipMemcpy(wd, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy")) {
-            auto run = [&]() {
-                return streamed ? conv_col7s_launch(in0, C0, in1, C1, B, Hin, Win, wd, 3, out, 96, s)
-                                : conv_col7_launch(in0, C0, B, Hin, Win, wd, out, s);
-            };
-            if (!bad(run(), "col7 launch") && iters > 0 && avg_ms) {
-                hipEvent_t e0, e1;
-                (void)hipEventCreate(&e0);
-                (void)hipEventCreate(&e1);
-                (void)hipEventRecord(e0, s);
-                for (int i = 0; i < iters; ++i) (void)run();
-                (void)hipEventRecord(e1, s);
-                (void)hipEventSynchronize(e1);
-                float ms = 0.f;
-                (void)hipEventElapsedTime(&ms, e0, e1);
-                *avg_ms = ms / iters;
-                (void)hipEventDestroy(e0);
-                (void)hipEventDestroy(e1);
-            }
-            bad(hipStreamSynchronize(s), "hipStreamSynchronize");
-        }
-        if (wd) (void)hipFree(wd);
-        return rc;   // bias is not applied here (the gather kernel adds it in the pipeline): callers pass zeros
-    }
-    if (tile_n == 3000 || tile_n == 3003) {   // spatial-patch kernels for the up-convolution: 3000 collapsed-phase form, 3003 polyphase minimal-filtering form
-        const bool pp = tile_n == 3003;
-        const int psplit = splitk > 1 ? splitk : 1;   // polyphase form only: the channel reduction over that many workgroups
-        if (kh != 3 || kw != 3 || !up || pool || resid || (Cout & 3) || (psplit > 1 && (!pp || ((C0 + C1) / 32) % psplit)))
-            return fail(nullptr, EAMM_ERR_ARG, "eamm_op_conv: unsupported patch-kernel configuration");
-        float* ppart = nullptr;
-        const size_t ppart_elems = psplit > 1 ? (size_t)psplit * B * 4 * Hin * Win * Cout : 0;
-        PatchLayer P;
-        P.C0 = C0;
-        P.C1 = C1;
-        P.Cout = Cout;
-        std::vector<float> packed(pp ? patch_poly_packed_elems(C0 + C1, Cout) : patch_packed_elems(C0 + C1, Cout));
-        std::vector<float> bias((size_t)((Cout + 63) / 64) * 64, 0.f);
-        if (pp) patch_poly_pack_host(w_host, Cout, C0 + C1, nullptr, C0 + C1, packed.data());
-        else patch_pack_host(w_host, Cout, C0 + C1, nullptr, C0 + C1, packed.data());
-        std::copy(b_host, b_host + Cout, bias.begin());
-        float** wslot = pp ? &P.w_poly : &P.w;
-        int rc = EAMM_OK;
-        auto bad = [&](hipError_t e, const char* what) {
-            if (e != hipSuccess) rc = fail(nullptr, EAMM_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
-            return e != hipSuccess;
-        };
-        if (!bad(hipMalloc((void**)wslot, packed.size() * sizeof(float)), "hipMalloc") &&
-            !bad(hipMalloc((void**)&P.bias, bias.size() * sizeof(float)), "hipMalloc") &&
-            !bad(hipMemcpy(*wslot, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy") &&
-            !bad(hipMemcpy(P.bias, bias.data(), bias.size() * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy") &&
-            (psplit == 1 || !bad(hipMalloc((void**)&ppart, ppart_elems * sizeof(float)), "hipMalloc"))) {
-            auto run = [&]() {
-                return pp ? patch_poly_launch(P, in0, in1, B, Hin, Win, act, out, s, psplit, ppart, ppart_elems)
-                          : patch_phase_launch(P, in0, in1, B, Hin, Win, act, out, s);
-            };
-            if (!bad(run(), "patch launch") && iters > 0 && avg_ms) {
-                hipEvent_t e0, e1;
-                (void)hipEventCreate(&e0);
-                (void)hipEventCreate(&e1);
-                (void)hipEventRecord(e0, s);
-                for (int i = 0; i < iters; ++i) (void)run();
-                (void)hipEventRecord(e1, s);
-                (void)hipEventSynchronize(e1);
-                float ms = 0.f;
-                (void)hipEventElapsedTime(&ms, e0, e1);
-                *avg_ms = ms / iters;
-                (void)hipEventDestroy(e0);
-                (void)hipEventDestroy(e1);
-            }
-            bad(hipStreamSynchronize(s), "hipStreamSynchronize");
-        }
-        if (P.w) (void)hipFree(P.w);
-        if (P.w_poly) (void)hipFree(P.w_poly);
-        if (ppart) (void)hipFree(ppart);
-        if (P.bias) (void)hipFree(P.bias);
-        return rc;
-    }
-    if (tile_n >= 2000 && tile_n < 2200) {  // Winograd: input transform + GEMM; 2000 + variant F(2x2,3x3), 2100 + variant F(4x4,3x3),
-        // 2150 + groups (2, 3, 6): F(4x4,3x3) with the transform-point rows split over workgroups + output-transform kernel
-        const bool w4 = tile_n >= 2100;
-        const int w4_groups = tile_n >= 2150 ? tile_n - 2150 : 1;
-        if (kh != 3 || kw != 3 || up || (pool && (w4_groups == 1 || resid)) || C1 || splitk > 1 || C0 % 64 || (Cout & 3) ||
-            (w4 && ((Hin & 3) || (Win & 3))))
-            return fail(nullptr, EAMM_ERR_ARG, "eamm_op_conv: unsupported Winograd configuration");
-        WinoLayer W;
-        W.Cin = C0;
-        W.Cout = Cout;
-        W.tile = w4 ? 4 : 2;
-        W.BN = w4 ? 64 : 128;
-        W.ntiles = (Cout + W.BN - 1) / W.BN;
-        std::vector<float> packed(w4 ? wino4_packed_elems(Cout, C0, W.BN) : wino_packed_elems(Cout, C0, W.BN)),
-            bias((size_t)W.ntiles * W.BN, 0.f);
-        if (w4)
-            wino4_pack_host(w_host, Cout, C0, W.BN, packed.data());
-        else
-            wino_pack_host(w_host, Cout, C0, W.BN, packed.data());
-        std::copy(b_host, b_host + Cout, bias.begin());
-        float *V = nullptr, *Zb = nullptr;
-        int rc = EAMM_OK;
-        auto done = [&](hipError_t e, const char* what) {
-            if (e != hipSuccess) rc = fail(nullptr, EAMM_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
-            return e != hipSuccess;
-        };
-        const size_t vel = (size_t)16 * B * (Hin / 2) * (Win / 2) * C0;
-        if (!done(hipMalloc((void**)&W.u, packed.size() * sizeof(float)), "hipMalloc") &&
-            !done(hipMalloc((void**)&W.bias, bias.size() * sizeof(float)), "hipMalloc") &&
-            !done(hipMalloc((void**)&V, vel * sizeof(float)), "hipMalloc") &&
-            !done(hipMalloc((void**)&Zb, (size_t)(w4_groups == 12 ? 48 : 24) * B * ((Hin + 3) / 4) * ((Win + 3) / 4) * Cout * sizeof(float) + 16), "hipMalloc") &&
-            !done(hipMemcpy(W.u, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy") &&
-            !done(hipMemcpy(W.bias, bias.data(), bias.size() * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy")) {
-            // timing-mode knob: EAMM_OP_WINO_PART = 1 times the input transform alone, 2 the GEMM alone
-            int part = env_int("EAMM_OP_WINO_PART", 0);
-            bool timing = false;
-            auto run = [&]() {
-                const bool tr = !timing || part != 2, gm = !timing || part != 1;
-                hipError_t e = hipSuccess;
-                if (w4) {
-                    if (tr) e = wino4_transform_launch(in0, nullptr, nullptr, B, Hin, Win, C0, V, s);
-                    if (e != hipSuccess || !gm) return e;
-                    return wino4_gemm_launch(W, V, B, Hin, Win, act, resid, out, s, w4_groups > 1 ? 0 : tile_n - 2100, w4_groups, Zb, pool);
-                }
-                if (tr) e = wino_transform_launch(in0, nullptr, nullptr, B, Hin, Win, C0, V, s);
-                if (e != hipSuccess || !gm) return e;
-                return wino_gemm_launch(W, V, B, Hin, Win, act, resid, out, s, tile_n - 2000);
-            };
-            if (!done(run(), "winograd launch") && iters > 0 && avg_ms) {
-                timing = true;
-                hipEvent_t e0, e1;
-                (void)hipEventCreate(&e0);
-                (void)hipEventCreate(&e1);
-                (void)hipEventRecord(e0, s);
-                for (int i = 0; i < iters; ++i) (void)run();
-                (void)hipEventRecord(e1, s);
-                (void)hipEventSynchronize(e1);
-                float ms = 0.f;
-                (void)hipEventElapsedTime(&ms, e0, e1);
-                *avg_ms = ms / iters;
-                (void)hipEventDestroy(e0);
-                (void)hipEventDestroy(e1);
-            }
-            done(hipStreamSynchronize(s), "hipStreamSynchronize");
-        }
-        if (W.u) (void)hipFree(W.u);
-        if (W.bias) (void)hipFree(W.bias);
-        if (V) (void)hipFree(V);
-        if (Zb) (void)hipFree(Zb);
-        return rc;
-    }
-    ConvLayer L;
-    L.kh = kh;
-    L.kw = kw;
-    L.phase = up != 0;
-    L.C0 = C0;
-    L.C1 = C1;
-    L.Cout = Cout;
-    L.BN = tile_n > 0 ? tile_n : conv_tile_n(Cout);
-    if (tile_n > 1000) {  // 1000 + id selects an LDS-DMA big-tile configuration
-        L.dma_cfg = tile_n - 1000;
-        if (!conv_dma_tile(L.dma_cfg, &L.BM, &L.BN) || kw == 1 || kh == 7)
-            return fail(nullptr, EAMM_ERR_ARG, "unknown / unsupported dma tile");
-    } else if (L.BN != 32 && L.BN != 64 && L.BN != 128) {
-        return fail(nullptr, EAMM_ERR_ARG, "tile_n must be 32/64/128 or 1000+dma id");
-    }
-    L.ntiles = (Cout + L.BN - 1) / L.BN;
-    const int taps = L.phase ? 4 : kh * kw;
-    L.nchunks = taps * ((C0 + C1) / CONV_BK);
-    std::vector<float> packed(conv_packed_elems(taps, C0 + C1, Cout, L.BN, L.phase ? 4 : 1));
-    conv_pack_host(w_host, Cout, C0 + C1, kh, kw, nullptr, C0 + C1, L.BN, L.phase, L.dma_cfg > 0, packed.data());
-    std::vector<float> bias((size_t)L.ntiles * L.BN, 0.f);
-    std::copy(b_host, b_host + Cout, bias.begin());
-    int rc = EAMM_OK;
-    float* partial = nullptr;
-    auto cleanup = [&]() {
-        (void)hipStreamSynchronize(s);
-        if (L.w) (void)hipFree(L.w);
-        if (L.bias) (void)hipFree(L.bias);
-        if (partial) (void)hipFree(partial);
-    };
-#define OP_TRY(expr)                                                                              \
-    do {                                                                                          \
-        hipError_t _e = (expr);                                                                   \
-        if (_e != hipSuccess) {                                                                   \
-            rc = fail(nullptr, EAMM_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e));      \
-            cleanup();                                                                            \
-            return rc;                                                                            \
-        }                                                                                         \
-    } while (0)
-    OP_TRY(hipMalloc((void**)&L.w, packed.size() * sizeof(float)));
-    OP_TRY(hipMalloc((void**)&L.bias, bias.size() * sizeof(float)));
-    OP_TRY(hipMemcpy(L.w, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
-    OP_TRY(hipMemcpy(L.bias, bias.data(), bias.size() * sizeof(float), hipMemcpyHostToDevice));
-    const int M = B * Hin * Win;
-    const ConvPlan pl = conv_plan(L, M, splitk);
-    if (pl.partial_elems) OP_TRY(hipMalloc((void**)&partial, pl.partial_elems * sizeof(float)));
-    ConvIO io{};
-    io.in0 = in0;
-    io.in1 = C1 ? in1 : nullptr;
-    io.B = B;
-    io.Hin = Hin;
-    io.Win = Win;
-    io.act = act;
-    io.pool = pool;
-    io.resid = resid;
-    io.out = out;
-    io.partial = partial;
-    io.partial_cap = pl.partial_elems;
-    OP_TRY(conv_launch(L, io, s, splitk));
-    if (iters > 0 && avg_ms) {  // kernel timing: `iters` back-to-back launches between two HIP events on `s`
-        hipEvent_t e0, e1;
-        OP_TRY(hipEventCreate(&e0));
-        OP_TRY(hipEventCreate(&e1));
-        OP_TRY(hipEventRecord(e0, s));
-        for (int i = 0; i < iters; ++i) OP_TRY(conv_launch(L, io, s, splitk));
-        OP_TRY(hipEventRecord(e1, s));
-        OP_TRY(hipEventSynchronize(e1));
-        float ms = 0.f;
-        OP_TRY(hipEventElapsedTime(&ms, e0, e1));
-        *avg_ms = ms / iters;
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-    }
-    cleanup();
-#undef OP_TRY
+    OP_ENTRY(!in0 || !w_host || !b_host || !out || !shape_ok || C0 % CONV_BK || C1 % CONV_BK || (up && (kh != 3 || kw != 3)),
+             "eamm_op_conv: bad argument");
+    const ConvOp a{in0, in1, C0, C1, B, Hin, Win, up, w_host, b_host, Cout, kh, kw, act, pool, resid, splitk, tile_n, out, iters, avg_ms, s};
+    OpBuffers t(device, s);
+    if (int rc = op_conv_run(&t, a)) return fail(nullptr, rc, "%s", t.err.c_str());
     return EAMM_OK;
 }
 
 int eamm_op_one_euro(int device, const float* x, int T, int E, float mincutoff, float beta, float dcutoff, float freq, float scale,
                      float* out, float* state, int resume, void* stream_) {
-    if (!x || !out || T < 0 || E < 1 || (resume && !state)) return fail(nullptr, EAMM_ERR_ARG, "eamm_op_one_euro: bad argument");
-    DeviceGuard guard(device);
-    if (guard.status != hipSuccess) return fail(nullptr, EAMM_ERR_HIP, "hipSetDevice failed");
-    const hipError_t e = one_euro_launch(x, T, E, mincutoff, beta, dcutoff, freq, scale, out, reinterpret_cast<hipStream_t>(stream_), state, resume);
+    OP_ENTRY(!x || !out || T < 0 || E < 1 || (resume && !state), "eamm_op_one_euro: bad argument");
+    const hipError_t e = one_euro_launch(x, T, E, mincutoff, beta, dcutoff, freq, scale, out, s, state, resume);
     return e == hipSuccess ? EAMM_OK : fail(nullptr, EAMM_ERR_HIP, "one_euro_kernel: %s", hipGetErrorString(e));
 }
 
 int eamm_op_warp(int device, const float* feat, const float* deformation, const float* occlusion, int n, int ns, int hf,
                  int wf, int C, int h, int w, float* out, int iters, float* avg_ms, void* stream_) {
-    if (!feat || !deformation || !out || n < 1 || (ns != 1 && ns != n) || hf < 1 || wf < 1 || h < 1 || w < 1 || C < 8 || (C & 7))
-        return fail(nullptr, EAMM_ERR_ARG, "eamm_op_warp: bad argument");
-    DeviceGuard guard(device);
-    if (guard.status != hipSuccess) return fail(nullptr, EAMM_ERR_HIP, "hipSetDevice failed");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream_);
+    OP_ENTRY(!feat || !deformation || !out || n < 1 || (ns != 1 && ns != n) || hf < 1 || wf < 1 || h < 1 || w < 1 || C < 8 || (C & 7),
+             "eamm_op_warp: bad argument");
     auto run = [&]() { return warp_features_launch(feat, deformation, occlusion, n, ns, hf, wf, C, h, w, out, nullptr, nullptr, nullptr, s); };
     hipError_t e = run();
-    if (e == hipSuccess && iters > 0 && avg_ms) {
-        hipEvent_t e0, e1;
-        (void)hipEventCreate(&e0);
-        (void)hipEventCreate(&e1);
-        (void)hipEventRecord(e0, s);
-        for (int i = 0; i < iters && e == hipSuccess; ++i) e = run();
-        (void)hipEventRecord(e1, s);
-        (void)hipEventSynchronize(e1);
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        *avg_ms = ms / iters;
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-    }
+    if (e == hipSuccess) e = time_launches(s, iters, avg_ms, run);
     // (no stream synchronisation outside the timing branch: like every other operator entry the work is only ENQUEUED on
     // `stream` -- the differentiable forward calls this three times per pass and must stay capturable)
     if (e == hipSuccess) e = hipGetLastError();
-    if (e != hipSuccess) return fail(nullptr, EAMM_ERR_HIP, "eamm_op_warp failed: %s", hipGetErrorString(e));
-    return EAMM_OK;
+    OP_DONE(e, "eamm_op_warp");
 }
 
 int eamm_op_warp_backward(int device, const float* feat, const float* deformation, const float* occlusion, const float* grad_out,
                           int n, int ns, int hf, int wf, int C, float* grad_feat, float* grad_deformation, float* grad_occlusion,
                           void* stream_) {
-    if (!feat || !deformation || !grad_out || n < 1 || (ns != 1 && ns != n) || hf < 1 || wf < 1 || C < 4 || (C & 3) ||
-        (!grad_feat && !grad_deformation && !grad_occlusion) || (grad_occlusion && !occlusion))
-        return fail(nullptr, EAMM_ERR_ARG, "eamm_op_warp_backward: bad argument");
-    DeviceGuard guard(device);
-    if (guard.status != hipSuccess) return fail(nullptr, EAMM_ERR_HIP, "hipSetDevice failed");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream_);
+    OP_ENTRY(!feat || !deformation || !grad_out || n < 1 || (ns != 1 && ns != n) || hf < 1 || wf < 1 || C < 4 || (C & 3) ||
+                 (!grad_feat && !grad_deformation && !grad_occlusion) || (grad_occlusion && !occlusion),
+             "eamm_op_warp_backward: bad argument");
     // the kernel accumulates: the gradients start from zero here, on the caller's stream
     hipError_t e = hipSuccess;
     if (grad_feat) e = hipMemsetAsync(grad_feat, 0, (size_t)ns * hf * wf * C * sizeof(float), s);
@@ -1888,8 +1780,7 @@ int eamm_op_warp_backward(int device, const float* feat, const float* deformatio
     if (e == hipSuccess)
         e = warp_features_backward_launch(feat, deformation, occlusion, grad_out, n, ns, hf, wf, C, grad_feat, grad_deformation,
                                           grad_occlusion, s);
-    if (e != hipSuccess) return fail(nullptr, EAMM_ERR_HIP, "eamm_op_warp_backward failed: %s", hipGetErrorString(e));
-    return EAMM_OK;
+    OP_DONE(e, "eamm_op_warp_backward");
 }
 
 // ---- convolution with DEVICE weights (training path): pack on the device into the caller's workspace, then the forward kernels
@@ -2047,40 +1938,30 @@ size_t eamm_op_conv7_thin_workspace_floats(int B, int H, int W, int N) {
 
 int eamm_op_conv7_thin(int device, const float* thin, const float* weight, const float* bias, int B, int H, int W, int N, int transposed,
                        float* out, float* workspace, size_t workspace_floats, void* stream_) {
-    if (!thin || !weight || !out || !workspace || B < 1 || H < 1 || W < 1 || (N != 32 && N != 64) ||
-        workspace_floats < conv7_thin_workspace_floats(B, H, W, N) || (long long)B * H * W * 64 >= (1ll << 31))
-        return fail(nullptr, EAMM_ERR_ARG, "eamm_op_conv7_thin: bad argument (N = 32 | 64, workspace of eamm_op_conv7_thin_workspace_floats)");
-    DeviceGuard guard(device);
-    if (guard.status != hipSuccess) return fail(nullptr, EAMM_ERR_HIP, "hipSetDevice failed");
-    hipError_t e = conv7_thin_in_launch(thin, weight, bias, B, H, W, N, transposed, out, workspace, reinterpret_cast<hipStream_t>(stream_));
-    if (e != hipSuccess) return fail(nullptr, EAMM_ERR_HIP, "eamm_op_conv7_thin failed: %s", hipGetErrorString(e));
-    return EAMM_OK;
+    OP_ENTRY(!thin || !weight || !out || !workspace || B < 1 || H < 1 || W < 1 || (N != 32 && N != 64) ||
+                 workspace_floats < conv7_thin_workspace_floats(B, H, W, N) || (long long)B * H * W * 64 >= (1ll << 31),
+             "eamm_op_conv7_thin: bad argument (N = 32 | 64, workspace of eamm_op_conv7_thin_workspace_floats)");
+    hipError_t e = conv7_thin_in_launch(thin, weight, bias, B, H, W, N, transposed, out, workspace, s);
+    OP_DONE(e, "eamm_op_conv7_thin");
 }
 
 int eamm_op_conv7_thin_wgrad(int device, const float* thin, const float* wide, int B, int H, int W, int N, int thin_is_input,
                              float* grad_weight, float* workspace, size_t workspace_floats, void* stream_) {
-    if (!thin || !wide || !grad_weight || !workspace || B < 1 || H < 1 || W < 1 || (N != 32 && N != 64) ||
-        workspace_floats < conv7_thin_workspace_floats(B, H, W, N) || (long long)B * H * W * 64 >= (1ll << 31))
-        return fail(nullptr, EAMM_ERR_ARG, "eamm_op_conv7_thin_wgrad: bad argument");
-    DeviceGuard guard(device);
-    if (guard.status != hipSuccess) return fail(nullptr, EAMM_ERR_HIP, "hipSetDevice failed");
-    hipError_t e = conv7_thin_wgrad_launch(thin, wide, B, H, W, N, thin_is_input, grad_weight, workspace, reinterpret_cast<hipStream_t>(stream_));
-    if (e != hipSuccess) return fail(nullptr, EAMM_ERR_HIP, "eamm_op_conv7_thin_wgrad failed: %s", hipGetErrorString(e));
-    return EAMM_OK;
+    OP_ENTRY(!thin || !wide || !grad_weight || !workspace || B < 1 || H < 1 || W < 1 || (N != 32 && N != 64) ||
+                 workspace_floats < conv7_thin_workspace_floats(B, H, W, N) || (long long)B * H * W * 64 >= (1ll << 31),
+             "eamm_op_conv7_thin_wgrad: bad argument");
+    hipError_t e = conv7_thin_wgrad_launch(thin, wide, B, H, W, N, thin_is_input, grad_weight, workspace, s);
+    OP_DONE(e, "eamm_op_conv7_thin_wgrad");
 }
 
 int eamm_op_final_conv_sigmoid(int device, const float* x, const float* weight, const float* bias, int B, int H, int W, int C,
                                float* out_nchw, float* workspace, size_t workspace_floats, void* stream_) {
-    if (!x || !weight || !bias || !out_nchw || !workspace || B < 1 || H < 1 || W < 1 || (C != 32 && C != 64) ||
-        workspace_floats < (size_t)7 * C * 32 || (reinterpret_cast<uintptr_t>(workspace) & 15))
-        return fail(nullptr, EAMM_ERR_ARG, "eamm_op_final_conv_sigmoid: bad argument (C = 32 | 64, workspace of 7 * C * 32 floats)");
-    DeviceGuard guard(device);
-    if (guard.status != hipSuccess) return fail(nullptr, EAMM_ERR_HIP, "hipSetDevice failed");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream_);
+    OP_ENTRY(!x || !weight || !bias || !out_nchw || !workspace || B < 1 || H < 1 || W < 1 || (C != 32 && C != 64) ||
+                 workspace_floats < (size_t)7 * C * 32 || (reinterpret_cast<uintptr_t>(workspace) & 15),
+             "eamm_op_final_conv_sigmoid: bad argument (C = 32 | 64, workspace of 7 * C * 32 floats)");
     hipError_t e = col7_pack_dev_launch(weight, C, workspace, s);
     if (e == hipSuccess) e = conv_col7_fused_launch(x, C, B, H, W, workspace, bias, out_nchw, s);
-    if (e != hipSuccess) return fail(nullptr, EAMM_ERR_HIP, "eamm_op_final_conv_sigmoid failed: %s", hipGetErrorString(e));
-    return EAMM_OK;
+    OP_DONE(e, "eamm_op_final_conv_sigmoid");
 }
 
 size_t eamm_op_conv_wgrad_workspace_floats(int B, int H, int W, int Cin, int Cout, int kh, int kw) {
@@ -2090,15 +1971,11 @@ size_t eamm_op_conv_wgrad_workspace_floats(int B, int H, int W, int Cin, int Cou
 
 int eamm_op_conv_wgrad(int device, const float* x, const float* grad_out, int B, int H, int W, int Cin, int Cout, int kh, int kw,
                        float* grad_weight, float* grad_bias, float* workspace, size_t workspace_floats, void* stream_) {
-    if (!x || !grad_out || !grad_weight || !workspace || B < 1 || H < 1 || W < 1 || Cin < 4 || Cout < 4 || (Cin & 3) || (Cout & 3) ||
-        Cout > 1024 || kh < 1 || kw < 1 || !(kh & 1) || !(kw & 1) || kh > 7 || kw > 7)
-        return fail(nullptr, EAMM_ERR_ARG, "eamm_op_conv_wgrad: bad argument (channels multiples of 4, Cout <= 1024, odd filter up to 7x7)");
-    DeviceGuard guard(device);
-    if (guard.status != hipSuccess) return fail(nullptr, EAMM_ERR_HIP, "hipSetDevice failed");
-    hipError_t e = conv_wgrad_launch(x, grad_out, B, H, W, Cin, Cout, kh, kw, grad_weight, grad_bias, workspace, workspace_floats,
-                                     reinterpret_cast<hipStream_t>(stream_));
-    if (e != hipSuccess) return fail(nullptr, EAMM_ERR_HIP, "eamm_op_conv_wgrad failed: %s", hipGetErrorString(e));
-    return EAMM_OK;
+    OP_ENTRY(!x || !grad_out || !grad_weight || !workspace || B < 1 || H < 1 || W < 1 || Cin < 4 || Cout < 4 || (Cin & 3) || (Cout & 3) ||
+                 Cout > 1024 || kh < 1 || kw < 1 || !(kh & 1) || !(kw & 1) || kh > 7 || kw > 7,
+             "eamm_op_conv_wgrad: bad argument (channels multiples of 4, Cout <= 1024, odd filter up to 7x7)");
+    hipError_t e = conv_wgrad_launch(x, grad_out, B, H, W, Cin, Cout, kh, kw, grad_weight, grad_bias, workspace, workspace_floats, s);
+    OP_DONE(e, "eamm_op_conv_wgrad");
 }
 
 size_t eamm_op_conv_saved_transform_offset(int B, int H, int W, int Cin, int Cout, int kh, int kw) {
@@ -2110,59 +1987,48 @@ size_t eamm_op_conv_saved_transform_offset(int B, int H, int W, int Cin, int Cou
 
 int eamm_op_conv_wgrad_saved(int device, const float* x_transformed, const float* grad_out, int B, int H, int W, int Cin, int Cout,
                              float* grad_weight, float* grad_bias, float* workspace, size_t workspace_floats, void* stream_) {
-    if (!x_transformed || !grad_out || !grad_weight || !workspace || eamm_op_conv_saved_transform_offset(B, H, W, Cin, Cout, 3, 3) == (size_t)-1 ||
-        Cout > 1024)
-        return fail(nullptr, EAMM_ERR_ARG, "eamm_op_conv_wgrad_saved: only where eamm_op_conv_saved_transform_offset names a saved transform");
-    DeviceGuard guard(device);
-    if (guard.status != hipSuccess) return fail(nullptr, EAMM_ERR_HIP, "hipSetDevice failed");
+    OP_ENTRY(!x_transformed || !grad_out || !grad_weight || !workspace || eamm_op_conv_saved_transform_offset(B, H, W, Cin, Cout, 3, 3) == (size_t)-1 ||
+                 Cout > 1024,
+             "eamm_op_conv_wgrad_saved: only where eamm_op_conv_saved_transform_offset names a saved transform");
     hipError_t e = conv_wgrad_launch(nullptr, grad_out, B, H, W, Cin, Cout, 3, 3, grad_weight, grad_bias, workspace, workspace_floats,
-                                     reinterpret_cast<hipStream_t>(stream_), x_transformed);
-    if (e != hipSuccess) return fail(nullptr, EAMM_ERR_HIP, "eamm_op_conv_wgrad_saved failed: %s", hipGetErrorString(e));
-    return EAMM_OK;
+                                     s, x_transformed);
+    OP_DONE(e, "eamm_op_conv_wgrad_saved");
 }
 
 // ---- differentiable dense-motion front end and flow head (motion.hip forward kernels, motion_backward.hip) -----------------------
-#define MOTION_ENTRY(cond, msg)                                                                  \
-    if (cond) return fail(nullptr, EAMM_ERR_ARG, msg);                                           \
-    DeviceGuard guard(device);                                                                   \
-    if (guard.status != hipSuccess) return fail(nullptr, EAMM_ERR_HIP, "hipSetDevice failed");   \
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream_)
-#define MOTION_DONE(e, name) \
-    return (e) == hipSuccess ? EAMM_OK : fail(nullptr, EAMM_ERR_HIP, name " failed: %s", hipGetErrorString(e))
-
 int eamm_op_antialias_down(int device, const float* source, const float* aa_weight, int B, int H, int W, int inv_scale, float* small,
                            void* stream_) {
-    MOTION_ENTRY(!source || !small || B < 1 || H < 1 || W < 1 || (inv_scale != 1 && inv_scale != 4) || (inv_scale == 4 && !aa_weight) ||
+    OP_ENTRY(!source || !small || B < 1 || H < 1 || W < 1 || (inv_scale != 1 && inv_scale != 4) || (inv_scale == 4 && !aa_weight) ||
                      H % inv_scale || W % inv_scale,
                  "eamm_op_antialias_down: bad argument (inv_scale 1 | 4: the 13x13 kernel of scale_factor 0.25)");
     hipError_t e = antialias_down_launch(source, aa_weight, B, H, W, inv_scale, 4, small, s);
-    MOTION_DONE(e, "eamm_op_antialias_down");
+    OP_DONE(e, "eamm_op_antialias_down");
 }
 
 int eamm_op_antialias_down_backward(int device, const float* grad_small, const float* aa_weight, int B, int H, int W, int inv_scale,
                                     float* grad_source, void* stream_) {
-    MOTION_ENTRY(!grad_small || !grad_source || B < 1 || H < 1 || W < 1 || (inv_scale != 1 && inv_scale != 4) ||
+    OP_ENTRY(!grad_small || !grad_source || B < 1 || H < 1 || W < 1 || (inv_scale != 1 && inv_scale != 4) ||
                      (inv_scale == 4 && !aa_weight) || H % inv_scale || W % inv_scale,
                  "eamm_op_antialias_down_backward: bad argument");
     hipError_t e = antialias_down_backward_launch(grad_small, aa_weight, B, H, W, inv_scale, grad_source, s);
-    MOTION_DONE(e, "eamm_op_antialias_down_backward");
+    OP_DONE(e, "eamm_op_antialias_down_backward");
 }
 
 int eamm_op_kp_records(int device, const float* kd_val, const float* kd_jac, const float* ks_val, const float* ks_jac, int n, int K,
                        float* records, int* singular_flag, void* stream_) {
-    MOTION_ENTRY(!kd_val || !ks_val || !records || !singular_flag || n < 1 || K < 1 || K > 31 || ((kd_jac == nullptr) != (ks_jac == nullptr)),
+    OP_ENTRY(!kd_val || !ks_val || !records || !singular_flag || n < 1 || K < 1 || K > 31 || ((kd_jac == nullptr) != (ks_jac == nullptr)),
                  "eamm_op_kp_records: bad argument");
     hipError_t e = kp_prepare_launch(kd_val, kd_jac, ks_val, ks_jac, n, n, K, records, singular_flag, s);
-    MOTION_DONE(e, "eamm_op_kp_records");
+    OP_DONE(e, "eamm_op_kp_records");
 }
 
 int eamm_op_kp_records_backward(int device, const float* kd_jac, const float* ks_jac, const float* grad_records, int n, int K,
                                 float* grad_kd_val, float* grad_ks_val, float* grad_kd_jac, float* grad_ks_jac, void* stream_) {
-    MOTION_ENTRY(!grad_records || n < 1 || K < 1 || ((kd_jac == nullptr) != (ks_jac == nullptr)) ||
+    OP_ENTRY(!grad_records || n < 1 || K < 1 || ((kd_jac == nullptr) != (ks_jac == nullptr)) ||
                      ((grad_kd_jac || grad_ks_jac) && !kd_jac),
                  "eamm_op_kp_records_backward: bad argument");
     hipError_t e = kp_records_backward_launch(kd_jac, ks_jac, grad_records, n, K, grad_kd_val, grad_ks_val, grad_kd_jac, grad_ks_jac, s);
-    MOTION_DONE(e, "eamm_op_kp_records_backward");
+    OP_DONE(e, "eamm_op_kp_records_backward");
 }
 
 size_t eamm_op_motion_workspace_floats(int n, int K, int h, int w) {
@@ -2172,47 +2038,48 @@ size_t eamm_op_motion_workspace_floats(int n, int K, int h, int w) {
 
 int eamm_op_motion_front(int device, const float* records, const float* small, int n, int K, int h, int w, float kp_variance, int Cpad,
                          float* hourglass_in, float* sparse_deformed, void* stream_) {
-    MOTION_ENTRY(!records || !small || !hourglass_in || n < 1 || K < 1 || K > 31 || h < 2 || w < 2 || Cpad < 4 * (K + 1) || (Cpad & 3) ||
+    OP_ENTRY(!records || !small || !hourglass_in || n < 1 || K < 1 || K > 31 || h < 2 || w < 2 || Cpad < 4 * (K + 1) || (Cpad & 3) ||
                      !(kp_variance > 0.f),
                  "eamm_op_motion_front: bad argument");
     hipError_t e = motion_front_launch(records, small, n, n, K, h, w, kp_variance, Cpad, hourglass_in, sparse_deformed, s);
-    MOTION_DONE(e, "eamm_op_motion_front");
+    OP_DONE(e, "eamm_op_motion_front");
 }
 
 int eamm_op_motion_front_backward(int device, const float* records, const float* small, int n, int K, int h, int w, float kp_variance,
                                   int Cpad, const float* grad_hourglass_in, const float* grad_sparse_deformed, float* grad_small,
                                   float* grad_records, float* workspace, size_t workspace_floats, void* stream_) {
-    MOTION_ENTRY(!records || !small || !grad_records || !workspace || (!grad_hourglass_in && !grad_sparse_deformed) || n < 1 || K < 1 ||
+    OP_ENTRY(!records || !small || !grad_records || !workspace || (!grad_hourglass_in && !grad_sparse_deformed) || n < 1 || K < 1 ||
                      K > 31 || h < 2 || w < 2 || Cpad < 4 * (K + 1) || (Cpad & 3) || !(kp_variance > 0.f) ||
                      workspace_floats < motion_backward_workspace_floats(n, K, h, w),
                  "eamm_op_motion_front_backward: bad argument");
     hipError_t e = motion_front_backward_launch(records, small, n, K, h, w, kp_variance, Cpad, grad_hourglass_in, grad_sparse_deformed,
                                                 grad_small, grad_records, workspace, s);
-    MOTION_DONE(e, "eamm_op_motion_front_backward");
+    OP_DONE(e, "eamm_op_motion_front_backward");
 }
 
 int eamm_op_motion_head(int device, const float* mask_logits, int ld, const float* occlusion_logits, int ldo, const float* records, int n,
                         int K, int h, int w, float* mask, float* deformation, float* occlusion, void* stream_) {
-    MOTION_ENTRY(!mask_logits || !records || !mask || !deformation || n < 1 || K < 1 || K > 31 || h < 2 || w < 2 || ld < K + 1 ||
+    OP_ENTRY(!mask_logits || !records || !mask || !deformation || n < 1 || K < 1 || K > 31 || h < 2 || w < 2 || ld < K + 1 ||
                      (occlusion_logits && (ldo < 1 || !occlusion)),
                  "eamm_op_motion_head: bad argument");
     hipError_t e = motion_head_forward_launch(mask_logits, ld, occlusion_logits, ldo, records, n, K, h, w, mask, deformation, occlusion, s);
-    MOTION_DONE(e, "eamm_op_motion_head");
+    OP_DONE(e, "eamm_op_motion_head");
 }
 
 int eamm_op_motion_head_backward(int device, const float* mask, const float* occlusion, const float* records, int n, int K, int h, int w,
                                  const float* grad_mask, const float* grad_deformation, const float* grad_occlusion,
                                  float* grad_mask_logits, int ld, float* grad_occlusion_logits, int ldo, float* grad_records,
                                  float* workspace, size_t workspace_floats, void* stream_) {
-    MOTION_ENTRY(!mask || !records || !grad_mask_logits || !grad_records || !workspace || n < 1 || K < 1 || K > 31 || h < 2 || w < 2 ||
+    OP_ENTRY(!mask || !records || !grad_mask_logits || !grad_records || !workspace || n < 1 || K < 1 || K > 31 || h < 2 || w < 2 ||
                      ld < K + 1 || (grad_occlusion_logits && (ldo < 1 || !occlusion)) ||
                      workspace_floats < motion_backward_workspace_floats(n, K, h, w),
                  "eamm_op_motion_head_backward: bad argument");
     hipError_t e = motion_head_backward_launch(mask, occlusion, records, n, K, h, w, grad_mask, grad_deformation, grad_occlusion,
                                                grad_mask_logits, ld, grad_occlusion_logits, ldo, grad_records, workspace, s);
-    MOTION_DONE(e, "eamm_op_motion_head_backward");
+    OP_DONE(e, "eamm_op_motion_head_backward");
 }
-#undef MOTION_ENTRY
-#undef MOTION_DONE
 
 }  // extern "C"
+
+#undef OP_ENTRY
+#undef OP_DONE

@@ -31,54 +31,6 @@ namespace {
 
 int side_of(int layer) { return 4 << layer; }   // output side of layer i: 4, 8, 16, ...
 
-// fold eval-mode BatchNorm (key prefix `norm`, may be empty) into per-channel scale / bias
-int fold_norm(eamm_deconv_ctx* c, const std::string& conv, const std::string& norm, int Cout, std::vector<double>* scale,
-              std::vector<double>* bias) {
-    const HostTensor* bt = find(c, conv + ".bias");
-    if (!bt || (int)bt->numel() != Cout) return fail(c, EAMM_ERR_KEY, "%s.bias missing or mis-shaped", conv.c_str());
-    scale->assign(Cout, 1.0);
-    bias->resize(Cout);
-    for (int o = 0; o < Cout; ++o) (*bias)[o] = bt->data[o];
-    if (norm.empty()) return EAMM_OK;
-    const HostTensor *g = find(c, norm + ".weight"), *be = find(c, norm + ".bias"), *mu = find(c, norm + ".running_mean"),
-                     *var = find(c, norm + ".running_var");
-    if (!g || !be || !mu || !var || (int)g->numel() != Cout || (int)be->numel() != Cout || (int)mu->numel() != Cout ||
-        (int)var->numel() != Cout)
-        return fail(c, EAMM_ERR_KEY, "BatchNorm entries of %s missing or mis-shaped", norm.c_str());
-    for (int o = 0; o < Cout; ++o) {
-        const double s = (double)g->data[o] / std::sqrt((double)var->data[o] + 1e-5);
-        (*scale)[o] = s;
-        (*bias)[o] = ((*bias)[o] - (double)mu->data[o]) * s + (double)be->data[o];
-    }
-    return EAMM_OK;
-}
-
-int finish_layer(eamm_deconv_ctx* c, ConvLayer* L, int kh, int kw, bool phase, int Cin, int Cout,
-                 const std::vector<float>& wf, const std::vector<float>& bf, int dma_cfg = 0) {
-    L->kh = kh;
-    L->kw = kw;
-    L->phase = phase;
-    L->C0 = Cin;
-    L->C1 = 0;
-    L->Cout = Cout;
-    L->BM = 128;
-    L->BN = conv_tile_n(Cout);
-    L->dma_cfg = dma_cfg;
-    if (dma_cfg > 0 && !conv_dma_tile(dma_cfg, &L->BM, &L->BN)) return fail(c, EAMM_ERR_ARG, "unknown dma tile %d", dma_cfg);
-    L->ntiles = (Cout + L->BN - 1) / L->BN;
-    const int taps = phase ? 4 : kh * kw;
-    L->nchunks = taps * (Cin / CONV_BK);
-    std::vector<float> packed(conv_packed_elems(taps, Cin, Cout, L->BN, phase ? 4 : 1));
-    if (phase)
-        conv_pack_phases_host(wf.data(), Cout, Cin, nullptr, Cin, L->BN, dma_cfg > 0, packed.data());
-    else
-        conv_pack_host(wf.data(), Cout, Cin, kh, kw, nullptr, Cin, L->BN, false, dma_cfg > 0, packed.data());
-    std::vector<float> bias_pad((size_t)L->ntiles * L->BN, 0.f);
-    std::copy(bf.begin(), bf.end(), bias_pad.begin());
-    if (int rc = upload(c, &L->w, packed)) return rc;
-    return upload(c, &L->bias, bias_pad);
-}
-
 }  // namespace
 
 extern "C" {
@@ -149,31 +101,34 @@ int eamm_deconv_finalize_weights(eamm_deconv_ctx* c) {
         auto W = [&](int ci, int o, int ky, int kx) { return (double)wt->data[(((size_t)ci * Cout + o) * k + ky) * k + kx]; };
         if (i == 0) {
             // 1x1 input, stride 2, padding 1: out[Y][X] = in * w[Y+1][X+1] for Y, X in 0..3 -> N = (Y*4 + X)*Cout + o
-            const int N = 16 * Cout;
-            std::vector<float> wf((size_t)N * Cin), bf(N);
+            HostConv f{16 * Cout, Cin, 1, 1};
+            f.w.resize((size_t)f.Cout * Cin);
+            f.b.resize(f.Cout);
             for (int Y = 0; Y < 4; ++Y)
                 for (int X = 0; X < 4; ++X)
                     for (int o = 0; o < Cout; ++o) {
                         const int n = (Y * 4 + X) * Cout + o;
-                        bf[n] = (float)bs[o];
-                        for (int ci = 0; ci < Cin; ++ci) wf[(size_t)n * Cin + ci] = (float)(W(ci, o, Y + 1, X + 1) * sc[o]);
+                        f.b[n] = (float)bs[o];
+                        for (int ci = 0; ci < Cin; ++ci) f.w[(size_t)n * Cin + ci] = (float)(W(ci, o, Y + 1, X + 1) * sc[o]);
                     }
-            if ((rc = finish_layer(c, &c->layers[i], 1, 1, false, Cin, N, wf, bf))) return rc;
+            if ((rc = pack_conv(c, f, nullptr, Cin, 0, MODE_PLAIN, 0, &c->layers[i]))) return rc;
         } else {
-            std::vector<float> wf((size_t)4 * Cout * Cin * 4), bf(Cout);
-            for (int o = 0; o < Cout; ++o) bf[o] = (float)bs[o];
+            HostConv f{Cout, Cin, 2, 2};   // MODE_PHASES: the four 2x2 phase filters [4][Cout][Cin][4]
+            f.w.resize((size_t)4 * Cout * Cin * 4);
+            f.b.resize(Cout);
+            for (int o = 0; o < Cout; ++o) f.b[o] = (float)bs[o];
             for (int ph = 0; ph < 4; ++ph) {
                 const int py = ph >> 1, px = ph & 1;
                 for (int o = 0; o < Cout; ++o)
                     for (int ci = 0; ci < Cin; ++ci)
                         for (int ty = 0; ty < 2; ++ty)
                             for (int tx = 0; tx < 2; ++tx)
-                                wf[(((size_t)ph * Cout + o) * Cin + ci) * 4 + ty * 2 + tx] =
+                                f.w[(((size_t)ph * Cout + o) * Cin + ci) * 4 + ty * 2 + tx] =
                                     (float)(W(ci, o, 3 - py - 2 * ty, 3 - px - 2 * tx) * sc[o]);
             }
-            if ((rc = finish_layer(c, &c->layers[i], 2, 2, true, Cin, Cout, wf, bf))) return rc;
+            if ((rc = pack_conv(c, f, nullptr, Cin, 0, MODE_PHASES, 0, &c->layers[i]))) return rc;
             if (i + 1 == c->nl && Cout + 1 <= 64 && c->dma_min_m >= 0) {   // (+ 1: the split hand-over's zero column)
-                if ((rc = finish_layer(c, &c->last_dma, 2, 2, true, Cin, Cout, wf, bf, 3))) return rc;
+                if ((rc = pack_conv(c, f, nullptr, Cin, 0, MODE_PHASES, 3, &c->last_dma))) return rc;
                 c->has_last_dma = true;
             }
         }

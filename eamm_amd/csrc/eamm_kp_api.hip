@@ -232,7 +232,6 @@ int eamm_kp_finalize_weights(eamm_kp_ctx* c) {
     if ((rc = dev_alloc(c, &c->logits, F * hw * c->head_cs))) return rc;
     if ((rc = dev_alloc(c, &c->head_ws, kp_head_workspace_floats((int)F, c->K)))) return rc;
     size_t need = 0;
-    auto upd1 = [&](const ConvLayer& L, size_t M) { need = std::max(need, conv_plan(L, (int)M).partial_elems); };
     if (g.with_predictor) {
         c->e_buf.resize(c->nb);
         c->u_buf.resize(c->nb);
@@ -242,20 +241,12 @@ int eamm_kp_finalize_weights(eamm_kp_ctx* c) {
         }
         for (size_t f = 1; f <= F; ++f)
             for (int i = 0; i < c->nb; ++i)
-                for (const LayerSet* S : {&c->hg_enc[i], &c->hg_dec[i]}) {
-                    const size_t M = S == &c->hg_enc[i] ? f * (hw >> (2 * i)) : f * (hw >> (2 * (c->nb - i)));
-                    upd1(S->base, M);
-                    if (S->has_dma) upd1(S->dma, M);
-                    if (S->has_big) upd1(S->big, M);
-                    if (S->has_skinny) {
-                        upd1(S->skinny32, M);
-                        upd1(S->skinny64, M);
-                    }
-                }
+                need = std::max({need, set_partial_elems(c->hg_enc[i], f * (hw >> (2 * i))),
+                                 set_partial_elems(c->hg_dec[i], f * (hw >> (2 * (c->nb - i))))});
     }
     for (size_t f = 1; f <= F; ++f) {
-        upd1(c->head, f * hw);
-        if (c->has_head_dma) upd1(c->head_dma, f * hw);
+        need = std::max(need, conv_plan(c->head, (int)(f * hw)).partial_elems);
+        if (c->has_head_dma) need = std::max(need, conv_plan(c->head_dma, (int)(f * hw)).partial_elems);
     }
     c->partial_elems = need;
     if ((rc = dev_alloc(c, &c->partial, need))) return rc;

@@ -404,10 +404,22 @@ int eamm_profile_read(eamm_ctx* ctx, double* stage_ms, int nstage, int64_t* call
  * in0/in1: [B,Hin,Win,C0|C1] (in1 optional: channel concatenation), weight: OIHW host pointer
  * [Cout,C0+C1,kh,kw], bias host [Cout]; up = 1 (3x3 only) computes conv3x3(nearest_x2(input)) in its
  * collapsed four-phase 2x2 form; act: 0 none, 1 relu, 2 sigmoid; pool = 1 applies avgpool2x2 after the
- * activation; resid: NHWC tensor added before the activation; splitk 0 = automatic; tile_n 0 =
- * automatic, 32/64/128 = register-staged 128 x tile_n kernel, 1000+id = LDS-DMA big-tile kernel (1: 256x256,
- * 2: 256x128, 3: 512x64), 4002 = the generator's final layer whole (7x7, Cout 3, act 2: out is NCHW [B,3,H,W]), 2000 = Winograd F(2x2,3x3) (input transform + GEMM; 3x3, single input, no pool); out NHWC [B,H(/2),W(/2),Cout] with H = Hin << up.  iters > 0 additionally times `iters`
- * back-to-back launches with HIP events on `stream` and stores the average milliseconds in *avg_ms. */
+ * activation; resid: NHWC tensor added before the activation; splitk 0 = automatic.  tile_n picks the kernel, with the
+ * weights packed as the engine packs them for it:
+ *   0                automatic register-staged tile; 32 / 64 / 128: the register-staged 128 x tile_n kernel
+ *   1000 + id        LDS-DMA tile (1: 256x256, 2: 256x128, 3: 512x64, 4: 32x128, 5: 64x128); not 7x7 / 7x1
+ *   2000 + variant   Winograd F(2x2,3x3): input transform + GEMM (3x3, single input, Cin % 64 == 0, no pool)
+ *   2100 + variant   Winograd F(4x4,3x3) (as 2000, Hin and Win multiples of 4)
+ *   2150 + groups    F(4x4,3x3) with the transform-point rows split over 2, 3, 6 or 12 workgroups + output-transform
+ *                    kernel (pool allowed without resid)
+ *   3000 / 3003      spatial-patch kernel of the up-convolution (up = 1): collapsed-phase / polyphase form (3003 only:
+ *                    splitk > 1 splits the channel reduction)
+ *   4000 / 4001      column-patch kernel of a row-split 7x1 convolution (weights [Cout][C][7][1], no bias applied, act 0):
+ *                    4000 the final layer (Cout 32, C0 32 or 64, no in1), 4001 the flow head (Cout 96, two inputs)
+ *   4002             the generator's final layer whole (7x7, Cout 3, act 2: out is NCHW [B,3,H,W])
+ * out NHWC [B,H(/2),W(/2),Cout] with H = Hin << up.  iters > 0 additionally times `iters` back-to-back launches with HIP
+ * events on `stream` and stores the average milliseconds in *avg_ms; a failed launch returns EAMM_ERR_HIP and stores
+ * no time. */
 int eamm_op_conv(int device, const float* in0, int C0, const float* in1, int C1, int B, int Hin, int Win, int up,
                  const float* weight_host, const float* bias_host, int Cout, int kh, int kw,
                  int act, int pool, const float* resid, int splitk, int tile_n, float* out, int iters,
