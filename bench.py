@@ -1,13 +1,19 @@
 #!/usr/bin/env python
 """bench.py -- 256x256 frames/sec of the dense-motion + generator forward path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
     `--dump-outputs DIR` also writes what the last timed step returned as DIR/<name>.npy (seeded inputs: runs compare)
 
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the contract line (the headline, the
+configuration it was measured under, the knobs and the launch plan) -- nothing else.  `--full` adds every other leg listed below:
+the roofline / stage keys, the in-run parity checks against the committed reference fixture, the five-key forward, one frame per
+call, the clip and end-to-end legs, the isolated warp kernel, the CPU baseline, the training step and `--graph`.
+
 Timing: W warm-up steps, then EXACTLY K steps between barrier + synchronize (the contract's region; nothing but the steps is
-enqueued, the library's stage events are off), then the same K steps once more with the events on for the roofline / stage keys.
+enqueued, the library's stage events are off); with --full, then the same K steps once more with the events on for the roofline /
+stage keys.
 
 A "step" is one pass of the hot path (eamm_forward_frames: key points -> dense motion -> warp ->
 decoder) over one batch of 16 synthetic driving frames of a 256x256 clip on each GPU, with the source
@@ -17,7 +23,7 @@ points) are resident in HBM before the timed region; outputs stay on the device.
 are independent, so the path shards by frames with no data-path collective: weak scaling, value =
 all ranks' frames / max-over-ranks time.   `--size 512 --batch 8` is BASELINE.json configs[4].
 
-Prints ONE JSON line with the contract keys plus
+Prints ONE JSON line with the contract keys; with --full also
   roofline     -- the dominant kernel (the 3x3 256->256 bottleneck convolution: 12 launches per step, 67 % of
                   the reference FLOPs), FLOPs / its average launch duration measured with HIP events on the
                   launch stream inside the timed steps (executed-MFMA and reference-algorithmic figures);
@@ -147,6 +153,22 @@ def knob_record(eng, frames, extra_plans=None):
     return rec
 
 
+def contract_line(args, size, batch, world, dt, eng):
+    """The line's leading keys, plain run and --full alike: the headline (frames of all ranks / max-over-ranks seconds of the
+    K timed steps) and the workload it was measured on."""
+    which = "configs[2]" if (size, batch) == (256, 16) else ("configs[4]" if (size, batch) == (512, 8) else "a non-BASELINE size")
+    return {
+        "metric": "256x256 frames/sec (dense-motion + generator forward)" if size == 256 else f"{size}x{size} frames/sec",
+        "value": round(args.steps * batch * world / dt, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"{size}x{size}, 10 keypoints, batch={batch} synthetic frames per GPU per step, source "
+                               f"encoded once per clip (BASELINE.json {which})",
+                   "frames_per_step_per_gpu": batch, "parallelism": f"frame-sharded x{world}",
+                   "flops_per_frame": round(eng.flops_per_frame / 1e9, 3)},
+    }
+
+
 def physical_cores():
     """Physical cores of the host (distinct (package, core) pairs of /proc/cpuinfo; psutil as a fallback; None if unknown)."""
     try:
@@ -273,7 +295,7 @@ def train_step_leg(cfg, sd, size, pairs, steps=4):
                     "eamm_amd/train_graph.py; batch-statistics BatchNorm; not part of `value`"}
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -304,11 +326,23 @@ def main():
                          "at most 64 MB in all (a seeded sample of frames beyond that, indices in "
                          "DIR/<name>_frames.npy); with N > 1 every rank writes <name>.rank<r>.npy.  Inputs are seeded: two builds "
                          "run with the same arguments can be compared output for output")
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the contract line's steps, also run every other leg: roofline / stage keys, parity against the "
+                         "reference fixture, five-key forward, one frame per call, clip, end to end, isolated warp, CPU baseline, "
+                         "training step (--cpu-frames .. --graph configure these legs and act only here).  Off: the run only sets up, warms "
+                         "up, times the steps, writes --dump-outputs and prints the contract line")
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.graph and not args.full:
+        ap.error("--graph is a leg of --full")
     if args.batch is None:
         args.batch = 16 if args.size <= 256 else 8
+    return args
+
+
+def main():
+    args = parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # bare `python bench.py --gpus N`: become the launcher -- N ranks of this script under torch.distributed.run, one per
@@ -443,6 +477,24 @@ def main():
     if args.dump_outputs:
         dumped = dump_outputs(args.dump_outputs, last, "" if world == 1 else f".rank{rank}", DUMP_BUDGET // world)
     del last
+    if not args.full:
+        # a plain run ends here: the library's own error check of the timed calls, the headline, nothing else on the GPU
+        eng.check_numeric()
+        dt = max_over_ranks(dt)
+        if rank == 0:
+            line = contract_line(args, S, B, world, dt, eng)
+            line["knobs"] = knob_record(eng, B)
+            if t_bcast_ms is not None:
+                line["source_broadcast_ms"] = round(t_bcast_ms, 3)
+            if rccl_warmup_ms is not None:
+                line["rccl_warmup_ms"] = round(rccl_warmup_ms, 2)
+            if dumped is not None:
+                line["dump_outputs"] = dumped
+            print(json.dumps(line), flush=True)
+        if use_dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     # the same K steps again with the library's HIP events on (stage boundaries, every bottleneck launch, every chain's bottleneck
     # window): the roofline / stage keys come from this second region (the events cost ~0.3 % of a step)
     eng.profile(True)
@@ -785,7 +837,6 @@ def main():
         ms_step = dt / args.steps * 1e3
         ms_step_prof = dt_prof / args.steps * 1e3          # the events' region (stage times, executed-flop rates)
         traffic, traffic_src = measured_traffic(form, S, B, chains)
-        which = "configs[2]" if (S, B) == (256, 16) else ("configs[4]" if (S, B) == (512, 8) else "a non-BASELINE size")
         warp_bytes_frame = (2 * hf * hf * cb + 3 * (S // 4) * (S // 4)) * 4.0    # 8.438 MB at 256^2
         warp_joint = os.environ.get("EAMM_WARP_JOINT") == "1" and pchains > 1      # one launch for all chains' frames (knob, off by default)
         warp_frames = B if warp_joint else B // pchains                         # frames of ONE in-pipeline launch
@@ -811,15 +862,8 @@ def main():
             return {"achieved": round(by / (ms * 1e-3) / 1e9, 1), "frac": round(by / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
                     "algorithmic_bytes_per_launch": int(by), "avg_launch_ms": round(ms, 4)}
 
-        line = {
-            "metric": "256x256 frames/sec (dense-motion + generator forward)" if S == 256 else f"{S}x{S} frames/sec",
-            "value": round(fps, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_step, 4), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"{S}x{S}, 10 keypoints, batch={B} synthetic frames per GPU per step, source "
-                                   f"encoded once per clip (BASELINE.json {which})",
-                       "frames_per_step_per_gpu": B, "parallelism": f"frame-sharded x{world}",
-                       "flops_per_frame": round(eng.flops_per_frame / 1e9, 3)},
+        line = contract_line(args, S, B, world, dt, eng)
+        line.update({
             "roofline": {"bound": "mfma", "flops_basis": "executed (what the kernels' grids issue: Winograd F(4x4) = 1/4 of the reference's "
                                                          "multiplies); `achieved` / `frac` / `per_launch` / `whole_path.executed_*` all use it",
                          "kernel": {4: f"wino4_gemm_kernel (bottleneck 3x3 {cb}->{cb} @{hf}x{hf} in Winograd F(4x4,3x3) form)",
@@ -872,7 +916,7 @@ def main():
             "stage_sum_ms": round(total_ms / calls, 4),
             "stage_region_ms_per_step": round(ms_step_prof, 4),   # wall clock of the second (event-instrumented) K steps
             "stage_roofline": stage_roofline,
-        }
+        })
         line["parity_check"] = parity
         line["knobs"] = knob_record(eng, B)
         if t_bcast_ms is not None:

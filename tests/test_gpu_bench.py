@@ -1,4 +1,4 @@
-"""bench.py contract on the GPU box: the JSON line at N=1, and the N=2 code path (two ranks sharing GPU 0, gloo
+"""bench.py contract on the GPU box: the JSON line at N=1 (plain and --full), and the N=2 code path (two ranks sharing GPU 0, gloo
 collectives staged through the host -- the driver's real N>1 runs use one rank per GPU over RCCL)."""
 import json
 import os
@@ -25,7 +25,7 @@ def run(cmd, env=None):
 
 
 def test_bench_single_gpu_line():
-    d = run([sys.executable, "bench.py", "--steps", "10", "--warmup", "3", "--cpu-frames", "10"])
+    d = run([sys.executable, "bench.py", "--steps", "10", "--warmup", "3", "--cpu-frames", "10", "--full"])
     assert REQUIRED <= set(d)
     assert d["n_gpus"] == 1 and d["steps"] == 10 and d["warmup"] == 3 and d["scaling"] == "weak"
     assert d["unit"] == "frames/s" and d["higher_is_better"] is True and d["vs_baseline"] is None
@@ -154,10 +154,24 @@ def _check_train_step_against_the_oracle(t):
         assert abs(got[k] - want[k]) <= 2e-2 * abs(want[k]), (k, got[k], want[k])
 
 
+def test_bench_plain_run_prints_the_contract_line_only():
+    """Without --full the run sets up, warms up, times the K steps and prints the contract line: the same headline keys as
+    the --full line, the knobs and launch plan they were measured under, and none of the other legs' keys."""
+    d = run([sys.executable, "bench.py", "--steps", "5", "--warmup", "2"])
+    assert {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+            "dtype", "data", "config", "knobs"} == set(d)
+    assert d["n_gpus"] == 1 and d["steps"] == 5 and d["warmup"] == 2 and d["scaling"] == "weak"
+    assert d["unit"] == "frames/s" and d["higher_is_better"] is True and d["vs_baseline"] is None
+    assert d["dtype"] == "f32" and d["data"] == "synthetic" and "configs[2]" in d["config"]["workload"]
+    assert d["metric"] == "256x256 frames/sec (dense-motion + generator forward)"
+    assert abs(d["value"] - 5 * 16 / (d["ms_per_step"] * 5e-3)) / d["value"] < 0.01   # value == frames / timed seconds
+    assert d["knobs"]["plan"]["frames"] == 16 and d["knobs"]["experiments_build"] == 0
+
+
 def test_bench_512_batch8_line():
     """BASELINE configs[4]: --size 512 (batch 8 by default) prints the same line for the 512x512 workload."""
     d = run([sys.executable, "bench.py", "--size", "512", "--steps", "3", "--warmup", "1", "--cpu-frames", "0",
-             "--clip-frames", "0"])
+             "--clip-frames", "0", "--full"])
     assert "512x512" in d["config"]["workload"] and "configs[4]" in d["config"]["workload"]
     assert d["config"]["frames_per_step_per_gpu"] == 8 and d["clip"] is None and d["cpu_baseline"] is None
     assert abs(d["value"] - 3 * 8 / (d["ms_per_step"] * 3e-3)) / d["value"] < 0.01
@@ -174,7 +188,7 @@ def test_bench_two_ranks_share_one_gpu():
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
     d = run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-             "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--clip-frames", "70", "--clip-gather", "--e2e-frames", "0"],
+             "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--clip-frames", "70", "--clip-gather", "--e2e-frames", "0", "--full"],
             env={"EAMM_BENCH_BACKEND": "gloo"})
     assert d["n_gpus"] == 2 and d["cpu_baseline"] is None and "source_broadcast_ms" in d
     k = d["clip"]    # 70 frames over 2 ranks: 35 each, broadcast + compute + uint8 gather timed
@@ -189,7 +203,7 @@ def test_bench_bare_gpus2_spawns_its_ranks():
     runs one rank per GPU over RCCL."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["EAMM_BENCH_BACKEND"] = "gloo"
-    out = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--clip-frames", "64", "--e2e-frames", "40"],
+    out = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--clip-frames", "64", "--e2e-frames", "40", "--full"],
                          cwd=ROOT, capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -210,7 +224,8 @@ def test_bench_rccl_path_single_rank():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
-    d = run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--cpu-frames", "0", "--clip-frames", "64", "--e2e-frames", "0"],
+    d = run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--cpu-frames", "0", "--clip-frames", "64", "--e2e-frames", "0",
+             "--full"],
             env={"EAMM_BENCH_FORCE_DIST": "1", "RANK": "0", "WORLD_SIZE": "1", "LOCAL_RANK": "0",
                  "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(port)})
     assert d["n_gpus"] == 1 and "source_broadcast_ms" in d and d["value"] > 0 and d["rccl_warmup_ms"] > 0
@@ -225,7 +240,8 @@ def test_bench_refuses_a_wrong_results_knob():
                          env={**os.environ, "EAMM_WINO4_EPI_V": "1"})
     assert out.returncode != 0 and not [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert "EAMM_WINO4_EPI_V" in out.stderr and "EXPERIMENTS" in out.stderr
-    d = run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--cpu-frames", "0", "--clip-frames", "0", "--train-pairs", "0", "--e2e-frames", "0"],
+    d = run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--cpu-frames", "0", "--clip-frames", "0", "--train-pairs", "0", "--e2e-frames", "0",
+             "--full"],
             env={"EAMM_PASS_CHAINS": "1", "EAMM_FINAL_FUSED_MIN_ROWS": "100000"})
     # a documented knob is honoured and recorded; a TUNING aid without EAMM_TUNING=1 is ignored (and reported as such): a stray
     # variable cannot change the plan silently

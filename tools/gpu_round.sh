@@ -10,8 +10,8 @@ mkdir -p $O
 cd $R
 timeout 1500 python -m pytest tests -m gpu -x -q -s > $O/pytest_gpu.log 2>&1; echo "pytest rc=$?" | tee -a $O/pytest_gpu.log
 tail -5 $O/pytest_gpu.log
-timeout 600 python bench.py > $O/bench_256_b16.log 2>&1; grep '^{' $O/bench_256_b16.log > $O/bench_256_b16.json; cut -c1-600 $O/bench_256_b16.json
-timeout 600 python bench.py --size 512 --cpu-frames 0 --clip-frames 512 > $O/bench_512_b8.log 2>&1; grep '^{' $O/bench_512_b8.log > $O/bench_512_b8.json; cut -c1-400 $O/bench_512_b8.json
+timeout 600 python bench.py --full > $O/bench_256_b16.log 2>&1; grep '^{' $O/bench_256_b16.log > $O/bench_256_b16.json; cut -c1-600 $O/bench_256_b16.json
+timeout 600 python bench.py --full --size 512 --cpu-frames 0 --clip-frames 512 > $O/bench_512_b8.log 2>&1; grep '^{' $O/bench_512_b8.log > $O/bench_512_b8.json; cut -c1-400 $O/bench_512_b8.json
 timeout 300 python tools/module_latency.py > $O/module_latency.txt 2>&1; cat $O/module_latency.txt
 timeout 300 python tools/bn_bench.py 2>&1 < /dev/null | grep -v amdgpu.ids > $O/bn_bench.txt; cat $O/bn_bench.txt
 timeout 300 python tools/backward_bench.py 16 2>&1 < /dev/null | grep -v amdgpu.ids > $O/backward_bench.txt; cut -c1-260 $O/backward_bench.txt
