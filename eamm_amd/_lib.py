@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libeamm_hip.so")
 
-ABI_VERSION = 5   # round 6: split NHWC hand-over DeconvTail -> KPDetector_a (eamm_deconv_forward_split, eamm_kp_detect_features_split)
+ABI_VERSION = 6   # the emotion detector Emotion_k (eamm_emo_*)
 
 EAMM_OK = 0
 ERR_ARG, ERR_STATE, ERR_KEY, ERR_HIP, ERR_NUMERIC = -1, -2, -3, -4, -5
@@ -58,6 +58,17 @@ class EammKpOutputs(C.Structure):
     _fields_ = [("value", C.c_void_p), ("jacobian", C.c_void_p), ("heatmap", C.c_void_p)]
 
 
+class EammEmoConfig(C.Structure):
+    _fields_ = [
+        ("block_expansion", C.c_int32), ("num_channels", C.c_int32), ("max_features", C.c_int32), ("num_blocks", C.c_int32),
+        ("inv_scale", C.c_int32), ("num_classes", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("max_batch", C.c_int32),
+    ]
+
+
+class EammEmoOutputs(C.Structure):
+    _fields_ = [("value", C.c_void_p), ("jacobian", C.c_void_p), ("fake", C.c_void_p), ("feature", C.c_void_p)]
+
+
 # name -> (restype, argtypes); kept in one table so tests can check that every symbol declared in
 # include/eamm_hip.h is exported and bound.
 SIGNATURES = {
@@ -95,6 +106,12 @@ SIGNATURES = {
     "eamm_kp_detect_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(EammKpOutputs), C.c_void_p]),
     "eamm_kp_split_channels": (C.c_int, [C.c_void_p]),
     "eamm_kp_detect_features_split": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(EammKpOutputs), C.c_void_p]),
+    "eamm_emo_create": (C.c_int, [C.POINTER(EammEmoConfig), C.c_int, C.POINTER(C.c_void_p)]),
+    "eamm_emo_destroy": (None, [C.c_void_p]),
+    "eamm_emo_last_error": (C.c_char_p, [C.c_void_p]),
+    "eamm_emo_load_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
+    "eamm_emo_finalize_weights": (C.c_int, [C.c_void_p]),
+    "eamm_emo_detect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(EammEmoOutputs), C.c_void_p]),
     "eamm_deconv_create": (C.c_int, [C.POINTER(EammDeconvConfig), C.c_int, C.POINTER(C.c_void_p)]),
     "eamm_deconv_destroy": (None, [C.c_void_p]),
     "eamm_deconv_last_error": (C.c_char_p, [C.c_void_p]),
@@ -206,7 +223,8 @@ def lib() -> C.CDLL:
     return _lib
 
 
-def check(code: int, ctx=None, kp: bool = False, deconv: bool = False):
+def check(code: int, ctx=None, kp: bool = False, deconv: bool = False, emo: bool = False):
     if code != EAMM_OK:
-        msg = (lib().eamm_deconv_last_error if deconv else lib().eamm_kp_last_error if kp else lib().eamm_last_error)(ctx)
+        msg = (lib().eamm_emo_last_error if emo else lib().eamm_deconv_last_error if deconv else lib().eamm_kp_last_error if kp
+               else lib().eamm_last_error)(ctx)
         raise EammError(code, msg.decode() if msg else "?")

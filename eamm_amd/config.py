@@ -81,3 +81,9 @@ def tiny_kp_config(audio: bool = False) -> dict:
     if audio:
         c["num_channels_a"] = 3
     return c
+
+
+# emotion detector Emotion_k: reference demo.py:68-70 builds Emotion_k(block_expansion=32, num_channels=3, max_features=1024,
+# num_blocks=5, scale_factor=0.25, num_classes=8)
+def emotion_detector_config() -> dict:
+    return {"block_expansion": 32, "num_channels": 3, "max_features": 1024, "num_blocks": 5, "scale_factor": 0.25, "num_classes": 8}

@@ -1,0 +1,226 @@
+// Stride-2 KSxKS convolution (pad KS/2) on NHWC fp32 activations as an implicit GEMM on the CDNA4 matrix cores: the first
+// 3x3 convolution of a down-sampling ResNet BasicBlock and its 1x1 `downsample` shortcut (reference modules/util.py:1069-1099,
+// Emotion_k layer2..layer4, :1291-1305).
+//
+// The same GEMM as conv_mfma.hip's register-staged kernel -- M = B*Ho*Wo output pixels, N = Cout, K = taps * Cin, exact fp32
+// via v_mfma_f32_32x32x2_f32, both operands staged HBM/L2 -> VGPR -> LDS with raw buffer loads (an out-of-range offset reads
+// zero: the padding), LDS double buffer, one barrier per 32-channel K chunk -- with the stride in the operand loader: output
+// pixel (oy, ox) reads input pixel (2 oy + ky - KS/2, 2 ox + kx - KS/2).  The weights are pack_conv's plain image
+// ([ntiles][nchunks][BN][BK]), the epilogue (bias, residual, activation) and split-K slabs are conv_common.h's, so nothing of
+// the stride-1 kernels changes.
+#include "conv_common.h"
+
+#include <algorithm>
+#include <cstring>
+
+namespace eamm {
+
+template <int KS, int MT, int NT, int WM, int WN>
+__global__ __launch_bounds__(256) void conv_s2_kernel(const ConvArgs p, int Hin, int Win) {
+    constexpr int BM = WM * MT * 32, BN = WN * NT * 32;
+    constexpr int BK = CONV_BK, LDK = CONV_LDK;
+    constexpr int T = KS * KS;
+    constexpr int A_PER = BM / 32, B_PER = BN / 32;
+    static_assert(WM * WN == 4, "4 waves per block");
+
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* As = smem;                 // [2][BM][LDK]
+    float* Bs = smem + 2 * BM * LDK;  // [2][BN][LDK]
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int l31 = lane & 31, half = lane >> 5;
+    const int wm = wave / WN, wn = wave % WN;
+
+    int L = xcd_remap(blockIdx.x, gridDim.x);
+    const int ntile = L % p.ntiles;
+    L /= p.ntiles;
+    const int mtile = L % p.mtiles;
+    L /= p.mtiles;
+    const int split = L;
+    const int mbase = mtile * BM;
+    const int c_begin = split * p.chunks_per_split;
+    const int c_end = min(p.nchunks, c_begin + p.chunks_per_split);
+
+    // operand loader: this thread stages rows arow+32j, 16 bytes at column acol; (ry, rx) = the input pixel of tap (0, 0) + pad
+    const int arow = tid >> 3, acol = (tid & 7) * 4;
+    int ry[A_PER], rx[A_PER], rb[A_PER];
+#pragma unroll
+    for (int j = 0; j < A_PER; ++j) {
+        const int m = mbase + arow + 32 * j;
+        if (m < p.M) {
+            int b, y, x;
+            pix_decode(p, m, b, y, x);
+            ry[j] = 2 * y;
+            rx[j] = 2 * x;
+            rb[j] = b * Hin * Win;
+        } else {
+            ry[j] = -(1 << 20);  // never inside the image
+            rx[j] = 0;
+            rb[j] = 0;
+        }
+    }
+
+    const __amdgpu_buffer_rsrc_t rs0 = __builtin_amdgcn_make_buffer_rsrc((void*)p.in0, 0, p.in0_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.w_bytes, 0x00020000);
+    constexpr unsigned OOB = 0xFFFFFFF0u;
+    const int wtile = ntile * p.nchunks;
+
+    u32x4 av[A_PER], bv[B_PER];
+    auto load_chunk = [&](int ci) {
+        const int cc = ci / T, tap = ci - cc * T;
+        const int dy = tap / KS - KS / 2, dx = tap % KS - KS / 2;
+        const int coff = cc * BK + acol;
+#pragma unroll
+        for (int j = 0; j < A_PER; ++j) {
+            const int yy = ry[j] + dy, xx = rx[j] + dx;
+            const bool ok = ((unsigned)yy < (unsigned)Hin) & ((unsigned)xx < (unsigned)Win);
+            const unsigned off = ok ? (unsigned)((rb[j] + yy * Win + xx) * p.C0 + coff) * 4u : OOB;
+            av[j] = __builtin_amdgcn_raw_buffer_load_b128(rs0, off, 0, 0);
+        }
+        const unsigned woff = (unsigned)((wtile + ci) * (BN * BK) + tid * 4) * 4u;
+#pragma unroll
+        for (int j = 0; j < B_PER; ++j) bv[j] = __builtin_amdgcn_raw_buffer_load_b128(rsw, woff + j * 4096u, 0, 0);
+    };
+    auto store_chunk = [&](int st) {
+        float* a = As + st * BM * LDK + arow * LDK + acol;
+#pragma unroll
+        for (int j = 0; j < A_PER; ++j) *reinterpret_cast<u32x4*>(a + j * 32 * LDK) = av[j];
+        float* b = Bs + st * BN * LDK + arow * LDK + acol;
+#pragma unroll
+        for (int j = 0; j < B_PER; ++j) *reinterpret_cast<u32x4*>(b + j * 32 * LDK) = bv[j];
+    };
+
+    f32x16 acc[MT][NT];
+    static_for<MT>([&](auto ic) {
+        static_for<NT>([&](auto jc) {
+            static_for<16>([&](auto rc) { acc[decltype(ic)::value][decltype(jc)::value][decltype(rc)::value] = 0.f; });
+        });
+    });
+
+    auto compute = [&](int st) {
+        const float* a_base = As + st * BM * LDK + (wm * MT * 32 + l31) * LDK + half * 4;
+        const float* b_base = Bs + st * BN * LDK + (wn * NT * 32 + l31) * LDK + half * 4;
+#pragma unroll
+        for (int s = 0; s < BK / 8; ++s) {
+            f32x4 a[MT], b[NT];
+#pragma unroll
+            for (int i = 0; i < MT; ++i) a[i] = *reinterpret_cast<const f32x4*>(a_base + i * 32 * LDK + s * 8);
+#pragma unroll
+            for (int j = 0; j < NT; ++j) b[j] = *reinterpret_cast<const f32x4*>(b_base + j * 32 * LDK + s * 8);
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+#pragma unroll
+                for (int i = 0; i < MT; ++i)
+#pragma unroll
+                    for (int j = 0; j < NT; ++j)
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i][t], b[j][t], acc[i][j], 0, 0, 0);
+        }
+    };
+
+    if (c_begin < c_end) {
+        load_chunk(c_begin);
+        store_chunk(0);
+        __syncthreads();
+        int st = 0;
+        for (int ci = c_begin; ci < c_end; ++ci) {
+            const bool more = ci + 1 < c_end;
+            if (more) load_chunk(ci + 1);  // buffer loads in flight under the MFMAs
+            compute(st);
+            if (more) store_chunk(st ^ 1);
+            __syncthreads();
+            st ^= 1;
+        }
+    }
+
+    conv_epilogue<MT, NT, BN>(p, acc, mbase, ntile, wm, wn, l31, half, 0, split);
+}
+
+// split-K: the slabs summed in slice order (fixed, no atomics), then conv_common.h's epilogue
+__global__ __launch_bounds__(256) void conv_s2_reduce_kernel(const ConvArgs p, int splits) {
+    const size_t total = (size_t)p.M * p.Cout;
+    const size_t slab = (size_t)p.Mpad * p.Npad;
+    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
+        const int n = (int)(idx % p.Cout);
+        const int r = (int)(idx / p.Cout);
+        float s = 0.f;
+        for (int sp = 0; sp < splits; ++sp) s += p.partial[(size_t)sp * slab + (size_t)r * p.Npad + n];
+        int b, y, x;
+        pix_decode(p, r, b, y, x);
+        epilogue_store(p, 0, b, y, x, n, s + p.bias[n], 0.f, 0.f);
+    }
+}
+
+template <int KS, int MT, int NT, int WM, int WN>
+static hipError_t s2_cfg(const ConvArgs& a, int Hin, int Win, int blocks, hipStream_t stream) {
+    constexpr int BM = WM * MT * 32, BN = WN * NT * 32;
+    constexpr size_t lds = sizeof(float) * 2 * (BM + BN) * CONV_LDK;
+    auto kern = conv_s2_kernel<KS, MT, NT, WM, WN>;
+    static lds_once_mask configured{0};
+    if (hipError_t e = ensure_dynamic_lds(kern, lds, &configured); e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, stream, a, Hin, Win);
+    return hipGetLastError();
+}
+
+template <int KS>
+static hipError_t s2_tile(int BN, const ConvArgs& a, int Hin, int Win, int blocks, hipStream_t stream) {
+    if (BN == 128) return s2_cfg<KS, 2, 2, 2, 2>(a, Hin, Win, blocks, stream);
+    if (BN == 64) return s2_cfg<KS, 2, 1, 2, 2>(a, Hin, Win, blocks, stream);
+    if (BN == 32) return s2_cfg<KS, 1, 1, 4, 1>(a, Hin, Win, blocks, stream);
+    return hipErrorInvalidValue;
+}
+
+size_t conv_s2_partial_elems(const ConvLayer& L, int B, int Hin, int Win) {
+    return conv_plan(L, B * (Hin / 2) * (Win / 2)).partial_elems;
+}
+
+hipError_t conv_s2_launch(const ConvLayer& L, const float* in, int B, int Hin, int Win, int act, const float* resid, float* out,
+                          float* partial, size_t partial_cap, hipStream_t stream) {
+    if (L.phase || L.dma_cfg || L.C1 || L.kh != L.kw || (L.kh != 1 && L.kh != 3) || (Hin & 1) || (Win & 1) || L.BM != 128)
+        return hipErrorInvalidValue;
+    ConvArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.in0 = in;
+    a.C0 = L.C0;
+    a.H = Hin / 2;
+    a.W = Win / 2;
+    a.nphase = 1;
+    a.M = B * a.H * a.W;
+    a.w = L.w;
+    {   // buffer-descriptor ranges (32-bit)
+        const size_t b0 = (size_t)B * Hin * Win * L.C0 * sizeof(float);
+        const size_t bw = (size_t)L.ntiles * L.nchunks * L.BN * CONV_BK * sizeof(float);
+        if (b0 >= 0xFFFFFFF0ull || bw >= 0xFFFFFFF0ull) return hipErrorInvalidValue;
+        a.in0_bytes = (unsigned)b0;
+        a.w_bytes = (unsigned)bw;
+    }
+    a.bias = L.bias;
+    a.Cout = L.Cout;
+    a.nchunks = L.nchunks;
+    ConvPlan pl = conv_plan(L, a.M);
+    while (pl.splits > 1 && pl.partial_elems > partial_cap) pl = conv_plan(L, a.M, pl.splits - 1);
+    if (pl.splits > 1 && partial == nullptr) return hipErrorInvalidValue;
+    a.mtiles = pl.mtiles;
+    a.ntiles = pl.ntiles;
+    a.chunks_per_split = pl.chunks_per_split;
+    a.Mpad = pl.Mpad;
+    a.Npad = pl.Npad;
+    a.partial = pl.splits > 1 ? partial : nullptr;
+    a.act = act;
+    a.resid = resid;
+    a.out = out;
+    a.linear = ((a.H | a.W) & 1) ? 1 : 0;
+    const int blocks = pl.mtiles * pl.ntiles * pl.splits;
+    note_mfma_flops(2.0 * pl.mtiles * L.BM * (double)pl.ntiles * L.BN * (double)L.nchunks * CONV_BK);
+    hipError_t e = L.kh == 3 ? s2_tile<3>(L.BN, a, Hin, Win, blocks, stream) : s2_tile<1>(L.BN, a, Hin, Win, blocks, stream);
+    if (e != hipSuccess) return e;
+    if (pl.splits > 1) {
+        const size_t total = (size_t)a.M * L.Cout;
+        const int rb = (int)std::min<size_t>((total + 255) / 256, 4096);
+        hipLaunchKernelGGL(conv_s2_reduce_kernel, dim3(rb), dim3(256), 0, stream, a, pl.splits);
+        e = hipGetLastError();
+    }
+    return e;
+}
+
+}  // namespace eamm

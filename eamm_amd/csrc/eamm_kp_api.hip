@@ -6,17 +6,16 @@
 // network's (pool in the epilogue, collapsed up-conv, concat in the loader), the `kp` and `jacobian` 7x7
 // convolutions run as ONE "same"-padded MFMA convolution (the reference's pad-0 output is its interior), and
 // kp_head_kernel does the temperature softmax, soft-argmax and jacobian reduction per (image, key point).
-#include "api_common.h"
+#include "hourglass_common.h"
 
 using namespace eamm;
 
 struct eamm_kp_ctx : eamm::CtxBase {
     eamm_kp_config cfg{};
-    int H = 0, W = 0, h = 0, w = 0, K = 0, nb = 0, njm = 0;
+    int H = 0, W = 0, h = 0, w = 0, K = 0, njm = 0;
     int Cin_pad = 32;             // RGB (or feature-map) channels padded to a multiple of 32
     int feat_c = 0;               // hourglass out_filters = block_expansion + in_features
-    std::vector<int> enc_c, dec_c;
-    std::vector<LayerSet> hg_enc, hg_dec;
+    Hourglass hg;                 // the predictor (hourglass_common.h)
     ConvLayer head;               // kp (K) + jacobian (4*njm) stacked along Cout
     ConvLayer head_dma;           // the same filters packed for the LDS-DMA tile (512 x 64 / 256 x 128), batched calls (round 6: the wide 7x7 head was
     bool has_head_dma = false;    // 73 % of KPDetector_a's time per frame at 0.38 of the fp32 matrix peak on the register-staged tile; 0.75 here)
@@ -33,7 +32,6 @@ struct eamm_kp_ctx : eamm::CtxBase {
     float* head_ws = nullptr;     // kp_head_launch's workspace (pixel-sliced reductions of batched calls)
     float *x_in = nullptr, *logits = nullptr, *partial = nullptr;
     size_t partial_elems = 0;
-    std::vector<float*> e_buf, u_buf;
 };
 
 namespace {
@@ -103,12 +101,10 @@ int eamm_kp_create(const eamm_kp_config* cfg, int device, eamm_kp_ctx** out) {
     c->h = c->H / g.inv_scale;
     c->w = c->W / g.inv_scale;
     c->K = g.num_kp;
-    c->nb = g.num_blocks;
     c->njm = g.estimate_jacobian ? (g.single_jacobian_map ? 1 : g.num_kp) : 0;
     c->head_cs = (c->K + 4 * c->njm + 63) / 64 * 64;
     c->feat_c = g.block_expansion + g.in_features;
-    for (int i = 0; i < c->nb; ++i) c->enc_c.push_back(std::min(g.max_features, g.block_expansion << (i + 1)));
-    for (int i = c->nb - 1; i >= 0; --i) c->dec_c.push_back(std::min(g.max_features, g.block_expansion << i));
+    hg_channels(&c->hg, g.block_expansion, g.max_features, g.num_blocks);
     read_tile_knobs(c);
     *out = c;
     return EAMM_OK;
@@ -137,8 +133,7 @@ int eamm_kp_finalize_weights(eamm_kp_ctx* c) {
             want.push_back("jacobian.bias");
         }
         if (g.with_predictor) {
-            for (int i = 0; i < c->nb; ++i) block_keys("predictor.encoder.down_blocks." + std::to_string(i), &want);
-            for (int i = 0; i < c->nb; ++i) block_keys("predictor.decoder.up_blocks." + std::to_string(i), &want);
+            hg_keys("predictor", c->hg.nb, &want);
             if (g.inv_scale != 1) want.push_back("down.weight");
         }
         if (int rc = check_keys(c, want)) return rc;
@@ -153,35 +148,11 @@ int eamm_kp_finalize_weights(eamm_kp_ctx* c) {
     const int head_dma_cfg = c->head_dma_min_m < 0 ? 0 : (c->head_cs == 64 ? 3 : (c->head_cs == 128 ? 2 : 0));
     c->has_head_dma = head_dma_cfg != 0;
     if (g.with_predictor) {
-        c->hg_enc.resize(c->nb);
-        c->hg_dec.resize(c->nb);
-        for (int i = 0; i < c->nb; ++i) {
-            const std::string p = "predictor.encoder.down_blocks." + std::to_string(i);
-            const int cr = i == 0 ? cin : c->enc_c[i - 1], cp = i == 0 ? c->Cin_pad : c->enc_c[i - 1];
-            if ((rc = build_set(c, {{p + ".conv", p + ".norm"}}, cr, cp, 0, 0, &c->hg_enc[i], MODE_PLAIN))) return rc;
-        }
-        for (int i = 0; i < c->nb; ++i) {
-            const std::string p = "predictor.decoder.up_blocks." + std::to_string(i);
-            const int c0 = i == 0 ? c->enc_c[c->nb - 1] : c->dec_c[i - 1];
-            const int c1 = i == 0 ? 0 : c->enc_c[c->nb - 1 - i];
-            if ((rc = build_set(c, {{p + ".conv", p + ".norm"}}, c0, c0, c1, c1, &c->hg_dec[i], MODE_PHASE))) return rc;
-        }
+        if ((rc = hg_build(c, &c->hg, "predictor", cin, c->Cin_pad))) return rc;
         // head input = cat[last up output (block_expansion), hourglass input (cin, stored padded)]  util.py:981-987
-        if ((rc = build_layer(c, parts, 7, c->dec_c.back(), c->dec_c.back(), cin, c->Cin_pad, &c->head))) return rc;
-        if (head_dma_cfg && (rc = build_layer(c, parts, 7, c->dec_c.back(), c->dec_c.back(), cin, c->Cin_pad, &c->head_dma, MODE_PLAIN, nullptr, head_dma_cfg))) return rc;
-        std::vector<float> aa((size_t)std::max(3, g.num_channels) * 169, 0.f);
-        if (g.inv_scale != 1) {
-            const HostTensor* t = find(c, "down.weight");
-            if (!t || (int)t->numel() != g.num_channels * 169)
-                return fail(c, EAMM_ERR_KEY, "down.weight must be [%d,1,13,13]", g.num_channels);
-            std::copy(t->data.begin(), t->data.end(), aa.begin());   // (the planes an image does not have keep zero filters)
-        }
-        if ((rc = upload(c, &c->aa_w, aa))) return rc;
-        if (g.num_channels < 3) {   // one / two image channels: the hourglass's first block has filters for those only (cin above)
-            const size_t n = (size_t)g.max_batch * 3 * c->H * c->W;
-            if ((rc = dev_alloc(c, &c->img_stage, n))) return rc;
-            HIP_TRY(c, hipMemset(c->img_stage, 0, n * sizeof(float)));
-        }
+        if ((rc = build_layer(c, parts, 7, c->hg.dec_c.back(), c->hg.dec_c.back(), cin, c->Cin_pad, &c->head))) return rc;
+        if (head_dma_cfg && (rc = build_layer(c, parts, 7, c->hg.dec_c.back(), c->hg.dec_c.back(), cin, c->Cin_pad, &c->head_dma, MODE_PLAIN, nullptr, head_dma_cfg))) return rc;
+        if ((rc = hg_build_input(c, g.num_channels, g.inv_scale, c->H, c->W, g.max_batch, &c->aa_w, &c->img_stage))) return rc;
     } else {
         // KPDetector_a: the caller's feature map already is the hourglass output (feat_c channels)
         const int cp = (c->feat_c + 31) / 32 * 32;
@@ -232,18 +203,7 @@ int eamm_kp_finalize_weights(eamm_kp_ctx* c) {
     if ((rc = dev_alloc(c, &c->logits, F * hw * c->head_cs))) return rc;
     if ((rc = dev_alloc(c, &c->head_ws, kp_head_workspace_floats((int)F, c->K)))) return rc;
     size_t need = 0;
-    if (g.with_predictor) {
-        c->e_buf.resize(c->nb);
-        c->u_buf.resize(c->nb);
-        for (int i = 0; i < c->nb; ++i) {
-            if ((rc = dev_alloc(c, &c->e_buf[i], F * (hw >> (2 * (i + 1))) * c->enc_c[i]))) return rc;
-            if ((rc = dev_alloc(c, &c->u_buf[i], F * (hw >> (2 * (c->nb - 1 - i))) * c->dec_c[i]))) return rc;
-        }
-        for (size_t f = 1; f <= F; ++f)
-            for (int i = 0; i < c->nb; ++i)
-                need = std::max({need, set_partial_elems(c->hg_enc[i], f * (hw >> (2 * i))),
-                                 set_partial_elems(c->hg_dec[i], f * (hw >> (2 * (c->nb - i))))});
-    }
+    if (g.with_predictor && (rc = hg_alloc(c, &c->hg, F, hw, &need))) return rc;
     for (size_t f = 1; f <= F; ++f) {
         need = std::max(need, conv_plan(c->head, (int)(f * hw)).partial_elems);
         if (c->has_head_dma) need = std::max(need, conv_plan(c->head_dma, (int)(f * hw)).partial_elems);
@@ -263,47 +223,10 @@ int eamm_kp_detect(eamm_kp_ctx* c, const float* image, int B, const eamm_kp_outp
     if (guard.status != hipSuccess) return fail(c, EAMM_ERR_HIP, "hipSetDevice(%d) failed", c->device);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream_);
     const int h = c->h, w = c->w;
-    if (c->img_stage) {   // [B,C,H,W] into the first C planes of [B,3,H,W]
-        const size_t HW = (size_t)c->H * c->W * sizeof(float), C = (size_t)c->cfg.num_channels;
-        HIP_TRY(c, hipMemcpy2DAsync(c->img_stage, 3 * HW, image, C * HW, C * HW, (size_t)B, hipMemcpyDeviceToDevice, s));
-        image = c->img_stage;
-    }
-    // x = down(x): anti-aliased, NHWC zero-padded to Cin_pad channels            keypoint_detector.py:79-80
-    if (c->cfg.num_channels <= 3) {
-        HIP_TRY(c, antialias_down_launch(image, c->aa_w, B, c->H, c->W, c->cfg.inv_scale, c->Cin_pad, c->x_in, s));
-    } else {   // four to eight channels: four per float4 slot, straight from the caller's [B,C,H,W] (real channels stay contiguous)
-        const int C = c->cfg.num_channels;
-        for (int g0 = 0, slot = 0; g0 < C; g0 += 4, ++slot)
-            HIP_TRY(c, antialias_down_launch(image, c->aa_w, B, c->H, c->W, c->cfg.inv_scale, c->Cin_pad, c->x_in, s, C, g0,
-                                             std::min(4, C - g0), slot));
-    }
-    for (int i = 0; i < c->nb; ++i) {   // hourglass encoder                      util.py:956-960
-        ConvIO io{};
-        io.in0 = i == 0 ? c->x_in : c->e_buf[i - 1];
-        io.B = B;
-        io.Hin = h >> i;
-        io.Win = w >> i;
-        io.act = ACT_RELU;
-        io.pool = 1;
-        io.out = c->e_buf[i];
-        io.partial = c->partial;
-        io.partial_cap = c->partial_elems;
-        HIP_TRY(c, conv_launch(pick(c, c->hg_enc[i], (size_t)B * io.Hin * io.Win), io, s));
-    }
-    for (int i = 0; i < c->nb; ++i) {   // hourglass decoder                      util.py:981-987
-        ConvIO io{};
-        io.in0 = i == 0 ? c->e_buf[c->nb - 1] : c->u_buf[i - 1];
-        io.in1 = i == 0 ? nullptr : c->e_buf[c->nb - 1 - i];
-        io.B = B;
-        io.Hin = h >> (c->nb - i);
-        io.Win = w >> (c->nb - i);
-        io.act = ACT_RELU;
-        io.out = c->u_buf[i];
-        io.partial = c->partial;
-        io.partial_cap = c->partial_elems;
-        if (int urc = launch_up(c, c->hg_dec[i], io, s)) return urc;
-    }
-    return run_head(c, c->u_buf[c->nb - 1], c->x_in, B, o, s);   // keypoint_detector.py:83-103
+    if (int rc = hg_input(c, image, c->aa_w, c->img_stage, B, c->cfg.num_channels, c->H, c->W, c->cfg.inv_scale, c->Cin_pad, c->x_in, s))
+        return rc;
+    if (int rc = hg_run(c, c->hg, c->x_in, B, h, w, c->partial, c->partial_elems, s)) return rc;
+    return run_head(c, c->hg.u_buf[c->hg.nb - 1], c->x_in, B, o, s);   // keypoint_detector.py:83-103
 }
 
 int eamm_kp_detect_features(eamm_kp_ctx* c, const float* feature_map, int B, const eamm_kp_outputs* o, void* stream_) {

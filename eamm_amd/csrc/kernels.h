@@ -287,6 +287,20 @@ hipError_t motion_head_backward_launch(const float* mask, const float* occlusion
                                        float* drec, float* workspace, hipStream_t s);
 
 // One-Euro smoothing of [T,E] sequences along T (keypoints.hip; reference filter1.py:13-47 as driven by demo.py:241-250).
+// Emotion detector Emotion_k (conv_s2.hip, emotion.hip).  conv_s2_launch: a stride-2 KSxKS convolution (KS 1 or 3, pad KS/2) of a
+// plain pack_conv layer on NHWC [B,Hin,Win,C0] (Hin, Win even) -> [B,Hin/2,Win/2,Cout], bias + resid + act epilogue, split-K through
+// `partial` (at most partial_cap floats; conv_s2_partial_elems: the plan's need).
+size_t conv_s2_partial_elems(const ConvLayer& L, int B, int Hin, int Win);
+hipError_t conv_s2_launch(const ConvLayer& L, const float* in, int B, int Hin, int Win, int act, const float* resid, float* out,
+                          float* partial, size_t partial_cap, hipStream_t stream);
+hipError_t emo_maxpool_launch(const float* in /*[B,H,W,C]*/, int B, int H, int W, int C, float* out /*[B,H/2,W/2,C]*/, hipStream_t s);
+hipError_t emo_avgpool_launch(const float* in /*[B,P,C]*/, int B, int P, int C, float* out /*[B,C]*/, hipStream_t s);
+hipError_t emo_embed_launch(const float* value /*[B,10,2]*/, const float* jacobian /*[B,10,2,2]*/, int B, float* out /*[B,1260]*/,
+                            hipStream_t s);
+hipError_t emo_linear_launch(const float* x0, int K0, const float* x1, int K1, const float* wt /*[K0+K1][O]*/, const float* bias, int O,
+                             int B, int relu, float* out /*[B,O]*/, hipStream_t s);
+hipError_t emo_final_launch(const float* a /*[B,64]*/, const float* w /*98 floats*/, int B, float* value, float* jacobian, hipStream_t s);
+
 hipError_t one_euro_launch(const float* x, int T, int E, float mincutoff, float beta, float dcutoff, float freq, float scale,
                            float* out, hipStream_t stream, float* state = nullptr, int resume = 0);
 

@@ -15,8 +15,12 @@ LSTM features in, the clip's frames in host memory out -- every step of the refe
            prediction.cpu().numpy() transposed             demo.py:281        uint8 / float frames copied to pinned host memory
                                                                               overlapped with the next batch's kernels
 
-The emotion network (``emo_detector``) and the audio LSTM are outside this path (out of scope / "stays in
-PyTorch-ROCm"): their outputs are inputs here -- ``lstm_features`` [T,256] and, optionally, ``emo_driving``.
+    for t: emo_detector(transformed_frame, raw kp)         demo.py:221-228 EmotionDetector.detect, `front_batch` frames per call
+                                                                              (``emo_detector`` + ``emotion_frames``)
+
+The audio LSTM is outside this path ("stays in PyTorch-ROCm"): its output is an input here --
+``lstm_features`` [T,256].  The emotion displacements are either computed here (``emo_detector`` + ``emotion_frames``, the
+reference's ``transformed_video``) or passed in precomputed (``emo_driving``).
 Under torch.distributed BOTH loops shard by frames: rank 0's inputs are broadcast (header + one payload), every rank runs the
 detectors on its frames, one all-gather gives every rank the whole key-point sequence (the One-Euro recurrence needs it; 0.7 ms,
 computed redundantly), and every rank animates its shard from its own encoding of the source -- three collectives per clip.
@@ -47,7 +51,8 @@ def animate_from_features(generator, kp_detector, deconv_tail, kp_detector_a, so
                           relative: bool = True, adapt_movement_scale: bool = True, smooth: bool = True, batch: int = 64,
                           front_batch: int = 256, uint8: bool = True, to_host: bool = True, group=None,
                           backend: Optional[EngineBackend] = None, timings: Optional[Dict[str, float]] = None,
-                          return_keypoints: bool = False, size: Optional[Tuple[int, int]] = None, stream: Optional[bool] = None):
+                          return_keypoints: bool = False, size: Optional[Tuple[int, int]] = None, stream: Optional[bool] = None,
+                          emo_detector=None, emotion_frames: Optional[torch.Tensor] = None):
     """make_animation_smooth (demo.py:194-282) for one clip.
 
     ``source_image``: [1,C,H,W] float in [0,1]; ``lstm_features``: [T,256] (or [1,T,256]), the audio network's LSTM output;
@@ -58,7 +63,12 @@ def animate_from_features(generator, kp_detector, deconv_tail, kp_detector_a, so
     the inputs (they are broadcast from rank 0).  ``timings`` is filled with the phases' wall-clock milliseconds (a device synchronisation at each
     boundary, only when asked for): front_ms (detectors), smooth_ms, normalize_ms, then animate_clip's own.  ``stream`` (default:
     on for one process on a GPU when no ``timings`` are asked for): the front end runs on its own stream, `front_batch` frames at
-    a time, BESIDE the generator of the frames whose key points are already complete (``_animate_streaming``)."""
+    a time, BESIDE the generator of the frames whose key points are already complete (``_animate_streaming``).
+
+    ``emo_detector`` (an ``EmotionDetector``) with ``emotion_frames`` [T,C,H,W] float in [0,1] (the reference's
+    ``transformed_video``, demo.py:221-228): ``emo_driving`` is computed on the device from the RAW (un-smoothed) driving key
+    points, ``front_batch`` frames per call, then smoothed and applied like a given one.  With ``return_keypoints`` the dict also
+    holds ``emo_driving`` (raw) and ``emotion_features`` [T,512] (``emo_detector.feature``)."""
     dev = backend.device if backend is not None else next(generator.parameters()).device
     on_gpu = torch.device(dev).type == "cuda"
     distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
@@ -75,6 +85,14 @@ def animate_from_features(generator, kp_detector, deconv_tail, kp_detector_a, so
         timings[name] = timings.get(name, 0.0) + (now - t_last[0]) * 1e3
         t_last[0] = now
 
+    if emotion_frames is not None or emo_detector is not None:
+        if emo_driving is not None:
+            raise ValueError("animate_from_features: pass either emo_driving or emo_detector + emotion_frames, not both")
+        if emotion_frames is None or emo_detector is None:
+            raise ValueError("animate_from_features: emo_detector and emotion_frames go together")
+        if distributed:
+            raise ValueError("animate_from_features: emotion_frames with a process group of more than one rank is not supported "
+                             "(the emotion frames are not sharded across ranks); compute emo_driving first and pass that instead")
     if backend is None:
         backend = EngineBackend(generator, batch=batch)
     if distributed:
@@ -96,12 +114,16 @@ def animate_from_features(generator, kp_detector, deconv_tail, kp_detector_a, so
         stream = on_gpu and not distributed and timings is None
     if stream and on_gpu and not distributed:
         return _animate_streaming(backend, kp_detector_a, deconv_tail, src, lstm_features.to(dev), kp_source, emo_driving, relative,
-                                  adapt_movement_scale, smooth, front_batch, uint8, to_host, return_keypoints, H, W, dev)
+                                  adapt_movement_scale, smooth, front_batch, uint8, to_host, return_keypoints, H, W, dev,
+                                  emo_detector, emotion_frames)
     a, b = shard_bounds(T, world, rank)
     raw = driving_keypoints(deconv_tail, kp_detector_a, lstm_features[a:b].to(dev), batch=front_batch) if b > a else None   # demo.py:212-219
     if distributed:
         raw = _all_gather_keypoints(raw, T, kp_source["value"].shape[1], dev, group)
     kp_initial = {k: v[:1].clone() for k, v in raw.items()}                                  # demo.py:207 (never smoothed)
+    emo_feats = None
+    if emotion_frames is not None:                                                           # demo.py:221-228
+        emo_driving, emo_feats = _emotion_driving(emo_detector, emotion_frames, raw, 0, T, front_batch, dev)
     mark("front_ms")
     kp_d = smooth_keypoints(raw, **KP_FILTER) if smooth else raw                             # demo.py:241-250
     if emo_driving is not None:
@@ -113,13 +135,30 @@ def animate_from_features(generator, kp_detector, deconv_tail, kp_detector_a, so
                            use_relative_movement=relative, use_relative_jacobian=relative)    # demo.py:276
     mark("normalize_ms")
     kps = {"kp_source": kp_source, "kp_driving_raw": raw, "kp_driving_smoothed": kp_d, "kp_norm": kp_norm} if return_keypoints else {}
+    if return_keypoints and emo_feats is not None:
+        kps["emo_driving"], kps["emotion_features"] = emo_driving, emo_feats
     frames, span = animate_clip(backend, src, kp_source, kp_norm, H, W, uint8=uint8, group=group, to_host=to_host,
                                 timings=timings, replicated=distributed)
     return (frames, span, kps) if return_keypoints else (frames, span)
 
 
+def _emotion_chunk(emo_detector, emotion_frames, raw, t0, t1, dev):
+    """emo_detector(transformed_frame, value, jacobian) and .feature(transformed_frame) of frames t0..t1 (demo.py:221-228), from
+    the raw driving key points of those frames (``raw``: the chunk's)."""
+    x = emotion_frames[t0:t1].to(dev, torch.float32)
+    out = emo_detector.detect(x, raw["value"], raw["jacobian"])
+    return {"value": out["value"], "jacobian": out["jacobian"]}, out["feature"]
+
+
+def _emotion_driving(emo_detector, emotion_frames, raw, t0, t1, front_batch, dev):
+    parts = [_emotion_chunk(emo_detector, emotion_frames, {k: v[s:min(t1, s + front_batch)] for k, v in raw.items()}, s,
+                            min(t1, s + front_batch), dev) for s in range(t0, t1, front_batch)]
+    emo = {k: torch.cat([p[0][k] for p in parts]) for k in ("value", "jacobian")}
+    return emo, torch.cat([p[1] for p in parts])
+
+
 def _animate_streaming(backend, kp_detector_a, deconv_tail, src, feats, kp_source, emo_driving, relative, adapt_movement_scale, smooth,
-                       front_batch, uint8, to_host, return_keypoints, H, W, dev):
+                       front_batch, uint8, to_host, return_keypoints, H, W, dev, emo_detector=None, emotion_frames=None):
     """One GPU, one process: the reference's FIRST loop (key points of every frame, demo.py:212-250) runs on its own stream,
     `front_batch` frames at a time, and the generator starts on the first frames as soon as their key points are complete --
     every step between the detector and the generator is causal (the One-Euro filter carries its memory from chunk to chunk:
@@ -133,7 +172,7 @@ def _animate_streaming(backend, kp_detector_a, deconv_tail, src, feats, kp_sourc
     if front is None:      # (small launches: a high-priority stream lets them in ahead of the generator's)
         front = backend._front_stream = torch.cuda.Stream(device=dev, priority=-1)
     norm = {"value": torch.empty(T, K, 2, device=dev), "jacobian": torch.empty(T, K, 2, 2, device=dev)}
-    keep = {"raw": [], "smoothed": []} if return_keypoints else None
+    keep = {"raw": [], "smoothed": [], "emo": [], "emo_feat": []} if return_keypoints else None
     emo = None if emo_driving is None else {k: v.to(dev) for k, v in _kp_only(emo_driving).items()}
     front.wait_stream(main)                        # the source's key points and the features are complete
     events, kp_state, emo_state, kp_initial, scale = [], {}, {}, None, None
@@ -146,8 +185,15 @@ def _animate_streaming(backend, kp_detector_a, deconv_tail, src, feats, kp_sourc
                 if adapt_movement_scale:
                     scale = movement_scale(kp_source, kp_initial)        # the clip's one host read (2 x K points), behind the first batch
             kp_d = smooth_keypoints(raw, **KP_FILTER, state=kp_state, resume=t0 > 0) if smooth else raw       # demo.py:241-250
-            if emo is not None:
+            e_c = None
+            if emotion_frames is not None:                                                                    # demo.py:221-228
+                e_c, e_f = _emotion_chunk(emo_detector, emotion_frames, raw, t0, t1, dev)
+                if keep is not None:
+                    keep["emo"].append(e_c)
+                    keep["emo_feat"].append(e_f)
+            elif emo is not None:
                 e_c = {k: v[t0:t1] for k, v in emo.items()}
+            if e_c is not None:
                 e_c = smooth_keypoints(e_c, **EMO_FILTER, state=emo_state, resume=t0 > 0) if smooth else e_c  # demo.py:231-239
                 kp_d = apply_emotion_offsets(kp_d, e_c)                                                       # demo.py:263-271
             n_c = normalize_kp(kp_source, kp_d, kp_initial, adapt_movement_scale=adapt_movement_scale, use_relative_movement=relative,
@@ -170,7 +216,10 @@ def _animate_streaming(backend, kp_detector_a, deconv_tail, src, feats, kp_sourc
         return frames, span
     # (concatenated on the caller's stream: the results belong to its allocator pool, the front stream's chunks die here, after the join)
     cat = lambda parts: {k: torch.cat([p[k] for p in parts]) for k in ("value", "jacobian")}
-    return frames, span, {"kp_source": kp_source, "kp_driving_raw": cat(keep["raw"]), "kp_driving_smoothed": cat(keep["smoothed"]), "kp_norm": norm}
+    kps = {"kp_source": kp_source, "kp_driving_raw": cat(keep["raw"]), "kp_driving_smoothed": cat(keep["smoothed"]), "kp_norm": norm}
+    if keep["emo"]:
+        kps["emo_driving"], kps["emotion_features"] = cat(keep["emo"]), torch.cat(keep["emo_feat"])
+    return frames, span, kps
 
 
 _IN_HEADER = 8   # T, feature channels, emotion points E (0: none), image channels, H, W, features given as [1,T,C], reserved

@@ -125,6 +125,57 @@ def kp_state_dict_spec(cfg):
     return spec
 
 
+def emotion_state_dict_spec(cfg):
+    """Checkpoint layout of Emotion_k (reference util.py:1223-1318), in its registration order: the `predictor` hourglass, the
+    anti-alias buffer, the bias-free 3x3 stem + BatchNorm, layer1..layer4 of BasicBlocks (util.py:1069-1082; a 1x1 `downsample`
+    + BatchNorm where the width or the stride changes), then the linear / Conv1d heads -- `fc`, `fc_n`, `final_4`, `final_10`
+    included, which forward does not use (223 entries for the demo's arguments)."""
+    spec = []
+    enc, dec, out_filters = hourglass_channels(cfg["block_expansion"], cfg["num_channels"], cfg["num_blocks"], cfg["max_features"])
+    for i, (ci, co) in enumerate(enc):
+        _block(f"predictor.encoder.down_blocks.{i}", ci, co, 3, spec, 2.0)
+    for i, (ci, co) in enumerate(dec):
+        _block(f"predictor.decoder.up_blocks.{i}", ci, co, 3, spec, 2.0)
+    if cfg.get("scale_factor", 1) != 1:
+        spec.append(("down.weight", (cfg["num_channels"], 1, 13, 13), "aa", None))
+    spec.append(("conv1.weight", (64, out_filters, 3, 3), "conv_w", 2.0))
+    _norm("bn1", 64, spec)
+    cin = 64
+    for li, planes in enumerate((64, 128, 256, 512)):
+        for bi in range(2):
+            p = f"layer{li + 1}.{bi}"
+            ci = cin if bi == 0 else planes
+            spec.append((p + ".conv1.weight", (planes, ci, 3, 3), "conv_w", 2.0))
+            _norm(p + ".bn1", planes, spec)
+            spec.append((p + ".conv2.weight", (planes, planes, 3, 3), "conv_w", 1.0))
+            _norm(p + ".bn2", planes, spec)
+            if bi == 0 and li > 0:
+                spec.append((p + ".downsample.0.weight", (planes, ci, 1, 1), "conv_w", 1.0))
+                _norm(p + ".downsample.1", planes, spec)
+        cin = planes
+
+    def lin(name, shape, gain=2.0):
+        spec.append((name + ".weight", shape, "fc_w", gain))
+        spec.append((name + ".bias", (shape[0],), "conv_b", None))
+    lin("fc", (cfg.get("num_classes", 8), 512), 1.0)
+    lin("fc_p.0", (1024, 1260))
+    lin("fc_p.2", (512, 1024))
+    lin("fc_n.0", (128, 60))
+    lin("fc_n.2", (512, 128))
+    lin("fc_all.0", (512, 1024))
+    lin("fc_all.2", (256, 512))
+    lin("fc_all.4", (64, 256))
+    lin("final.0", (2, 1, 4))
+    lin("final.3", (4, 2, 4))
+    lin("final.5", (4, 4, 3), 1.0)
+    lin("final_4.0", (4, 4, 3))
+    lin("final_4.3", (4, 4, 3), 1.0)
+    lin("final_10.0", (8, 4, 3))
+    lin("final_10.3", (10, 8, 3), 1.0)
+    lin("classify.last_fc", (8, 512), 1.0)
+    return spec
+
+
 DECONV_CHANNELS = (256, 256, 128, 128, 128, 35)   # AT_net2.decon, reference util.py:559-574
 
 
@@ -167,6 +218,9 @@ def synthetic_state_dict(cfg, seed: int = 1234, spec=None) -> "OrderedDict[str, 
     for key, shape, kind, gain in (state_dict_spec(cfg) if spec is None else spec):
         if kind == "conv_w":
             fan_in = shape[1] * shape[2] * shape[3]
+            v = rs.standard_normal(shape) * math.sqrt(gain / fan_in)
+        elif kind == "fc_w":        # nn.Linear [O,K] / nn.Conv1d [O,C,k]
+            fan_in = int(np.prod(shape[1:]))
             v = rs.standard_normal(shape) * math.sqrt(gain / fan_in)
         elif kind == "convT_w":
             fan_in = shape[0] * shape[2] * shape[3] / 4.0

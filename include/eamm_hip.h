@@ -1,6 +1,7 @@
 /*
  * eamm_hip.h -- C ABI of libeamm_hip.so: the MI355X (gfx950) implementation of EAMM's
- * dense-motion + OcclusionAwareGenerator forward path.
+ * dense-motion + OcclusionAwareGenerator forward path, the key-point detectors, the audio
+ * deconvolution tail and the emotion detector Emotion_k that feed it.
  *
  * The reference has no FFI layer for this path: its boundary is the Python nn.Module
  * `OcclusionAwareGenerator` (reference modules/generator.py:8-97).  The entry points below are what
@@ -29,7 +30,7 @@
 extern "C" {
 #endif
 
-#define EAMM_ABI_VERSION 5
+#define EAMM_ABI_VERSION 6
 
 typedef enum eamm_status {
     EAMM_OK = 0,
@@ -231,6 +232,44 @@ int eamm_kp_detect_features(eamm_kp_ctx* ctx, const float* feature_map, int B, c
  * eamm_deconv_forward_split; same outputs as eamm_kp_detect_features on the equivalent NCHW map, bit for bit. */
 int eamm_kp_split_channels(const eamm_kp_ctx* ctx);
 int eamm_kp_detect_features_split(eamm_kp_ctx* ctx, const float* wide, const float* thin, int B, const eamm_kp_outputs* out, void* stream);
+
+/*
+ * ---- emotion detector Emotion_k (reference modules/util.py:1223-1527, demo.py:68-70, --type linear_3) ------------------
+ * eamm_emo_detect runs Emotion_k.forward (util.py:1498-1527) and Emotion_k.feature (:1477-1496) in eval mode in ONE pass
+ * (demo.py:221-228 calls both per frame; the trunk is computed once here): anti-alias down-sampling + the `predictor` hourglass
+ * (the key-point detector's, hourglass_common.h), the 3x3 stem + BatchNorm + ReLU + MaxPool2d(3,2,1), the ResNet-18 trunk
+ * (layer1..layer4 of BasicBlocks; stride-2 3x3 and 1x1 convolutions in conv_s2.hip), AdaptiveAvgPool2d(1), and the head:
+ * classify.last_fc, the positional embedding get_embedder(10) of (value, jacobian) (accurate sinf / cosf), fc_p, fc_all and
+ * the Conv1d `final` stack.  Every BatchNorm folds at finalize.  `fc`, `fc_n`, `final_4`, `final_10` are accepted by
+ * eamm_emo_load_tensor and ignored (unused by forward).  The head hard-codes 10 input key points (fc_p: 10 x 126 inputs).
+ */
+typedef struct eamm_emo_ctx eamm_emo_ctx;
+typedef struct eamm_emo_config {
+    int32_t block_expansion;        /* 32                                                           */
+    int32_t num_channels;           /* 3 (1 .. 8 accepted)                                          */
+    int32_t max_features;           /* 1024                                                         */
+    int32_t num_blocks;             /* 5                                                            */
+    int32_t inv_scale;              /* 1 / scale_factor (1, 2, 4); the demo's 0.25 -> 4             */
+    int32_t num_classes;            /* outputs of classify.last_fc (8 in the reference)             */
+    int32_t height, width;          /* image size                                                   */
+    int32_t max_batch;
+} eamm_emo_config;
+
+typedef struct eamm_emo_outputs {   /* caller-owned device buffers; NULL pointers are skipped        */
+    float* value;                   /* [B,4,2]            kp['value']                               */
+    float* jacobian;                /* [B,4,2,2]          kp['jacobian']                            */
+    float* fake;                    /* [B,num_classes]    classify(out)                             */
+    float* feature;                 /* [B,512]            Emotion_k.feature(x): the pooled trunk    */
+} eamm_emo_outputs;
+
+int eamm_emo_create(const eamm_emo_config* cfg, int device, eamm_emo_ctx** out);
+void eamm_emo_destroy(eamm_emo_ctx* ctx);
+const char* eamm_emo_last_error(const eamm_emo_ctx* ctx);
+int eamm_emo_load_tensor(eamm_emo_ctx* ctx, const char* key, const float* host_data, const int64_t* shape, int ndim);
+int eamm_emo_finalize_weights(eamm_emo_ctx* ctx);
+/* image [B,C,H,W], kp_value [B,10,2], kp_jacobian [B,10,2,2] (both may be NULL when only `feature` / `fake` are asked for) */
+int eamm_emo_detect(eamm_emo_ctx* ctx, const float* image, const float* kp_value, const float* kp_jacobian, int B,
+                    const eamm_emo_outputs* out, void* stream);
 
 /*
  * ---- N3: audio-to-feature deconvolution tail ------------------------------------------------------------
