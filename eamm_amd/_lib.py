@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libeamm_hip.so")
 
-ABI_VERSION = 6   # the emotion detector Emotion_k (eamm_emo_*)
+ABI_VERSION = 6   # the emotion detector Emotion_k (eamm_emo_*); the audio network AT_net2 (eamm_audio_*) added symbols only
 
 EAMM_OK = 0
 ERR_ARG, ERR_STATE, ERR_KEY, ERR_HIP, ERR_NUMERIC = -1, -2, -3, -4, -5
@@ -65,6 +65,10 @@ class EammEmoConfig(C.Structure):
     ]
 
 
+class EammAudioConfig(C.Structure):
+    _fields_ = [("max_batch", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
 class EammEmoOutputs(C.Structure):
     _fields_ = [("value", C.c_void_p), ("jacobian", C.c_void_p), ("fake", C.c_void_p), ("feature", C.c_void_p)]
 
@@ -111,6 +115,14 @@ SIGNATURES = {
     "eamm_emo_last_error": (C.c_char_p, [C.c_void_p]),
     "eamm_emo_load_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
     "eamm_emo_finalize_weights": (C.c_int, [C.c_void_p]),
+    "eamm_audio_create": (C.c_int, [C.POINTER(EammAudioConfig), C.c_int, C.POINTER(C.c_void_p)]),
+    "eamm_audio_destroy": (None, [C.c_void_p]),
+    "eamm_audio_last_error": (C.c_char_p, [C.c_void_p]),
+    "eamm_audio_load_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
+    "eamm_audio_finalize_weights": (C.c_int, [C.c_void_p]),
+    "eamm_audio_lstm_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "eamm_audio_check": (C.c_int, [C.c_void_p, C.c_void_p]),
     "eamm_emo_detect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(EammEmoOutputs), C.c_void_p]),
     "eamm_deconv_create": (C.c_int, [C.POINTER(EammDeconvConfig), C.c_int, C.POINTER(C.c_void_p)]),
     "eamm_deconv_destroy": (None, [C.c_void_p]),
@@ -223,8 +235,8 @@ def lib() -> C.CDLL:
     return _lib
 
 
-def check(code: int, ctx=None, kp: bool = False, deconv: bool = False, emo: bool = False):
+def check(code: int, ctx=None, kp: bool = False, deconv: bool = False, emo: bool = False, audio: bool = False):
     if code != EAMM_OK:
-        msg = (lib().eamm_emo_last_error if emo else lib().eamm_deconv_last_error if deconv else lib().eamm_kp_last_error if kp
+        msg = (lib().eamm_audio_last_error if audio else lib().eamm_emo_last_error if emo else lib().eamm_deconv_last_error if deconv else lib().eamm_kp_last_error if kp
                else lib().eamm_last_error)(ctx)
         raise EammError(code, msg.decode() if msg else "?")

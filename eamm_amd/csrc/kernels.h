@@ -301,6 +301,31 @@ hipError_t emo_linear_launch(const float* x0, int K0, const float* x1, int K1, c
                              int B, int relu, float* out /*[B,O]*/, hipStream_t s);
 hipError_t emo_final_launch(const float* a /*[B,64]*/, const float* w /*98 floats*/, int B, float* value, float* jacobian, hipStream_t s);
 
+// Audio network AT_net2 (audio.hip): the first audio convolution 1 -> 64 (BatchNorm folded: w [9][64], b [64]) + ReLU from the raw
+// [F,H,W] MFCC windows to NHWC [F,H,W,64]; MaxPool2d(3, (sy, sx)) without padding on NHWC (C % 4 == 0); x *= scale.
+hipError_t audio_conv1_launch(const float* x, const float* w, const float* b, int F, int H, int W, float* out, hipStream_t s);
+hipError_t audio_maxpool_launch(const float* in, int F, int H, int W, int C, int sy, int sx, float* out, hipStream_t s);
+hipError_t audio_scale_launch(float* x, size_t n, float scale, hipStream_t s);
+// One LSTM layer (hidden 256, gates i f g o) over S steps for N <= 8 clips in one persistent launch of LSTM_WG workgroups.
+constexpr int LSTM_WG = 16;
+struct LstmArgs {
+    const float* whh;            // lstm_pack_whh_host image [16][256][64]
+    const float* xproj;          // [N*S][1024] input projection of step s of clip n at row n*S + s, biases included
+    const float* clipb;          // [N][1024] added to every step of clip n, or null
+    int N, S;
+    const float* h0;             // [N][256] h before the first step
+    float* hT;                   // [N][256] h after the last step (must not overlap h0)
+    float* c;                    // [N][256] cell state: read first, overwritten with the state after the last step
+    float* y;                    // h of step s of clip n at y[n * ystride + s * 256]
+    long long ystride;
+    unsigned long long* gran;    // [2][8][256] tagged hand-off words
+    unsigned epoch0;             // tag of the first step (step s: epoch0 + s); tags must never repeat on one gran buffer
+    unsigned long long limit;    // wall-clock ticks one wait may take before the error word is set
+    int* err;                    // host-visible error word
+};
+void lstm_pack_whh_host(const float* whh /*[1024][256]*/, float* dst /*[16][256][64]*/);
+hipError_t lstm_rec_launch(const LstmArgs& a, hipStream_t s);
+
 hipError_t one_euro_launch(const float* x, int T, int E, float mincutoff, float beta, float dcutoff, float freq, float scale,
                            float* out, hipStream_t stream, float* state = nullptr, int resume = 0);
 

@@ -18,9 +18,13 @@ LSTM features in, the clip's frames in host memory out -- every step of the refe
     for t: emo_detector(transformed_frame, raw kp)         demo.py:221-228 EmotionDetector.detect, `front_batch` frames per call
                                                                               (``emo_detector`` + ``emotion_frames``)
 
-The audio LSTM is outside this path ("stays in PyTorch-ROCm"): its output is an input here --
-``lstm_features`` [T,256].  The emotion displacements are either computed here (``emo_detector`` + ``emotion_frames``, the
-reference's ``transformed_video``) or passed in precomputed (``emo_driving``).
+    audio_feature(example_image, input_mfcc, pose)         demo.py:497     AudioFeatureNet.lstm_features (``audio_feature`` + ``audio`` +
+                                                                              ``pose``): one call, or ``front_batch`` steps per call
+                                                                              with the LSTM state carried when streamed
+
+The audio network's LSTM output ``lstm_features`` [T,256] is either computed here (``audio_feature`` + ``audio`` + ``pose``, the
+reference's ``input_mfcc`` windows and head pose) or passed in precomputed.  The emotion displacements are either computed
+here (``emo_detector`` + ``emotion_frames``, the reference's ``transformed_video``) or passed in precomputed (``emo_driving``).
 Under torch.distributed BOTH loops shard by frames: rank 0's inputs are broadcast (header + one payload), every rank runs the
 detectors on its frames, one all-gather gives every rank the whole key-point sequence (the One-Euro recurrence needs it; 0.7 ms,
 computed redundantly), and every rank animates its shard from its own encoding of the source -- three collectives per clip.
@@ -52,7 +56,8 @@ def animate_from_features(generator, kp_detector, deconv_tail, kp_detector_a, so
                           front_batch: int = 256, uint8: bool = True, to_host: bool = True, group=None,
                           backend: Optional[EngineBackend] = None, timings: Optional[Dict[str, float]] = None,
                           return_keypoints: bool = False, size: Optional[Tuple[int, int]] = None, stream: Optional[bool] = None,
-                          emo_detector=None, emotion_frames: Optional[torch.Tensor] = None):
+                          emo_detector=None, emotion_frames: Optional[torch.Tensor] = None, audio_feature=None,
+                          audio: Optional[torch.Tensor] = None, pose: Optional[torch.Tensor] = None, audio_weight: float = 1.6):
     """make_animation_smooth (demo.py:194-282) for one clip.
 
     ``source_image``: [1,C,H,W] float in [0,1]; ``lstm_features``: [T,256] (or [1,T,256]), the audio network's LSTM output;
@@ -68,7 +73,13 @@ def animate_from_features(generator, kp_detector, deconv_tail, kp_detector_a, so
     ``emo_detector`` (an ``EmotionDetector``) with ``emotion_frames`` [T,C,H,W] float in [0,1] (the reference's
     ``transformed_video``, demo.py:221-228): ``emo_driving`` is computed on the device from the RAW (un-smoothed) driving key
     points, ``front_batch`` frames per call, then smoothed and applied like a given one.  With ``return_keypoints`` the dict also
-    holds ``emo_driving`` (raw) and ``emotion_features`` [T,512] (``emo_detector.feature``)."""
+    holds ``emo_driving`` (raw) and ``emotion_features`` [T,512] (``emo_detector.feature``).
+
+    ``audio_feature`` (an ``AudioFeatureNet``) with ``audio`` [T,28,12] (or [1,T,28,12]; the reference's ``input_mfcc``) and
+    ``pose`` [T,6] (or [1,T,6]) instead of ``lstm_features``: the features are computed on the device from ``source_image``,
+    ``audio`` and ``pose`` with weight ``audio_weight`` (demo.py:497 passes the same source image and 1.6) -- one call, or when
+    streamed ``front_batch`` steps per call with the LSTM state carried (bit-identical).  Under a process group rank 0 computes
+    them and the other ranks pass None.  With ``return_keypoints`` the dict also holds ``lstm_features`` [T,256]."""
     dev = backend.device if backend is not None else next(generator.parameters()).device
     on_gpu = torch.device(dev).type == "cuda"
     distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
@@ -93,8 +104,26 @@ def animate_from_features(generator, kp_detector, deconv_tail, kp_detector_a, so
         if distributed:
             raise ValueError("animate_from_features: emotion_frames with a process group of more than one rank is not supported "
                              "(the emotion frames are not sharded across ranks); compute emo_driving first and pass that instead")
+    from_audio = any(x is not None for x in (audio_feature, audio, pose))
+    if from_audio:
+        if lstm_features is not None:
+            raise ValueError("animate_from_features: pass either lstm_features or audio_feature + audio + pose, not both")
+        if audio_feature is None or audio is None or pose is None:
+            raise ValueError("animate_from_features: audio_feature, audio and pose go together")
+        audio = audio[0] if audio.dim() == 4 and audio.shape[0] == 1 else audio
+        pose = pose[0] if pose.dim() == 3 and pose.shape[0] == 1 else pose
+        if audio.dim() != 3 or pose.dim() != 2 or pose.shape[0] != audio.shape[0]:
+            raise ValueError(f"animate_from_features: audio must be [T,28,12] and pose [T,6] for one clip, got "
+                             f"{tuple(audio.shape)} / {tuple(pose.shape)}")
     if backend is None:
         backend = EngineBackend(generator, batch=batch)
+    streamed = (stream if stream is not None else (on_gpu and not distributed and timings is None)) and on_gpu and not distributed
+    audio_src = None
+    if from_audio:
+        audio_src = _AudioSource(audio_feature, source_image.to(dev), audio, pose, audio_weight, dev)
+        if not streamed:                                                                     # demo.py:497
+            lstm_features = audio_src.chunk(0, audio_src.T)
+            audio_src = None
     if distributed:
         # every rank gets the clip's INPUTS (source image, LSTM features, emotion displacements: 2.9 MB for 2048 frames at
         # 256x256) in two broadcasts -- fixed header + one payload -- and runs the front end on ITS frames; one all-gather of the
@@ -103,19 +132,20 @@ def animate_from_features(generator, kp_detector, deconv_tail, kp_detector_a, so
         source_image, lstm_features, emo_driving = _broadcast_inputs(source_image, lstm_features, emo_driving, dev, group)
         mark("broadcast_ms")
     src = source_image.to(dev)
-    if lstm_features.dim() == 3 and lstm_features.shape[0] == 1:
+    if audio_src is None and lstm_features.dim() == 3 and lstm_features.shape[0] == 1:
         lstm_features = lstm_features[0]
-    T = lstm_features.shape[0]
+    T = audio_src.T if audio_src is not None else lstm_features.shape[0]
     if T < 1:
         raise ValueError("animate_from_features: the clip has no frames (lstm_features is empty)")
     kp_source = _kp_only(kp_detector(src))                                                   # demo.py:206
     H, W = (int(src.shape[-2]), int(src.shape[-1])) if size is None else size
-    if stream is None:
-        stream = on_gpu and not distributed and timings is None
-    if stream and on_gpu and not distributed:
-        return _animate_streaming(backend, kp_detector_a, deconv_tail, src, lstm_features.to(dev), kp_source, emo_driving, relative,
-                                  adapt_movement_scale, smooth, front_batch, uint8, to_host, return_keypoints, H, W, dev,
-                                  emo_detector, emotion_frames)
+    if streamed:
+        res = _animate_streaming(backend, kp_detector_a, deconv_tail, src, None if audio_src else lstm_features.to(dev), kp_source,
+                                 emo_driving, relative, adapt_movement_scale, smooth, front_batch, uint8, to_host, return_keypoints,
+                                 H, W, dev, emo_detector, emotion_frames, audio_src)
+        if audio_feature is not None:
+            audio_feature.check()          # a recurrence that timed out raises here instead of leaving wrong frames
+        return res
     a, b = shard_bounds(T, world, rank)
     raw = driving_keypoints(deconv_tail, kp_detector_a, lstm_features[a:b].to(dev), batch=front_batch) if b > a else None   # demo.py:212-219
     if distributed:
@@ -137,9 +167,31 @@ def animate_from_features(generator, kp_detector, deconv_tail, kp_detector_a, so
     kps = {"kp_source": kp_source, "kp_driving_raw": raw, "kp_driving_smoothed": kp_d, "kp_norm": kp_norm} if return_keypoints else {}
     if return_keypoints and emo_feats is not None:
         kps["emo_driving"], kps["emotion_features"] = emo_driving, emo_feats
+    if return_keypoints and from_audio:
+        kps["lstm_features"] = lstm_features
     frames, span = animate_clip(backend, src, kp_source, kp_norm, H, W, uint8=uint8, group=group, to_host=to_host,
                                 timings=timings, replicated=distributed)
+    if audio_feature is not None:
+        audio_feature.check()              # a recurrence that timed out raises here instead of leaving wrong frames
     return (frames, span, kps) if return_keypoints else (frames, span)
+
+
+class _AudioSource:
+    """The clip's LSTM features from its audio: ``chunk(t0, t1)`` for consecutive spans, the recurrence's state carried between
+    calls (so any split into spans gives the features of one whole-clip call, bit for bit)."""
+
+    def __init__(self, net, src, audio, pose, weight, dev):
+        self.net, self.src, self.weight = net, src, float(weight)
+        self.audio, self.pose = audio.to(dev)[None], pose.to(dev)[None]
+        self.T = int(audio.shape[0])
+        self.state: Dict[str, torch.Tensor] = {}
+        self.t = 0
+
+    def chunk(self, t0, t1):
+        if t0 != self.t:
+            raise RuntimeError(f"_AudioSource: spans must be consecutive (expected {self.t}, got {t0})")
+        self.t = t1
+        return self.net.lstm_features(self.src, self.audio[:, t0:t1], self.pose[:, t0:t1], self.weight, state=self.state)[0]
 
 
 def _emotion_chunk(emo_detector, emotion_frames, raw, t0, t1, dev):
@@ -158,7 +210,7 @@ def _emotion_driving(emo_detector, emotion_frames, raw, t0, t1, front_batch, dev
 
 
 def _animate_streaming(backend, kp_detector_a, deconv_tail, src, feats, kp_source, emo_driving, relative, adapt_movement_scale, smooth,
-                       front_batch, uint8, to_host, return_keypoints, H, W, dev, emo_detector=None, emotion_frames=None):
+                       front_batch, uint8, to_host, return_keypoints, H, W, dev, emo_detector=None, emotion_frames=None, audio_src=None):
     """One GPU, one process: the reference's FIRST loop (key points of every frame, demo.py:212-250) runs on its own stream,
     `front_batch` frames at a time, and the generator starts on the first frames as soon as their key points are complete --
     every step between the detector and the generator is causal (the One-Euro filter carries its memory from chunk to chunk:
@@ -166,20 +218,23 @@ def _animate_streaming(backend, kp_detector_a, deconv_tail, src, feats, kp_sourc
     frames t >= front_batch is hidden behind the generator of the frames before.  Bit-identical to the un-streamed path: the same
     kernels on the same batches, the filter resumed instead of run whole."""
     from .keypoints import movement_scale
-    T, K = feats.shape[0], kp_source["value"].shape[1]
+    T, K = (audio_src.T if audio_src is not None else feats.shape[0]), kp_source["value"].shape[1]
     main = torch.cuda.current_stream(dev)
     front = getattr(backend, "_front_stream", None)
     if front is None:      # (small launches: a high-priority stream lets them in ahead of the generator's)
         front = backend._front_stream = torch.cuda.Stream(device=dev, priority=-1)
     norm = {"value": torch.empty(T, K, 2, device=dev), "jacobian": torch.empty(T, K, 2, 2, device=dev)}
-    keep = {"raw": [], "smoothed": [], "emo": [], "emo_feat": []} if return_keypoints else None
+    keep = {"raw": [], "smoothed": [], "emo": [], "emo_feat": [], "feats": []} if return_keypoints else None
     emo = None if emo_driving is None else {k: v.to(dev) for k, v in _kp_only(emo_driving).items()}
     front.wait_stream(main)                        # the source's key points and the features are complete
     events, kp_state, emo_state, kp_initial, scale = [], {}, {}, None, None
     with torch.cuda.stream(front):
         for t0 in range(0, T, front_batch):
             t1 = min(T, t0 + front_batch)
-            raw = driving_keypoints(deconv_tail, kp_detector_a, feats[t0:t1], batch=front_batch)          # demo.py:212-219
+            f_c = audio_src.chunk(t0, t1) if audio_src is not None else feats[t0:t1]                          # demo.py:497
+            if keep is not None and audio_src is not None:
+                keep["feats"].append(f_c)
+            raw = driving_keypoints(deconv_tail, kp_detector_a, f_c, batch=front_batch)                       # demo.py:212-219
             if t0 == 0:
                 kp_initial = {k: v[:1].clone() for k, v in raw.items()}                                       # demo.py:207
                 if adapt_movement_scale:
@@ -219,6 +274,8 @@ def _animate_streaming(backend, kp_detector_a, deconv_tail, src, feats, kp_sourc
     kps = {"kp_source": kp_source, "kp_driving_raw": cat(keep["raw"]), "kp_driving_smoothed": cat(keep["smoothed"]), "kp_norm": norm}
     if keep["emo"]:
         kps["emo_driving"], kps["emotion_features"] = cat(keep["emo"]), torch.cat(keep["emo_feat"])
+    if keep["feats"]:
+        kps["lstm_features"] = torch.cat(keep["feats"])
     return frames, span, kps
 
 

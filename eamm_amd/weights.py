@@ -239,6 +239,14 @@ def synthetic_state_dict(cfg, seed: int = 1234, spec=None) -> "OrderedDict[str, 
         elif kind == "aa":
             sd[key] = antialias_kernel(shape[0])
             continue
+        elif kind == "lstm":       # U(-1/4, 1/4): 4x nn.LSTM's default bound 1/sqrt(256), whose three stacked layers shrink
+            v = rs.uniform(-0.25, 0.25, shape)   # lstm_out to std 0.04; here std ~0.25 and no |h| > 0.99 (the fixtures record both)
+        elif kind == "style_w":    # StyleGAN2 entries (unused by the 'cnn' branch): any finite values
+            v = rs.standard_normal(shape)
+        elif kind == "zero":
+            v = np.zeros(shape)
+        elif kind == "buf":
+            v = np.full(shape, 1.0 / np.prod(shape))
         else:  # pragma: no cover
             raise ValueError(kind)
         sd[key] = torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32))
@@ -352,3 +360,94 @@ def synthetic_keypoints(n: int, num_kp: int = 10, seed: int = 0, jacobian: bool 
     if jacobian:
         kp["jacobian"] = torch.from_numpy(np.stack(jacs).astype(np.float32))
     return kp
+
+
+def _stylegan2_spec(prefix, size=64, style_dim=256, n_mlp=8, out_channels=35):
+    """Key layout of the StyleGAN2 `Generator(64, 256, 8)` that AT_net2 holds as `generator` (its jaco_net='gan' branch, unused
+    by the demo's 'cnn' configuration): names, shapes and which entries are buffers ("buf": the blur / up-sampling kernels and
+    the fixed noises).  Held only so that a strict load of the reference's checkpoint works."""
+    spec = []
+
+    def lin(name, o, i):
+        spec.append((f"{prefix}.{name}.weight", (o, i), "fc_w", 1.0))
+        spec.append((f"{prefix}.{name}.bias", (o,), "conv_b", None))
+
+    def styled(name, cin, cout, k, up=False, noise=True):
+        spec.append((f"{prefix}.{name}.conv.weight", (1, cout, cin, k, k), "style_w", None))
+        if up:
+            spec.append((f"{prefix}.{name}.conv.blur.kernel", (4, 4), "buf", None))
+        lin(f"{name}.conv.modulation", cin, style_dim)
+        if noise:
+            spec.append((f"{prefix}.{name}.noise.weight", (1,), "zero", None))
+            spec.append((f"{prefix}.{name}.activate.bias", (1, cout, 1, 1), "zero", None))
+
+    def to_rgb(name, cin, up):
+        spec.append((f"{prefix}.{name}.bias", (1, out_channels, 1, 1), "zero", None))
+        if up:
+            spec.append((f"{prefix}.{name}.upsample.kernel", (4, 4), "buf", None))
+        styled(name, cin, out_channels, 1, noise=False)
+
+    for i in range(1, n_mlp + 1):
+        lin(f"style.{i}", style_dim, style_dim)
+    ch = {4: 256, 8: 256, 16: 128, 32: 64, 64: 32}
+    spec.append((f"{prefix}.input.input", (1, ch[4], 4, 4), "style_w", None))
+    styled("conv1", ch[4], ch[4], 3)
+    to_rgb("to_rgb1", ch[4], False)
+    log_size = int(math.log2(size))
+    cin, j = ch[4], 0
+    for i in range(3, log_size + 1):
+        cout = ch[2 ** i]
+        styled(f"convs.{j}", cin, cout, 3, up=True)
+        styled(f"convs.{j + 1}", cout, cout, 3)
+        j += 2
+        cin = cout
+    for i in range(3, log_size + 1):
+        to_rgb(f"to_rgbs.{i - 3}", ch[2 ** i], True)
+    for k in range((log_size - 2) * 2 + 1):
+        side = 2 ** ((k + 5) // 2)
+        spec.append((f"{prefix}.noises.noise_{k}", (1, 1, side, side), "buf", None))
+    return spec
+
+
+AUDIO_DOWN_CHANNELS = (3, 4, 8, 16, 32, 64, 128, 256, 512)   # AT_net2.down_blocks, reference util.py:518-523
+
+
+def audio_feature_state_dict_spec():
+    """Checkpoint layout of AT_net2 (reference util.py:514-582), in its registration order: the image encoder's eight DownBlock2d,
+    `pose_encoder`, `audio_eocder` (conv2d = bias-free conv + BatchNorm + ReLU, at Sequential indices 0, 1, 3, 4, 5),
+    `audio_eocder_fc`, the three-layer `lstm`, `decon` and the unused StyleGAN2 `generator` -- 235 entries.  The LSTM draws
+    U(+-1/4) ("lstm"), which keeps its gates away from both saturation and zero."""
+    spec = []
+    for i in range(8):
+        _block(f"down_blocks.{i}", AUDIO_DOWN_CHANNELS[i], AUDIO_DOWN_CHANNELS[i + 1], 3, spec, 2.0)
+
+    def lin(name, o, i, gain=2.0):
+        spec.append((name + ".weight", (o, i), "fc_w", gain))
+        spec.append((name + ".bias", (o,), "conv_b", None))
+    lin("pose_encoder.0", 128, 6)
+    lin("pose_encoder.2", 256, 128)
+    for idx, (ci, co) in zip((0, 1, 3, 4, 5), ((1, 64), (64, 128), (128, 256), (256, 256), (256, 512))):
+        spec.append((f"audio_eocder.{idx}.0.weight", (co, ci, 3, 3), "conv_w", 2.0))
+        _norm(f"audio_eocder.{idx}.1", co, spec)
+    lin("audio_eocder_fc.0", 2048, 12288)
+    lin("audio_eocder_fc.2", 256, 2048)
+    for layer in range(3):
+        spec.append((f"lstm.weight_ih_l{layer}", (1024, 1024 if layer == 0 else 256), "lstm", None))
+        spec.append((f"lstm.weight_hh_l{layer}", (1024, 256), "lstm", None))
+        spec.append((f"lstm.bias_ih_l{layer}", (1024,), "lstm", None))
+        spec.append((f"lstm.bias_hh_l{layer}", (1024,), "lstm", None))
+    spec += [("decon." + k, s, kind, g) for k, s, kind, g in deconv_state_dict_spec()]
+    spec += _stylegan2_spec("generator")
+    return spec
+
+
+def synthetic_audio_inputs(clips: int, steps: int, seed: int = 21, size: int = 256):
+    """AT_net2.forward's inputs for `clips` clips of `steps` steps: example_image [N,3,size,size] uniform [0,1), audio [N,T,28,12]
+    (MFCC windows, demo.py:326-332: coefficients 1..12 of 28 rows; N(0, 4^2) like real MFCCs' spread) and pose [N,T,6]
+    (demo.py:297; small rotations and translations, U(-0.3, 0.3))."""
+    rs = np.random.RandomState(seed)
+    image = rs.uniform(0.0, 1.0, (clips, 3, size, size))
+    audio = 4.0 * rs.standard_normal((clips, steps, 28, 12))
+    pose = rs.uniform(-0.3, 0.3, (clips, steps, 6))
+    f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
+    return f32(image), f32(audio), f32(pose)

@@ -272,6 +272,39 @@ int eamm_emo_detect(eamm_emo_ctx* ctx, const float* image, const float* kp_value
                     const eamm_emo_outputs* out, void* stream);
 
 /*
+ * ---- audio network AT_net2 up to its LSTM (reference modules/util.py:514-600; demo.py:286-354 test_auido) ------------------
+ * eamm_audio_lstm_features computes AT_net2's lstm_out [N,T,256] in eval mode: the image encoder (eight DownBlock2d: conv 3x3 +
+ * BatchNorm + ReLU + AvgPool2d(2), 3 -> 512 channels, 256x256 -> 1x1) once per clip; the audio encoder (conv2d blocks with
+ * BatchNorm folded, two MaxPool2d(3)), audio_eocder_fc * weight and pose_encoder over every step; then the three-layer
+ * nn.LSTM(1024, 256) from the zero state or a given one.  Steps run max_batch / N at a time (encoders, input projections, then
+ * the recurrence of each layer as one persistent launch); results do not depend on how a clip is split into calls: a clip
+ * computed in chunks with the state carried (h_out / c_out of one call as h0 / c0 of the next) is bit-identical to one call.
+ * State-dict keys: the reference's 235 except decon.* (DeconvTail's handle) and generator.* (unused StyleGAN2 branch).  Calls on
+ * one handle must be issued to one stream at a time.  A recurrence that cannot complete (a workgroup waiting longer than the
+ * wall-clock limit for another) sets a sticky error word: eamm_audio_check (after synchronising `stream`, when given) and every
+ * later call on the handle then fail with EAMM_ERR_HIP.
+ */
+typedef struct eamm_audio_ctx eamm_audio_ctx;
+typedef struct eamm_audio_config {
+    int32_t max_batch;              /* steps x clips per encoder pass (8 .. 4096)                      */
+    int32_t reserved[3];
+} eamm_audio_config;
+
+int eamm_audio_create(const eamm_audio_config* cfg, int device, eamm_audio_ctx** out);
+void eamm_audio_destroy(eamm_audio_ctx* ctx);
+const char* eamm_audio_last_error(const eamm_audio_ctx* ctx);
+int eamm_audio_load_tensor(eamm_audio_ctx* ctx, const char* key, const float* host_data, const int64_t* shape, int ndim);
+int eamm_audio_finalize_weights(eamm_audio_ctx* ctx);
+/* image [N,3,256,256], audio [N,T,28,12], pose [N,T,6], out [N,T,256]: device fp32, 1 <= N <= 8, T >= 1.  h0 / c0: [3,N,256]
+ * (layer-major, as nn.LSTM's hidden tuple) or NULL for zeros; h_out / c_out: [3,N,256] or NULL (may be h0 / c0 themselves).
+ * clip_bias: NULL or [N,1024], the image's share of the layer-0 gates (W_ih_l0[:, :512] image_feature + both layer-0 biases):
+ * written when `image` is given; with image NULL it is read instead, so the later chunks of a clip skip the image encoder. */
+int eamm_audio_lstm_features(eamm_audio_ctx* ctx, const float* image, const float* audio, const float* pose, int N, int T, float weight,
+                             const float* h0, const float* c0, float* h_out, float* c_out, float* clip_bias, float* out, void* stream);
+/* EAMM_OK, or EAMM_ERR_HIP once a recurrence has timed out; stream non-NULL: synchronised first, so the calls issued to it are covered */
+int eamm_audio_check(eamm_audio_ctx* ctx, void* stream);
+
+/*
  * ---- N3: audio-to-feature deconvolution tail ------------------------------------------------------------
  * Replaces the nn.Sequential `AT_net2.decon` (reference modules/util.py:559-576), which the reference evaluates
  * once per frame on the LSTM output (util.py:604-607) to produce the [35,64,64] maps KPDetector_a consumes
