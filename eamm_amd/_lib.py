@@ -11,7 +11,8 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libeamm_hip.so")
 
-ABI_VERSION = 6   # the emotion detector Emotion_k (eamm_emo_*); the audio network AT_net2 (eamm_audio_*) added symbols only
+ABI_VERSION = 6   # the emotion detector Emotion_k (eamm_emo_*); the audio network AT_net2 (eamm_audio_*) and the MFCC front end
+                  # (eamm_op_mfcc*) added symbols only
 
 EAMM_OK = 0
 ERR_ARG, ERR_STATE, ERR_KEY, ERR_HIP, ERR_NUMERIC = -1, -2, -3, -4, -5
@@ -96,6 +97,8 @@ SIGNATURES = {
     "eamm_pass_chains": (C.c_int, [C.c_void_p, C.c_int]),
     "eamm_op_one_euro": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                   C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "eamm_op_mfcc_frames": (C.c_int64, [C.c_int64, C.c_int]),
+    "eamm_op_mfcc": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
     "eamm_last_stream_set": (C.c_int, [C.c_void_p]),
     "eamm_describe_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_int]),
     "eamm_knobs_json": (C.c_int, [C.c_char_p, C.c_int]),

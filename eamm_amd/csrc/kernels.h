@@ -329,4 +329,10 @@ hipError_t lstm_rec_launch(const LstmArgs& a, hipStream_t s);
 hipError_t one_euro_launch(const float* x, int T, int E, float mincutoff, float beta, float dcutoff, float freq, float scale,
                            float* out, hipStream_t stream, float* state = nullptr, int resume = 0);
 
+// mfcc.hip: python_speech_features.mfcc(signal, 16000, winstep=0.01) of n_clips clips [n_clips][clip_stride] of n_samples each,
+// padded virtually with `pad` zeros on each side -> out [n_clips][mfcc_frames(n_samples, pad)][13]
+long long mfcc_frames(long long n_samples, int pad);
+hipError_t mfcc_launch(const float* pcm, long long n_samples, int n_clips, long long clip_stride, int pad, float* out,
+                       hipStream_t stream);
+
 }  // namespace eamm

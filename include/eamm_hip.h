@@ -506,6 +506,18 @@ int eamm_op_conv(int device, const float* in0, int C0, const float* in1, int C1,
 int eamm_op_one_euro(int device, const float* x, int T, int E, float mincutoff, float beta, float dcutoff, float freq, float scale,
                      float* out, float* state, int resume, void* stream);
 
+/* The reference's audio front end (demo.py:314-318): python_speech_features.mfcc(signal, 16000, winstep=0.01) with the package's
+ * defaults (pre-emphasis 0.97, 400-sample frames every 160 samples, rectangular window, 512-point power spectrum, 26 mel filters
+ * over 0..8000 Hz, log, orthonormal DCT-II keeping 13, lifter 22, coefficient 0 replaced by the log frame energy) of a signal
+ * padded with `pad` zeros on each side (1920 in the demo; the zeros are not materialised).  eamm_op_mfcc_frames gives the frame
+ * count F: 1 for n_samples + 2 pad <= 400, else 1 + ceil((n_samples + 2 pad - 400) / 160); 0 for n_samples < 1 or pad < 0.
+ * pcm: device float32 [n_clips][clip_stride] (the first n_samples of each row are the clip), out: device float32
+ * [n_clips][F][13].  A frame's row depends on its own samples only, bit for bit.  EAMM_ERR_ARG (message in
+ * eamm_last_error(NULL)) for n_samples < 1, n_clips < 1 or > 65535, pad < 0 or clip_stride < n_samples with several clips.
+ * Stream-ordered, no sync. */
+int64_t eamm_op_mfcc_frames(int64_t n_samples, int pad);
+int eamm_op_mfcc(int device, const float* pcm, int64_t n_samples, int n_clips, int64_t clip_stride, int pad, float* out, void* stream);
+
 /* The HBM-bound kernel of the path on its own: out = grid_sample(feat, deformation, bilinear, zeros, align_corners=False)
  * * occlusion (reference modules/generator.py:50-57, 79-84).  feat: NHWC [ns,hf,wf,C] (ns = 1 broadcasts one source to
  * all frames, else ns = n), deformation [n,h,w,2], occlusion [n,h,w] or NULL, out NHWC [n,hf,wf,C]; when (h,w) != (hf,wf)
