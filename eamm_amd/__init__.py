@@ -13,10 +13,12 @@ from .keypoint_detector import KPDetector, KPDetector_a  # noqa: F401
 from .emotion_detector import EmotionDetector  # noqa: F401
 from .audio_feature import AudioFeatureNet  # noqa: F401
 from .audio_input import animate_from_audio, mfcc, mfcc_reference, mfcc_windows, prepare_pose, read_wav  # noqa: F401
+from .video_input import (EmotionVideo, align_video, crop_source, crop_source_reference, draw_augmentation,  # noqa: F401
+                          emotion_video_reference, perspective_params, similarity_transform)
 from .deconv_tail import DeconvTail, SplitFeatureMap  # noqa: F401
 from .sync_batchnorm import SynchronizedBatchNorm2d  # noqa: F401
 from .data_parallel import all_reduce_gradients  # noqa: F401
-from .config import kp_detector_config, kp_detector_a_config, tiny_kp_config, emotion_detector_config  # noqa: F401
+from .config import kp_detector_config, kp_detector_a_config, tiny_kp_config, emotion_detector_config, emotion_augmentation_config  # noqa: F401
 
-__all__ = ["OcclusionAwareGenerator", "Engine", "EngineBackend", "animate_clip", "animate_from_features", "animate_from_audio", "mfcc", "mfcc_reference", "mfcc_windows", "prepare_pose", "read_wav", "driving_keypoints", "shard_bounds", "normalize_kp", "apply_emotion_offsets", "smooth_keypoints", "one_euro_smooth", "KPDetector", "KPDetector_a", "EmotionDetector", "AudioFeatureNet", "DeconvTail", "SplitFeatureMap", "SynchronizedBatchNorm2d",
+__all__ = ["OcclusionAwareGenerator", "Engine", "EngineBackend", "animate_clip", "animate_from_features", "animate_from_audio", "mfcc", "mfcc_reference", "mfcc_windows", "prepare_pose", "read_wav", "EmotionVideo", "align_video", "crop_source", "crop_source_reference", "draw_augmentation", "emotion_video_reference", "perspective_params", "similarity_transform", "emotion_augmentation_config", "driving_keypoints", "shard_bounds", "normalize_kp", "apply_emotion_offsets", "smooth_keypoints", "one_euro_smooth", "KPDetector", "KPDetector_a", "EmotionDetector", "AudioFeatureNet", "DeconvTail", "SplitFeatureMap", "SynchronizedBatchNorm2d",
            "all_reduce_gradients", "hot_path_config", "tiny_config"]

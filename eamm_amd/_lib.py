@@ -12,7 +12,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libeamm_hip.so")
 
 ABI_VERSION = 6   # the emotion detector Emotion_k (eamm_emo_*); the audio network AT_net2 (eamm_audio_*) and the MFCC front end
-                  # (eamm_op_mfcc*) added symbols only
+                  # (eamm_op_mfcc*) and the emotion video's preprocessing (eamm_op_resize_aa, eamm_op_similarity_warp,
+                  # eamm_op_emotion_augment) added symbols only
 
 EAMM_OK = 0
 ERR_ARG, ERR_STATE, ERR_KEY, ERR_HIP, ERR_NUMERIC = -1, -2, -3, -4, -5
@@ -99,6 +100,12 @@ SIGNATURES = {
                                   C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "eamm_op_mfcc_frames": (C.c_int64, [C.c_int64, C.c_int]),
     "eamm_op_mfcc": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
+    "eamm_op_resize_aa": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int,
+                                    C.POINTER(C.c_double), C.c_int, C.c_void_p, C.c_void_p]),
+    "eamm_op_similarity_warp": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                          C.c_void_p]),
+    "eamm_op_emotion_augment": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_void_p,
+                                          C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "eamm_last_stream_set": (C.c_int, [C.c_void_p]),
     "eamm_describe_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_int]),
     "eamm_knobs_json": (C.c_int, [C.c_char_p, C.c_int]),

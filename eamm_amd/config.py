@@ -83,6 +83,22 @@ def tiny_kp_config(audio: bool = False) -> dict:
     return c
 
 
+# the emotion video's test-time augmentation: reference config/MEAD_emo_video_aug_delta_4_crop_random_crop.yaml:6-24
+# (dataset_params.augmentation_params), which demo.py:184-190 builds AllAugmentationTransform from
+_EMO_AUG = {
+    "crop_mouth_param": {"center_x": 135, "center_y": 190, "mask_width": 100, "mask_height": 60},
+    "rotation_param": {"degrees": 30},
+    "perspective_param": {"pers_num": 30, "enlarge_num": 40},
+    "flip_param": {"horizontal_flip": True, "time_flip": False},
+    "jitter_param": {"brightness": 0, "contrast": 0, "saturation": 0, "hue": 0},
+}
+
+
+def emotion_augmentation_config() -> dict:
+    """The shipped config's ``augmentation_params``, literally (what ``eamm_amd.video_input`` accepts as ``params``)."""
+    return copy.deepcopy(_EMO_AUG)
+
+
 # emotion detector Emotion_k: reference demo.py:68-70 builds Emotion_k(block_expansion=32, num_channels=3, max_features=1024,
 # num_blocks=5, scale_factor=0.25, num_classes=8)
 def emotion_detector_config() -> dict:

@@ -1762,6 +1762,47 @@ int eamm_op_mfcc(int device, const float* pcm, int64_t n_samples, int n_clips, i
     return e == hipSuccess ? EAMM_OK : fail(nullptr, EAMM_ERR_HIP, "mfcc_kernel: %s", hipGetErrorString(e));
 }
 
+int eamm_op_resize_aa(int device, const uint8_t* in, int n, int H, int W, int C, const double* taps_y, int ry, const double* taps_x,
+                      int rx, uint8_t* out, void* stream_) {
+    OP_ENTRY(!in || !out || !taps_y || !taps_x || n < 1 || n > 65535 || H < 1 || W < 1 || H > 8192 || W > 8192 || (C != 3 && C != 4) ||
+                 ry < 0 || rx < 0 || ry >= VIDEO_MAX_RADIUS || rx >= VIDEO_MAX_RADIUS,
+             "eamm_op_resize_aa: bad argument (1 <= n <= 65535, sides 1..8192, C = 3 | 4, tap radii 0..31)");
+    VideoResizeTaps t{};
+    std::memcpy(t.wy, taps_y, sizeof(double) * (2 * ry + 1));
+    std::memcpy(t.wx, taps_x, sizeof(double) * (2 * rx + 1));
+    t.ry = ry;
+    t.rx = rx;
+    const hipError_t e = resize_aa_launch(in, n, H, W, C, t, out, s);
+    OP_DONE(e, "eamm_op_resize_aa");
+}
+
+int eamm_op_similarity_warp(int device, const uint8_t* in, int n, int H, int W, int C, const double* maps, int mode, void* out,
+                            void* stream_) {
+    OP_ENTRY(!in || !out || !maps || n < 1 || n > 65535 || H < 1 || W < 1 || H > 8192 || W > 8192 || (C != 3 && C != 4) ||
+                 (mode != 0 && mode != 1),
+             "eamm_op_similarity_warp: bad argument (1 <= n <= 65535, sides 1..8192, C = 3 | 4, mode 0 | 1)");
+    const hipError_t e = similarity_warp_launch(in, n, H, W, C, maps, mode, out, s);
+    OP_DONE(e, "eamm_op_similarity_warp");
+}
+
+int eamm_op_emotion_augment(int device, const float* aligned, int64_t n_src, int64_t t0, int count, int flip, const double* rot,
+                            const double* hinv, const float* noise, uint64_t noise_seed, int mouth_x, int mouth_y, int mouth_w,
+                            int mouth_h, float* out, void* stream_) {
+    OP_ENTRY(!aligned || !rot || !hinv || !out || n_src < 1 || t0 < 0 || count < 1 || count > 65535 || mouth_x < 0 || mouth_y < 0 ||
+                 mouth_w < 1 || mouth_h < 1 || mouth_x + mouth_w > 256 || mouth_y + mouth_h > 256,
+             "eamm_op_emotion_augment: bad argument (n_src >= 1, t0 >= 0, 1 <= count <= 65535, a mouth rectangle inside 256 x 256)");
+    VideoAugParams p{};
+    std::memcpy(p.rot, rot, sizeof p.rot);
+    p.noise_seed = noise_seed;
+    p.flip = flip ? 1 : 0;
+    p.mouth_x = mouth_x;
+    p.mouth_y = mouth_y;
+    p.mouth_w = mouth_w;
+    p.mouth_h = mouth_h;
+    const hipError_t e = emotion_augment_launch(aligned, n_src, t0, count, hinv, noise, p, out, s);
+    OP_DONE(e, "eamm_op_emotion_augment");
+}
+
 int eamm_op_warp(int device, const float* feat, const float* deformation, const float* occlusion, int n, int ns, int hf,
                  int wf, int C, int h, int w, float* out, int iters, float* avg_ms, void* stream_) {
     OP_ENTRY(!feat || !deformation || !out || n < 1 || (ns != 1 && ns != n) || hf < 1 || wf < 1 || h < 1 || w < 1 || C < 8 || (C & 7),

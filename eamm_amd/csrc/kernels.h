@@ -335,4 +335,24 @@ long long mfcc_frames(long long n_samples, int pad);
 hipError_t mfcc_launch(const float* pcm, long long n_samples, int n_clips, long long clip_stride, int pad, float* out,
                        hipStream_t stream);
 
+// video_prep.hip: the emotion video's resize (S0), similarity alignment (S1) and fused augmentation (S2..S6); 256 x 256 outputs
+constexpr int VIDEO_MAX_RADIUS = 32;                 // Gaussian radius < 32 per axis: input sides up to about 4000 pixels
+struct VideoResizeTaps {                             // normalised Gaussian taps, index i + r for offset i = -r .. r (r = 0: {1})
+    double wy[2 * VIDEO_MAX_RADIUS - 1];
+    double wx[2 * VIDEO_MAX_RADIUS - 1];
+    int ry, rx;
+};
+struct VideoAugParams {
+    double rot[6];                                   // S4: input (x', y') = [rot0 rot1 rot2; rot3 rot4 rot5] (x, y, 1)
+    unsigned long long noise_seed;                   // device-hash seed (when no explicit noise is passed)
+    int flip;                                        // S3: horizontal flip of the clip
+    int mouth_x, mouth_y, mouth_w, mouth_h;          // S2: the noise rectangle (columns mouth_x .., rows mouth_y ..)
+};
+hipError_t resize_aa_launch(const unsigned char* in, int n, int H, int W, int C, const VideoResizeTaps& taps, unsigned char* out,
+                            hipStream_t stream);
+hipError_t similarity_warp_launch(const unsigned char* in, int n, int H, int W, int C, const double* maps, int mode, void* out,
+                                  hipStream_t stream);
+hipError_t emotion_augment_launch(const float* aligned, long long n_src, long long t0, int count, const double* hinv, const float* noise,
+                                  const VideoAugParams& p, float* out, hipStream_t stream);
+
 }  // namespace eamm

@@ -518,6 +518,39 @@ int eamm_op_one_euro(int device, const float* x, int T, int E, float mincutoff, 
 int64_t eamm_op_mfcc_frames(int64_t n_samples, int pad);
 int eamm_op_mfcc(int device, const float* pcm, int64_t n_samples, int n_clips, int64_t clip_stride, int pad, float* out, void* stream);
 
+/* The emotion video's preprocessing (demo.py:490 resize, demo.py:146-182 get_aligned_image, augmentation.py:403-431 with the
+ * shipped config, demo.py:433-454 crop_image).  Frames are HWC uint8, coordinates (x = column, y = row); every output is
+ * 256 x 256; all arithmetic after the inputs is float64 (eamm_amd/video_input.py holds the numpy oracle of every step).  Device
+ * pointers unless said otherwise; stream-ordered, no sync.  EAMM_ERR_ARG (message in eamm_last_error(NULL)) before any launch
+ * for a bad shape.
+ *
+ * eamm_op_resize_aa: in [n,H,W,C] (C = 3 | 4, alpha dropped) -> out [n,256,256,3] = trunc(255 v), v = the linear zoom
+ *   (in = (o + 0.5) H / 256 - 0.5, neighbours mirrored) of the image x / 255 blurred along rows, then along columns, by the
+ *   normalised Gaussian taps taps_y [2 ry + 1] / taps_x [2 rx + 1] (HOST arrays; ry, rx < 32; r = 0 with {1.0}: no blur) with
+ *   'mirror' borders.  skimage.transform.resize(anti_aliasing=True) of one frame, then demo.py:162's uint8 truncation.
+ * eamm_op_similarity_warp: in [n,H,W,C], maps [n][6] float64 -> output pixel (x, y) samples frame i at
+ *   (maps[0] x + maps[1] y + maps[2], maps[3] x + maps[4] y + maps[5]) bilinearly (floor / ceil neighbours, a neighbour outside
+ *   reads 0; skimage warp order 1, mode 'constant').  mode 0: out float32 NHWC [n,256,256,3] (the aligned video); mode 1: out
+ *   float32 NCHW [n,3,256,256] = trunc(255 v) / 255 (the cropped portrait).
+ * eamm_op_emotion_augment: aligned float32 NHWC [n_src,256,256,3] -> out float32 NCHW [count,3,256,256], output frame t0 + t
+ *   from source frame (t0 + t) mod n_src:
+ *     S2 the rectangle rows mouth_y .. + mouth_h, columns mouth_x .. + mouth_w replaced by noise: noise [n_src][mouth_h][mouth_w][3]
+ *        float32, or, with noise NULL, the device hash
+ *            key = mix64(noise_seed + G),  u = mix64(key + ((src * mouth_h * mouth_w + row * mouth_w + col) * 3 + ch + 1) * G) >> 40,
+ *            value = u * 2^-24 (float32),  G = 0x9E3779B97F4A7C15, mix64 = the splitmix64 finaliser (uint64 arithmetic)
+ *     S3 flip != 0: horizontal flip;  S4 bilinear sample at rot (HOST [6], 2 x 3) (x, y, 1), zero outside (skimage rotate);
+ *     S5 hinv [n_src][9] (the inverse homography, row-major): X0, Y0, W = hinv (x, y, 1), X = rint(X0 * (32 / W)), likewise Y;
+ *        neighbours (X >> 5, Y >> 5) .. + 1, each clamped to the image, weights (32 - fx)(32 - fy) / 1024 ... with fx = X & 31
+ *        (cv2.warpPerspective, BORDER_REPLICATE);
+ *     S6 min(255, max(0, rint(255 v))) / 255 as float32. */
+int eamm_op_resize_aa(int device, const uint8_t* in, int n, int H, int W, int C, const double* taps_y, int ry, const double* taps_x,
+                      int rx, uint8_t* out, void* stream);
+int eamm_op_similarity_warp(int device, const uint8_t* in, int n, int H, int W, int C, const double* maps, int mode, void* out,
+                            void* stream);
+int eamm_op_emotion_augment(int device, const float* aligned, int64_t n_src, int64_t t0, int count, int flip, const double* rot,
+                            const double* hinv, const float* noise, uint64_t noise_seed, int mouth_x, int mouth_y, int mouth_w,
+                            int mouth_h, float* out, void* stream);
+
 /* The HBM-bound kernel of the path on its own: out = grid_sample(feat, deformation, bilinear, zeros, align_corners=False)
  * * occlusion (reference modules/generator.py:50-57, 79-84).  feat: NHWC [ns,hf,wf,C] (ns = 1 broadcasts one source to
  * all frames, else ns = n), deformation [n,h,w,2], occlusion [n,h,w] or NULL, out NHWC [n,hf,wf,C]; when (h,w) != (hf,wf)
