@@ -1,4 +1,4 @@
-// Shared internals of the C-ABI translation units (eamm_api.hip, eamm_kp_api.hip): handle base class, error
+// Shared internals of the C-ABI translation units (eamm_api.hip and its siblings, eamm_kp_api.hip, ...): handle base class, error
 // reporting, device allocation, and the state_dict -> BatchNorm-folded, MFMA-packed layer builders.
 #pragma once
 #include "../../include/eamm_hip.h"
@@ -15,6 +15,13 @@
 #include <vector>
 
 namespace eamm {
+
+// The text behind every *_last_error(NULL): the last failure, on this thread, of an entry that has no handle to report
+// through (a create, an eamm_op_* operator).  ONE per thread for the whole library (an inline variable, unlike the helpers
+// in the anonymous namespace below, of which every translation unit has its own copy): the generator's entries are spread
+// over several translation units and eamm_last_error(NULL) must see all of them.
+inline thread_local std::string g_create_error;
+
 namespace {
 
 struct HostTensor {
@@ -26,8 +33,6 @@ struct HostTensor {
         return n;
     }
 };
-
-thread_local std::string g_create_error;
 
 // A convolution layer packed for the register-staged 128 x BN kernel and, where it pays, also for an LDS-DMA
 // big-tile kernel; conv launches pick by problem size (see pick()).

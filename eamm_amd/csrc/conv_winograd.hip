@@ -393,7 +393,7 @@ static hipError_t wino_launch_variant(const WinoArgs& a, hipStream_t stream) {
 }
 
 hipError_t wino_gemm_launch(const WinoLayer& L, const float* V, int B, int H, int W, int act, const float* resid,
-                            float* out, hipStream_t stream, int variant) {
+                            float* out, hipStream_t stream) {
     constexpr int BM = 128, BN = 128;
     if (L.BN != BN || (L.Cout & 3) || L.Cin % (2 * CONV_BK) || (H & 1) || (W & 1)) return hipErrorInvalidValue;
     WinoArgs a{};
@@ -414,16 +414,9 @@ hipError_t wino_gemm_launch(const WinoLayer& L, const float* V, int B, int H, in
     if (vb >= 0xFFFFFFF0ull || ub >= 0xFFFFFFF0ull) return hipErrorInvalidValue;
     a.v_bytes = (unsigned)vb;
     a.u_bytes = (unsigned)ub;
-    switch (variant) {   // (chunks per barrier, ring depth, MFMAs per DMA piece) -- profiles/r01_wino_variants.txt
-        case 0: return wino_launch_variant<2, 2, 4>(a, stream);
-        case 1: return wino_launch_variant<1, 4, 4>(a, stream);
-        case 2: return wino_launch_variant<1, 5, 4>(a, stream);
-        case 3: return wino_launch_variant<2, 2, 2>(a, stream);
-        case 4: return wino_launch_variant<2, 2, 1>(a, stream);
-        case 5: return wino_launch_variant<1, 3, 4>(a, stream);
-        case 6: return wino_launch_variant<1, 4, 2>(a, stream);
-        default: return hipErrorInvalidValue;
-    }
+    // (chunks per barrier, ring depth, MFMAs per DMA piece): deeper rings and denser pieces measured within noise in the pipeline
+    // (profiles/r01_wino_variants.txt)
+    return wino_launch_variant<2, 2, 4>(a, stream);
 }
 
 }  // namespace eamm

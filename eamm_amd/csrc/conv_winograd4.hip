@@ -174,10 +174,8 @@ struct Wino4Args {
     int act;
     const float* resid;    // NHWC [B,H,W,Cout]
     float* out;            // NHWC [B,H,W,Cout]
-    int groups;            // > 1: the 36 transform points are split over `groups` workgroups per tile (small M): 2 / 3 / 6 = whole rows of six,
-                           // 12 = HALF rows (round 6: one frame per call = 16 blocks of 64 x 64 -> 192 workgroups of the eight-wave kernel)
-    float* zout;           // groups > 1: [24][Mq][Cout] x-folded products Z[i][q] (groups == 12: [48]: slot 2 i + half holds the partial x fold
-                           // of its three points), finished by wino4_output_transform_kernel
+    int groups;            // > 1: the 36 transform points are split over `groups` workgroups per tile (small M): 2 / 3 / 6 = whole rows of six
+    float* zout;           // groups > 1: [24][Mq][Cout] x-folded products Z[i][q], finished by wino4_output_transform_kernel
     float* epi_scratch;    // DBG 30 (timing experiment, EAMM_WINO4_EPI_V): the epilogue also writes 2.25 x the output here
 };
 
@@ -196,7 +194,7 @@ __global__ __launch_bounds__(WM* WN * 64) void wino4_gemm_kernel(const Wino4Args
     constexpr int A_INSTR = BM / 8 / NW, B_INSTR = BN / 8 / NW;       // DMA instructions per wave per chunk
     constexpr int NPIECE = SUB * (A_INSTR + B_INSTR);
     constexpr bool TRACE = DBG == 8 || DBG == 9;   // DBG: 0 product; 1 no DMA in the loop; 8/9 interval trace (with/without DMA);
-    constexpr bool YOUNG_FIRST = DBG != 20;        // 20: every wave interleaves its pieces (the first version)
+                                                   // 30 V-sized extra output; 40 non-temporal V loads
     static_assert(BM % (8 * NW) == 0 && BN % (8 * NW) == 0, "tile rows must split evenly over the waves");
     static_assert(BK == 32, "two 16-wide K steps per chunk");
 
@@ -214,7 +212,7 @@ __global__ __launch_bounds__(WM* WN * 64) void wino4_gemm_kernel(const Wino4Args
     const int ntile = L % p.ntiles;
     const int mtile = (L / p.ntiles) % p.mtiles;
     const int grp = L / (p.ntiles * p.mtiles);          // which transform points (0 when groups == 1)
-    const int xis_per = 36 / p.groups;                   // 36, 18, 12, 6: whole rows; 3 (groups == 12): half a row
+    const int xis_per = 36 / p.groups;                   // 36, 18, 12, 6: whole rows
     const int xi0 = grp * xis_per;                       // first transform point of this workgroup
     const int mbase = mtile * BM;
     const int cchunks = p.C / BK;                         // channel chunks per transform point
@@ -329,7 +327,7 @@ __global__ __launch_bounds__(WM* WN * 64) void wino4_gemm_kernel(const Wino4Args
             });
         });
     };
-    const bool young = YOUNG_FIRST && wave >= NW / 2;
+    const bool young = wave >= NW / 2;
     auto interval = [&](int st, bool more) {
         if (more) {
             if (young) compute(st, std::true_type{}, std::true_type{});
@@ -409,7 +407,11 @@ __global__ __launch_bounds__(WM* WN * 64) void wino4_gemm_kernel(const Wino4Args
     __syncthreads();
     int st = 0;
     int xi_left = per_xi, xj = xi0 % 6, xrow = xi0 / 6;
-    const bool half_rows = p.groups == 12;   // a workgroup's three points are half of row xrow: its Z is a partial x fold, slot = grp
+    // A workgroup whose points end inside a row (xis_per % 6 != 0) would leave a PARTIAL x fold in slot grp.  No launch has such a
+    // split (wino4_gemm_launch admits 1, 2, 3, 6), so half_rows is always false; the three lines that serve it stay because
+    // hipcc lays out the whole main loop differently without them and the bottleneck GEMM then runs 0.2 - 0.3 % slower (measured
+    // on the 16-frame plan, alternated runs) -- they cost one scalar compare per workgroup.
+    const bool half_rows = p.groups == 12;
     for (int sc = 0; sc < nsuper; ++sc) {
         const bool more = sc + D < nsuper;
         long long ts0 = 0, ts1 = 0, ts2 = 0;
@@ -445,7 +447,7 @@ __global__ __launch_bounds__(WM* WN * 64) void wino4_gemm_kernel(const Wino4Args
     }
 
     if (p.zout != nullptr) {
-        if (half_rows && xj != 0) store_z(grp);   // the first half of a row ends at j = 2: its partial fold has not left yet
+        if (half_rows && xj != 0) store_z(grp);
         return;
     }
     // ---- epilogue: one output row py (four pixels) per round, staged through LDS, 16-byte row accesses.
@@ -518,8 +520,7 @@ __global__ __launch_bounds__(WM* WN * 64) void wino4_gemm_kernel(const Wino4Args
 
 // y fold of the split form: Y[p][q] = sum_i A^T[p][i] Z[i][q] (+ bias, residual, activation) -> the 4x4 output pixels;
 // POOL: followed by the 2x2 average of DownBlock2d (reference modules/util.py:903-921) -> 2x2 pixels of [B,H/2,W/2,Cout]
-// HALVES = 2 (groups == 12): row i arrives as two partial x folds, slots 2 i and 2 i + 1, added first (always in that order).
-template <bool POOL, bool RESID, int HALVES = 1>
+template <bool POOL, bool RESID>
 __global__ __launch_bounds__(256) void wino4_output_transform_kernel(const float* __restrict__ Z, const float* __restrict__ bias,
                                                                      const float* __restrict__ resid, int Mq, int Cout, int H,
                                                                      int W, int act, float* __restrict__ out) {
@@ -539,19 +540,8 @@ __global__ __launch_bounds__(256) void wino4_output_transform_kernel(const float
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             f32x4_t zi[6];
-            if constexpr (HALVES == 2) {
-                f32x4_t za[6], zb[6];      // all twelve loads in flight before the first add
 #pragma unroll
-                for (int i = 0; i < 6; ++i) {
-                    za[i] = z[(size_t)((2 * i) * 4 + q) * plane];
-                    zb[i] = z[(size_t)((2 * i + 1) * 4 + q) * plane];
-                }
-#pragma unroll
-                for (int i = 0; i < 6; ++i) zi[i] = za[i] + zb[i];
-            } else {
-#pragma unroll
-                for (int i = 0; i < 6; ++i) zi[i] = z[(size_t)(i * 4 + q) * plane];
-            }
+            for (int i = 0; i < 6; ++i) zi[i] = z[(size_t)(i * 4 + q) * plane];
             const f32x4_t s12 = zi[1] + zi[2], d12 = zi[1] - zi[2], s34 = zi[3] + zi[4], d34 = zi[3] - zi[4];
             f32x4_t y[4];
             y[0] = zi[0] + s12 + s34;
@@ -696,8 +686,7 @@ hipError_t wino4_gemm_launch(const WinoLayer& L, const float* V, int B, int H, i
     a.act = act;
     a.resid = resid;
     a.out = out;
-    if (groups != 1 && groups != 2 && groups != 3 && groups != 6 && groups != 12) return hipErrorInvalidValue;
-    if (groups == 12 && (pool || (L.Cin / CONV_BK) * 3 % 4 != 0)) return hipErrorInvalidValue;   // half rows: three points x Cin / 32 chunks, four per interval
+    if (groups != 1 && groups != 2 && groups != 3 && groups != 6) return hipErrorInvalidValue;
     if (groups > 1 && zbuf == nullptr) return hipErrorInvalidValue;
     a.groups = groups;
     a.zout = groups > 1 ? zbuf : nullptr;
@@ -727,25 +716,14 @@ hipError_t wino4_gemm_launch(const WinoLayer& L, const float* V, int B, int H, i
         case 17: e = wino4_launch_variant<4, 2, 4, 9>(a, stream); break;
 #endif
         case 0: e = sub4 ? wino4_launch_variant<4, 2, 4>(a, stream) : wino4_launch_variant<2, 2, 4>(a, stream); break;
-        case 1: e = wino4_launch_variant<2, 2, 4>(a, stream); break;
-        case 2: e = wino4_launch_variant<2, 3, 4>(a, stream); break;
         case 3: e = sub4 ? wino4_launch_variant<4, 2, 8>(a, stream) : wino4_launch_variant<2, 2, 4>(a, stream); break;
-        case 4: e = wino4_launch_variant<2, 4, 4>(a, stream); break;
         case 6: e = sub4 ? wino4_launch_variant<4, 2, 8, 40>(a, stream) : wino4_launch_variant<2, 2, 4>(a, stream); break;   // variant 3 with non-temporal V loads (the default since round 5: 4034 -> 4048 frames/s)
-        case 5: e = sub4 ? wino4_launch_variant<4, 2, 4, 20>(a, stream) : wino4_launch_variant<2, 2, 4, 20>(a, stream); break;
-        default: break;
+        default: break;   // (eamm_create admits 0, 3, 6 only)
     }
     if (e != hipSuccess || groups == 1) return e;
     const size_t total = (size_t)a.Mq * (L.Cout / 4);
     const int blocks = (int)std::min<size_t>((total + 255) / 256, (size_t)1 << 20);
-    if (groups == 12) {
-        if (resid != nullptr)
-            hipLaunchKernelGGL((wino4_output_transform_kernel<false, true, 2>), dim3(blocks), dim3(256), 0, stream, zbuf, L.bias, resid,
-                               a.Mq, L.Cout, H, W, act, out);
-        else
-            hipLaunchKernelGGL((wino4_output_transform_kernel<false, false, 2>), dim3(blocks), dim3(256), 0, stream, zbuf, L.bias, resid,
-                               a.Mq, L.Cout, H, W, act, out);
-    } else if (pool)
+    if (pool)
         hipLaunchKernelGGL((wino4_output_transform_kernel<true, false>), dim3(blocks), dim3(256), 0, stream, zbuf, L.bias, resid,
                            a.Mq, L.Cout, H, W, act, out);
     else if (resid != nullptr)

@@ -1,4 +1,5 @@
-// The generator handle (private to the C-ABI translation units eamm_api.hip and eamm_train_api.hip).
+// The generator handle and what its C-ABI translation units share: eamm_api.hip (handle, weights, workspace, source encoding),
+// eamm_forward.hip (launch plan, per-frame pass, profiling), eamm_op_api.hip (operator entries), eamm_train_api.hip.
 #pragma once
 #include "../../include/eamm_hip.h"
 #include "api_common.h"
@@ -55,38 +56,31 @@ struct eamm_ctx : eamm::CtxBase {
                                            // when each chain's F(4x4) GEMM keeps enough workgroups (pass_chains_min_blocks); otherwise off)
     int pass_chains_min_blocks = 80;       // automatic mode: fewest bottleneck-GEMM workgroups per chain (EAMM_PASS_CHAINS_MIN_BLOCKS)
     int pass_chains_min_frames = 8;        // ... from this many frames per call (EAMM_PASS_CHAINS_MIN_FRAMES)
-    std::vector<hipStream_t> side_streams; // the other chains' streams of the call being enqueued: pool_streams or own_streams (StreamLease in eamm_api.hip)
+    std::vector<hipStream_t> side_streams; // the other chains' streams of the call being enqueued: pool_streams or own_streams (StreamLease in eamm_forward.hip)
     std::vector<hipStream_t> pool_streams; // ... the device's shared pool (chain_stream(), not owned)
     std::vector<hipStream_t> own_streams;  // ... this handle's private set: used while the caller's stream is being captured or another
                                            // thread holds the pool; created on first need, destroyed with the handle
     int private_streams = 0;               // EAMM_PRIVATE_STREAMS=1: always the private set
     int last_streams = 0;                  // which set the last call used: 0 pool, 1 private (pool taken), 2 private (capture)
     hipEvent_t ev_fork = nullptr;
-    hipEvent_t ev_stagger = nullptr;       // recorded by the first chain after its first bottleneck input transform
     hipEvent_t ev_warp = nullptr;          // recorded by the first chain behind the joint warp launch (EAMM_WARP_JOINT)
-    int enc_cus_pct = 100;                 // EAMM_ENC_CUS_PCT: the hourglass encoder's F(4x4) point-row split is sized for this share of the chip's CUs
-                                           // (measured hg_enc ms per step: 25 %: 0.342, 50 %: 0.256, 100 %: 0.242, 200 %: 0.252, 400 %: 0.251)
     int epi_v = 0;                         // EAMM_WINO4_EPI_V=1: timing experiment (wrong results): see conv_winograd4.hip DBG 30
     float* epi_scratch = nullptr;
     int warp_joint = 0;                    // one feature-warp launch for all chains' frames
-    int bneck_stagger = 0;                 // EAMM_BNECK_STAGGER=1: the other whole-pass chains start their bottleneck stage behind that event, so the
-                                           // chains' HBM-bound input transforms run beside the other chain's GEMM instead of beside each other
     std::vector<hipEvent_t> ev_join;
     int cur_pass_chains = 1;               // whole-pass chains of the call being enqueued
     int cur_call_frames = 0;               // ... and its frames (all chains)
     int wino_tile = 4;                     // preferred output tile (EAMM_WINO_TILE): 4 -> F(4x4) where it applies, 2 -> F(2x2)
-    int wino4_variant = 6;                 // wino4_gemm_kernel pipeline variant (3: one DMA piece per 8 MFMAs; 2.062 -> 2.047 ms per step vs one per 4;
-                                           // 6 = 3 with the V stream loaded non-temporally where every GEMM workgroup of the call has a CU
-                                           // of its own, 3 for larger calls: wino4_variant_for, eamm_api.hip)
+    int wino4_variant = 6;                 // wino4_gemm_kernel pipeline variant, 0 | 3 | 6 (3: one DMA piece per 8 MFMAs; 2.062 -> 2.047 ms per step vs
+                                           // one per 4; 6 = 3 with the V stream loaded non-temporally where every GEMM workgroup of the call has a CU
+                                           // of its own, 3 for larger calls: wino4_variant_for, eamm_forward.hip)
     bool wino4_variant_pinned = false;     // EAMM_WINO4_VARIANT set: that variant for every call size
     int cus = 256;                         // the device's CU count, read ONCE in eamm_create (the per-call launch rules size their splits by it)
-    int wino4_groups_knob = 0;             // EAMM_WINO4_GROUPS read once in eamm_create (0: unset -> the rule in wino4_groups())
     float* wino_v = nullptr;               // [16][F*hf*wf/4][Cb] (F(2x2)) or [36][F*hf*wf/16][Cb] transformed activations
-    float* wino_z = nullptr;               // [24][F*hf*wf/16][Cb] x-folded products of the split F(4x4) form (few tiles; [48] for the half-row split)
+    float* wino_z = nullptr;               // [24][F*hf*wf/16][Cb] x-folded products of the split F(4x4) form (few tiles)
     size_t wino_z_elems = 0;               // its size in floats
     int wino_min_m = 49152;                // smallest pixel count for which the bottleneck runs in Winograd F(2x2) form
     int wino4_min_m = 0;                   // ... in F(4x4) form: with the transform-point rows split over workgroups it wins from one frame up
-    int wino_variant = 0;                  // wino_gemm_kernel pipeline variant (see wino_gemm_launch); in-pipeline all are within noise
     std::vector<float*> pre_s, pre_t;  // res-block pre-activation scale/shift (norm1)
     float* aa_w = nullptr;
     float* head_bias = nullptr;    // mask / occlusion biases when the head runs row-split (applied by the head kernel)
@@ -156,3 +150,39 @@ struct eamm_ctx : eamm::CtxBase {
     int pending_c = 0;                     // channels of the site whose sums are pending
 };
 
+// ---- plan rules that more than one translation unit applies (the per-call rules live in eamm_forward.hip) ----------------
+
+// F(4x4) with few tiles: the six rows of transform points are split over 6, 3 or 2 workgroups per 64 x 64 (tile, cout)
+// block -- the largest split that still fits one round of the chip, one block per CU; 1 = no split.  A POOLED level (hourglass
+// encoder, source down blocks) takes at least 2: its epilogue is the output-transform kernel's.
+inline int wino4_row_split(const eamm_ctx* c, int tiles, int ntiles, bool pooled = false) {
+    const int nblk = ((tiles + 63) / 64) * ntiles;
+    for (int g : {6, 3, 2})
+        if (nblk * g <= c->cus) return g;
+    return pooled ? 2 : 1;
+}
+
+// Whole-pass chains in automatic mode (EAMM_PASS_CHAINS=0): two; four from 64 frames per call, where every chain still gets
+// 16 (256x256: 4150 -> 4197 frames/s, profiles/r04_experiments.txt section 16; four chains of 8 at 32 frames gain nothing)
+inline int auto_pass_chains(int frames) { return frames >= 64 ? 4 : 2; }
+// ... and the most any call of this handle can use (pass_chains is clamped to 0..4 in eamm_create): one split-K slab and one
+// stream per chain
+inline int max_pass_chains(const eamm_ctx* c) { return c->pass_chains == 0 ? auto_pass_chains(c->cfg.max_frames) : c->pass_chains; }
+
+// The ConvIO of a single-input convolution over B images of Hin x Win; a second input, residual, pooling ... are the caller's to add
+inline ConvIO conv_io(const float* in0, int B, int Hin, int Win, int act, float* out, float* partial, size_t partial_cap) {
+    ConvIO io{};
+    io.in0 = in0;
+    io.B = B;
+    io.Hin = Hin;
+    io.Win = Win;
+    io.act = act;
+    io.out = out;
+    io.partial = partial;
+    io.partial_cap = partial_cap;
+    return io;
+}
+
+// Side stream k of `device` from the pool every handle of the process shares (created on first use, never destroyed; null on
+// failure).  One definition, in eamm_forward.hip beside StreamLease, which leases the pool per call.
+hipStream_t chain_stream(int device, int k);

@@ -101,17 +101,9 @@ int eamm_train_begin(eamm_ctx* c, const float* source, int n, const float* kd_va
     auto conv = [&](const LayerSet* S, const ConvLayer* single, const float* in0, const float* in1, int Hin, int Win, const float* resid,
                     float* dst) {
         step([=]() -> int {
-            ConvIO io{};
-            io.in0 = in0;
+            ConvIO io = conv_io(in0, n, Hin, Win, ACT_NONE, dst, c->partial, c->partial_elems);
             io.in1 = in1;
-            io.B = n;
-            io.Hin = Hin;
-            io.Win = Win;
-            io.act = ACT_NONE;
             io.resid = resid;
-            io.out = dst;
-            io.partial = c->partial;
-            io.partial_cap = c->partial_elems;
             HIP_TRY(c, conv_launch(S ? pick(c, *S, (size_t)n * Hin * Win) : *single, io, s));
             return 0;
         });
@@ -147,16 +139,8 @@ int eamm_train_begin(eamm_ctx* c, const float* source, int n, const float* kd_va
             bn_site(c->raw, n, 2 * Hin, 2 * Win, c->dec_c[i], 0, c->u_buf[i]);
         }
         step([=]() -> int {   // mask / occlusion logits, softmax, flow, sigmoid (dense_motion.py:98-111): no BatchNorm here
-            ConvIO io{};
-            io.in0 = c->u_buf[c->nb - 1];
+            ConvIO io = conv_io(c->u_buf[c->nb - 1], n, h, w, ACT_NONE, c->logits, c->partial, c->partial_elems);
             io.in1 = c->hg_in;
-            io.B = n;
-            io.Hin = h;
-            io.Win = w;
-            io.act = ACT_NONE;
-            io.out = c->logits;
-            io.partial = c->partial;
-            io.partial_cap = c->partial_elems;
             ConvLayer head = c->head;
             if (c->head_nc) {
                 head.Cout = 128;
@@ -200,15 +184,7 @@ int eamm_train_begin(eamm_ctx* c, const float* source, int n, const float* kd_va
         cur = c->up_buf[i];
     }
     step([=]() -> int {
-        ConvIO io{};
-        io.in0 = cur;
-        io.B = n;
-        io.Hin = H;
-        io.Win = W;
-        io.act = ACT_NONE;
-        io.out = c->final_part;
-        io.partial = c->partial;
-        io.partial_cap = c->partial_elems;
+        const ConvIO io = conv_io(cur, n, H, W, ACT_NONE, c->final_part, c->partial, c->partial_elems);
         ConvLayer fl = c->final_conv;
         fl.Cout = 32;
         HIP_TRY(c, conv_launch(fl, io, s));

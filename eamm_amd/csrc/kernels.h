@@ -145,13 +145,14 @@ void wino_pack_host(const float* w_oihw, int Cout, int Cin, int BN, float* dst);
 hipError_t wino_transform_launch(const float* x, const float* s, const float* t, int B, int H, int W, int C, float* V,
                                  hipStream_t stream);
 hipError_t wino_gemm_launch(const WinoLayer& L, const float* V, int B, int H, int W, int act, const float* resid,
-                            float* out, hipStream_t stream, int variant = 0);
+                            float* out, hipStream_t stream);
 
 size_t wino4_packed_elems(int Cout, int Cin, int BN);
 void wino4_pack_host(const float* w_oihw, int Cout, int Cin, int BN, float* dst);
 // V[36][B*H/4*W/4][C] = B^T d B of x (optionally of relu(x*s + t)); H, W multiples of 4
 hipError_t wino4_transform_launch(const float* x, const float* s, const float* t, int B, int H, int W, int C, float* V,
                                   hipStream_t stream);
+// variant: the GEMM's software pipeline, 0 | 3 | 6 (conv_winograd4.hip)
 // groups in {1,2,3,6}: > 1 splits the six rows of transform points over that many workgroups per tile (few tiles) and
 // finishes with wino4_output_transform_kernel; zbuf: [24][B*H/4*W/4][Cout] floats; pool (groups > 1 only): 2x2 average
 // after the activation, out is [B,H/2,W/2,Cout]

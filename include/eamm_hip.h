@@ -167,10 +167,10 @@ int eamm_describe_plan(const eamm_ctx* ctx, int n, char* buf, int cap);
  *                                          KPDetector_a's heads (wide + thin split | one padded convolution)
  *   EAMM_WGRAD_WINO4, EAMM_WGRAD_ROW, EAMM_CONV_DEV_WINO4   (0 | 1) forms of the training operators
  *   EAMM_PRIVATE_STREAMS (0 | 1)           never use the shared side-stream pool
- *   EAMM_WARP_JOINT, EAMM_BNECK_STAGGER    scheduling variants measured in round 4 (off)
- *   EAMM_WINO4_VARIANT (0-6)               software pipeline of the F(4x4) bottleneck GEMM, pinned for every call size; unset: 6 (variant 3 with
+ *   EAMM_WARP_JOINT                        scheduling variant measured in round 4 (off)
+ *   EAMM_WINO4_VARIANT (0 | 3 | 6)         software pipeline of the F(4x4) bottleneck GEMM, pinned for every call size; unset: 6 (variant 3 with
  *                                          the transformed input loaded non-temporally) while the call's GEMM workgroups number at most the CUs,
- *                                          3 above (bit-identical results)
+ *                                          3 above (bit-identical results); eamm_create refuses any other value
  * TUNING aids (tile-size thresholds, pipeline variants, split sizes: everything else the sources read) are honoured only together
  * with EAMM_TUNING=1; without it they are ignored and reported with "set": 2.
  * Knobs that compute WRONG results (timing experiments: EAMM_WINO4_EPI_V, EAMM_COL7_DBG, EAMM_WINO4_VARIANT 10/16/17/50) exist
@@ -429,7 +429,8 @@ const char* eamm_bn_last_error(void);
  *                              squares and the element count as in eamm_bn_local_sums -- ALL-REDUCE them over the replicas on the
  *                              same stream (nothing to do on one replica) and call again; returns 0 when the outputs given
  *                              to eamm_train_begin are complete (stream-ordered), < 0 on error.
- * Forward only: the outputs carry no gradient (the convolution and warp backward kernels are not built).
+ * Forward only: the outputs carry no gradient (the backward pass is composed from the differentiable operator entries further
+ * down -- eamm_op_conv_dev, eamm_op_conv_wgrad, eamm_op_warp_backward, ... -- by eamm_amd/train_graph.py, not by this forward).
  */
 typedef struct eamm_bn_site {
     const float* weight;     /* [C] device                                  */
@@ -480,9 +481,9 @@ int eamm_profile_read(eamm_ctx* ctx, double* stage_ms, int nstage, int64_t* call
  * weights packed as the engine packs them for it:
  *   0                automatic register-staged tile; 32 / 64 / 128: the register-staged 128 x tile_n kernel
  *   1000 + id        LDS-DMA tile (1: 256x256, 2: 256x128, 3: 512x64, 4: 32x128, 5: 64x128); not 7x7 / 7x1
- *   2000 + variant   Winograd F(2x2,3x3): input transform + GEMM (3x3, single input, Cin % 64 == 0, no pool)
- *   2100 + variant   Winograd F(4x4,3x3) (as 2000, Hin and Win multiples of 4)
- *   2150 + groups    F(4x4,3x3) with the transform-point rows split over 2, 3, 6 or 12 workgroups + output-transform
+ *   2000             Winograd F(2x2,3x3): input transform + GEMM (3x3, single input, Cin % 64 == 0, no pool)
+ *   2100 + variant   Winograd F(4x4,3x3) (as 2000, Hin and Win multiples of 4); variant 0 | 3 | 6: the GEMM's software pipeline
+ *   2150 + groups    F(4x4,3x3) with the transform-point rows split over 2, 3 or 6 workgroups + output-transform
  *                    kernel (pool allowed without resid)
  *   3000 / 3003      spatial-patch kernel of the up-convolution (up = 1): collapsed-phase / polyphase form (3003 only:
  *                    splitk > 1 splits the channel reduction)

@@ -130,18 +130,16 @@ CASES = {
     "wino_basic":        dict(B=2, H=16, W=16, C0=64, C1=0, Cout=128, ks=3, act=1, tile_n=2000),
     "wino_tails_resid":  dict(B=1, H=6, W=10, C0=64, C1=0, Cout=136, ks=3, resid=True, tile_n=2000),
     "wino_bottleneck":   dict(B=4, H=64, W=64, C0=256, C1=0, Cout=256, ks=3, resid=True, tile_n=2000),
-    "wino_ring4":        dict(B=2, H=16, W=16, C0=64, C1=0, Cout=128, ks=3, act=1, tile_n=2001),
-    "wino_ring5":        dict(B=1, H=6, W=10, C0=128, C1=0, Cout=136, ks=3, resid=True, tile_n=2002),
-    "wino_pe1":          dict(B=2, H=16, W=16, C0=64, C1=0, Cout=128, ks=3, act=1, tile_n=2004),
-    "wino_ring3":        dict(B=2, H=16, W=16, C0=64, C1=0, Cout=128, ks=3, act=1, tile_n=2005),
-    # Winograd F(4x4,3x3) path (tile_n = 2100 + pipeline variant)
+    "wino_ring5":        dict(B=1, H=6, W=10, C0=128, C1=0, Cout=136, ks=3, resid=True, tile_n=2000),   # Cin = 128, ragged Cout
+    # Winograd F(4x4,3x3) path (tile_n = 2100 + pipeline variant: 0, 3 = one DMA piece per 8 MFMAs, 6 = 3 with non-temporal V
+    # loads; "ring3" / "ring4" / "interleaved" name pipelines that are gone -- the cases keep their shapes on a kept variant)
     "wino4_basic":       dict(B=2, H=16, W=16, C0=128, C1=0, Cout=128, ks=3, act=1, tile_n=2100),
     "wino4_sub2":        dict(B=2, H=16, W=16, C0=64, C1=0, Cout=64, ks=3, act=1, tile_n=2100),
     "wino4_tails_resid": dict(B=1, H=8, W=12, C0=64, C1=0, Cout=136, ks=3, resid=True, tile_n=2100),
     "wino4_bottleneck":  dict(B=4, H=64, W=64, C0=256, C1=0, Cout=256, ks=3, resid=True, tile_n=2100),
-    "wino4_ring3":       dict(B=3, H=16, W=20, C0=128, C1=0, Cout=96, ks=3, act=1, tile_n=2102),
+    "wino4_ring3":       dict(B=3, H=16, W=20, C0=128, C1=0, Cout=96, ks=3, act=1, tile_n=2103),
     "wino4_pe8":         dict(B=2, H=16, W=16, C0=128, C1=0, Cout=128, ks=3, act=1, tile_n=2103),
-    "wino4_ring4":       dict(B=1, H=12, W=8, C0=192, C1=0, Cout=64, ks=3, resid=True, tile_n=2104),
+    "wino4_ring4":       dict(B=1, H=12, W=8, C0=192, C1=0, Cout=64, ks=3, resid=True, tile_n=2106),   # Cin = 192: the two-chunk fallback
     "wino4_split6":      dict(B=1, H=16, W=16, C0=128, C1=0, Cout=128, ks=3, act=1, tile_n=2156),
     "wino4_split3_res":  dict(B=2, H=8, W=12, C0=64, C1=0, Cout=136, ks=3, resid=True, tile_n=2153),
     "wino4_split2":      dict(B=1, H=64, W=64, C0=256, C1=0, Cout=256, ks=3, resid=True, tile_n=2152),
@@ -151,13 +149,8 @@ CASES = {
     "wino4_pool_enc3":   dict(B=3, H=8, W=8, C0=512, C1=0, Cout=1024, ks=3, act=1, pool=1, tile_n=2156),
     # one frame of the bottleneck: 32-tile four-wave blocks, six transform-point rows per tile, residual in the output transform
     "wino4_one_frame_narrow": dict(B=1, H=64, W=64, C0=256, C1=0, Cout=256, ks=3, resid=True, tile_n=2156),
-    # round 6: the HALF-row split (12 workgroups per 64 x 64 block, 48 planes of partial x folds summed by the output transform) --
-    # the one-frame plan of the bottleneck (192 eight-wave workgroups), with and without residual, ragged M / Cout tails
-    "wino4_half_rows_one_frame": dict(B=1, H=64, W=64, C0=256, C1=0, Cout=256, ks=3, resid=True, tile_n=2162),
-    "wino4_half_rows_relu":      dict(B=1, H=64, W=64, C0=256, C1=0, Cout=256, ks=3, act=1, tile_n=2162),
-    "wino4_half_rows_ragged":    dict(B=3, H=12, W=20, C0=128, C1=0, Cout=72, ks=3, resid=True, tile_n=2162),
     "wino4_pool_ragged": dict(B=1, H=12, W=20, C0=64, C1=0, Cout=72, ks=3, act=1, pool=1, tile_n=2156),
-    "wino4_interleaved": dict(B=3, H=16, W=20, C0=128, C1=0, Cout=96, ks=3, resid=True, tile_n=2105),
+    "wino4_interleaved": dict(B=3, H=16, W=20, C0=128, C1=0, Cout=96, ks=3, resid=True, tile_n=2106),
     "7x1_rowsplit":      dict(B=2, H=16, W=16, C0=64, C1=0, Cout=21, ks=7, kw=1),
     "7x7_head":          dict(B=1, H=16, W=16, C0=32, C1=64, Cout=12, ks=7),
     "7x7_sigmoid":       dict(B=1, H=32, W=32, C0=32, C1=0, Cout=3, ks=7, act=2),
@@ -176,6 +169,26 @@ def test_conv_mfma_matches_torch(name):
     # exact-fp32 MFMA (fmaf chain) vs oneDNN: only summation order differs
     # Winograd: same fp32 arithmetic, but the transform-domain sums cancel -> a few ulp more rounding
     assert err <= (6e-5 if CASES[name].get("tile_n", 0) >= 2000 else 2e-5) * scale, (name, err, scale)
+
+
+def test_removed_winograd_launch_forms_are_refused(monkeypatch):
+    """The GEMM pipeline variants other than 0 / 3 / 6, the F(2x2) variants and the half-row split are gone: the operator entry
+    refuses their tile codes before it launches a GEMM, and eamm_create refuses an EAMM_WINO4_VARIANT the library does not have
+    (it used to be accepted and then fail every forward)."""
+    from eamm_amd import tiny_config
+    from eamm_amd.engine import Engine
+    shape = dict(B=1, H=16, W=16, C0=128, C1=0, Cout=128, ks=3)
+    for tile_n in (2001, 2006, 2101, 2102, 2104, 2105, 2162):
+        with pytest.raises(_lib.EammError):
+            run_case(**shape, tile_n=tile_n)
+    for variant in ("1", "2", "4", "5", "7"):
+        monkeypatch.setenv("EAMM_WINO4_VARIANT", variant)
+        with pytest.raises(_lib.EammError, match="EAMM_WINO4_VARIANT=" + variant) as exc:
+            Engine(tiny_config(), 64, 64)
+        assert exc.value.code == _lib.ERR_ARG
+    for variant in ("0", "3", "6"):
+        monkeypatch.setenv("EAMM_WINO4_VARIANT", variant)
+        Engine(tiny_config(), 64, 64)
 
 
 def test_conv_linearity_property():

@@ -1,6 +1,6 @@
 """The launch plan BASELINE.json configs[3] is quoted on (VERDICT r04 "What's weak" 1): calls of 64 frames at 256x256 run as
 FOUR whole-pass chains on the caller's stream + three side streams taken from a per-device pool shared by every handle
-(eamm_api.hip: pass_chains, StreamLease).  An 8-GPU job over a 2048-frame clip gives each rank 256 frames = four such calls.
+(eamm_forward.hip: pass_chains, StreamLease).  An 8-GPU job over a 2048-frame clip gives each rank 256 frames = four such calls.
 
 Checked here, through the C ABI: (a) a 64-frame call against the same frames in four 16-frame calls (two chains of 8: the
 plan `value` is measured on) and against the CPU oracle on frames {0, 17, 40, 63}, every output key; (b) ragged calls of 50
@@ -158,7 +158,7 @@ def test_three_chains_by_knob(monkeypatch):
 def test_gemm_cache_policy_variants_are_bit_identical(monkeypatch):
     """The bottleneck GEMM's variant 6 = variant 3 with the transformed-input stream loaded non-temporally.  The library picks 6
     while every GEMM workgroup of a call has a CU of its own (16 frames at 256x256: + 0.3 %) and 3 for larger calls (128 frames:
-    6 costs 2 %; eamm_api.hip wino4_variant_for); EAMM_WINO4_VARIANT pins one for every call size.  A cache hint must not change a
+    6 costs 2 %; eamm_forward.hip wino4_variant_for); EAMM_WINO4_VARIANT pins one for every call size.  A cache hint must not change a
     bit: each plan under the other variant against the default's frames."""
     st = state()
     kd, ks = cuda(st["kp_d"]), cuda(st["kp_s"])
