@@ -83,3 +83,25 @@ def test_hip_forms_on_the_adversarial_network(name, cfg_fn, form, env, monkeypat
                                outputs=KEYS)
         e.check_numeric()
     compare(f"HIP form {form} vs reference, {name}", out, fx)
+
+
+@pytest.mark.gpu
+def test_adversarial_network_at_the_timed_16_frame_plan():
+    """The forms above run the fixture's two frames in a two-frame call; the benchmark times 16 frames per call at 256x256 (other
+    tiles, split-K and chain plans).  Here the fixture's frames are rows 0 .. of a 16-frame call whose remaining rows repeat the
+    fixture's driving key points; the fixture's rows are held to the same max(TOL, 4 x floor)."""
+    cfg = hot_path_config()
+    fx, sd, src, kp_d, kp_s = rebuild("full256_adversarial", cfg)
+    n = kp_d["value"].shape[0]
+    rows = torch.arange(16) % n
+    with torch.no_grad():
+        gen = OcclusionAwareGenerator(**cfg)
+        gen.load_state_dict(sd, strict=True)
+        gen = gen.to("cuda:0").eval()
+        e = gen.encode_source(src.to("cuda:0"), max_frames=16)
+        assert e.bottleneck_form(16) == 4
+        out = e.forward_frames({k: v[rows].to("cuda:0") for k, v in kp_d.items()}, {k: v.to("cuda:0") for k, v in kp_s.items()},
+                               outputs=KEYS)
+        e.check_numeric()
+    assert out["prediction"].shape[0] == 16
+    compare("HIP 16-frame plan vs reference, full256_adversarial", {k: v[:n] for k, v in out.items()}, fx)

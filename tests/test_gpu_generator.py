@@ -210,6 +210,54 @@ def test_full_batch16_properties():
         assert worst[k] <= TOL[k], (k, worst[k])
 
 
+def _num_kp_engine(num_kp, size, frames):
+    """A generator of the shipped configuration with another num_kp, its source encoded for `frames` frames per call."""
+    cfg = {**hot_path_config(), "num_kp": num_kp}
+    sd = synthetic_state_dict(cfg, seed=1234)
+    gen = OcclusionAwareGenerator(**cfg)
+    gen.load_state_dict(sd, strict=True)
+    gen = gen.to(DEV).eval()
+    src, kp_s, kp_d = synthetic_source(size, seed=1), synthetic_keypoints(1, num_kp, seed=0), synthetic_keypoints(frames, num_kp, seed=2)
+    return cfg, sd, src, kp_s, kp_d, gen.encode_source(src.to(DEV), max_frames=frames)
+
+
+def _against_oracle(tag, full, pick, cfg, sd, src, kp_s, kp_d):
+    n = len(pick)
+    ref = orc.generator_forward(sd, cfg, src.expand(n, -1, -1, -1).contiguous(), {k: v[pick] for k, v in kp_d.items()},
+                                {k: v.expand(n, *v.shape[1:]).contiguous() for k, v in kp_s.items()})
+    errs = {k: float((full[k][pick].cpu() - ref[k]).abs().max()) for k in KEYS}
+    report(tag, errs)
+    for k in KEYS:
+        assert errs[k] <= TOL[k], (tag, k, errs[k])
+
+
+@pytest.mark.parametrize("num_kp", [5, 15, 30])
+def test_num_kp_at_the_16_frame_launch_geometry(num_kp):
+    """num_kp != 10 at the size the benchmark times (256x256, 16 frames per call): K sets the flow head's N = 7(K+2) padding and
+    the line width of motion_front_kernel, and both change tile choice with the batch size -- the num_kp fixtures run one or two
+    frames only.  Every key of frames 0 and 15 against the oracle, the softmax over the K+1 motions, frame independence."""
+    cfg, sd, src, kp_s, kp_d, e = _num_kp_engine(num_kp, 256, 16)
+    full = e.forward_frames(cuda(kp_d), cuda(kp_s), outputs=KEYS)
+    e.check_numeric()
+    assert full["prediction"].shape == (16, 3, 256, 256) and full["mask"].shape == (16, num_kp + 1, 64, 64)
+    assert float((full["mask"].sum(dim=1) - 1).abs().max()) <= 1e-5
+    alone = e.forward_frames(cuda({k: v[9:10] for k, v in kp_d.items()}), cuda(kp_s))["prediction"]
+    assert float((alone[0] - full["prediction"][9]).abs().max()) <= 2e-5
+    _against_oracle(f"num_kp {num_kp}, 256x256 x 16 vs oracle (frames 0, 15)", full, [0, 15], cfg, sd, src, kp_s, kp_d)
+
+
+def test_num_kp_15_at_512_batch8():
+    """num_kp = 15 at 512x512, 8 frames per call (the motion grid is 128x128 there): one frame against the oracle, every key."""
+    cfg, sd, src, kp_s, kp_d, e = _num_kp_engine(15, 512, 8)
+    full = e.forward_frames(cuda(kp_d), cuda(kp_s), outputs=KEYS)
+    e.check_numeric()
+    assert full["prediction"].shape == (8, 3, 512, 512)
+    assert float((full["mask"].sum(dim=1) - 1).abs().max()) <= 1e-5
+    alone = e.forward_frames(cuda({k: v[5:6] for k, v in kp_d.items()}), cuda(kp_s))["prediction"]
+    assert float((alone[0] - full["prediction"][5]).abs().max()) <= 2e-5
+    _against_oracle("num_kp 15, 512x512 x 8 vs oracle (frame 6)", full, [6], cfg, sd, src, kp_s, kp_d)
+
+
 def test_batch8_512_matches_oracle():
     """BASELINE config 5 size (512x512, batch 8): every output key of two of the eight frames against the CPU oracle at
     the batch-8 launch geometry, the reference fixture's frame inside the batch, and frame independence."""
