@@ -1,6 +1,7 @@
 // The operator entries of the C ABI (eamm_op_*, include/eamm_hip.h): each runs ONE kernel family of the path -- or one
 // operator of the differentiable training graph -- on caller-provided device buffers, without a handle.
 #include "eamm_ctx.h"
+#include <algorithm>
 #include <mutex>
 
 namespace {
@@ -588,6 +589,38 @@ int eamm_op_motion_head_backward(int device, const float* mask, const float* occ
     hipError_t e = motion_head_backward_launch(mask, occlusion, records, n, K, h, w, grad_mask, grad_deformation, grad_occlusion,
                                                grad_mask_logits, ld, grad_occlusion_logits, ldo, grad_records, workspace, s);
     OP_DONE(e, "eamm_op_motion_head_backward");
+}
+
+// ---- the key-point heads' reduction as a differentiable operator (motion.hip forward kernels, kp_head_backward.hip) -----------------
+size_t eamm_op_kp_head_workspace_floats(int B, int K) {
+    if (B < 1 || K < 1) return 0;
+    return std::max(kp_head_workspace_floats(B, K), kp_head_backward_workspace_floats(B, K));
+}
+
+int eamm_op_kp_head(int device, const float* logits, int B, int K, int njm, int h, int w, int Cs, int pad, float temperature, float* value,
+                    float* jacobian, float* heatmap, float* stats, float* workspace, size_t workspace_floats, void* stream_) {
+    OP_ENTRY(!logits || !value || !workspace || B < 1 || B > 65535 || K < 1 || (njm != 0 && njm != 1 && njm != K) || h < 1 || w < 1 ||
+                     Cs < K + 4 * njm || pad < 0 || pad > 3 || h - 6 + 2 * pad < 1 || w - 6 + 2 * pad < 1 || !(temperature > 0.f) ||
+                     workspace_floats < eamm_op_kp_head_workspace_floats(B, K),
+                 "eamm_op_kp_head: bad argument (njm 0 | 1 | K, Cs >= K + 4 njm, a window of at least 1 x 1, workspace of "
+                 "eamm_op_kp_head_workspace_floats)");
+    hipError_t e = kp_head_launch(logits, B, K, njm, h, w, Cs, pad, temperature, value, njm > 0 ? jacobian : nullptr, heatmap, s, workspace, stats);
+    OP_DONE(e, "eamm_op_kp_head");
+}
+
+int eamm_op_kp_head_backward(int device, const float* logits, const float* stats, const float* value, const float* jacobian,
+                             const float* g_value, const float* g_jacobian, const float* g_heatmap, int B, int K, int njm, int h, int w, int Cs,
+                             int pad, float temperature, float* grad_logits, float* workspace, size_t workspace_floats, void* stream_) {
+    OP_ENTRY(!logits || !stats || !value || !grad_logits || !workspace || B < 1 || B > 65535 || K < 1 || (njm != 0 && njm != 1 && njm != K) ||
+                     h < 1 || w < 1 || Cs < K + 4 * njm || (Cs & 3) || pad < 0 || pad > 3 || h - 6 + 2 * pad < 1 || w - 6 + 2 * pad < 1 ||
+                     !(temperature > 0.f) || (njm > 0 && g_jacobian && !jacobian) || (long long)B * h * w * Cs >= (1ll << 31) ||
+                     (reinterpret_cast<uintptr_t>(logits) & 15) || (reinterpret_cast<uintptr_t>(grad_logits) & 15) ||
+                     workspace_floats < eamm_op_kp_head_workspace_floats(B, K),
+                 "eamm_op_kp_head_backward: bad argument (njm 0 | 1 | K, Cs a multiple of 4 and >= K + 4 njm, 16-byte aligned tensors of "
+                 "fewer than 2^31 floats, workspace of eamm_op_kp_head_workspace_floats)");
+    hipError_t e = kp_head_backward_launch(logits, stats, value, jacobian, g_value, g_jacobian, g_heatmap, B, K, njm, h, w, Cs, pad, temperature,
+                                           grad_logits, workspace, s);
+    OP_DONE(e, "eamm_op_kp_head_backward");
 }
 
 }  // extern "C"

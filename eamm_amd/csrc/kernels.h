@@ -202,9 +202,17 @@ hipError_t nchw_to_nhwc_pad_launch(const float* src /*[B,planes,H,W]*/, int B, i
 hipError_t kp_head_launch(const float* logits /*[B,h,w,Cs]*/, int B, int K, int njm, int h, int w, int Cs, int pad,
                           float temperature, float* value /*[B,K,2]*/, float* jacobian /*[B,K,2,2] or null*/,
                           float* heatmap /*[B,K,h-6+2pad,w-6+2pad] or null*/, hipStream_t s,
-                          float* ws = nullptr /* kp_head_workspace_floats(B, K) floats: batched calls run the pixel-sliced form */);
+                          float* ws = nullptr /* kp_head_workspace_floats(B, K) floats: batched calls run the pixel-sliced form */,
+                          float* stats = nullptr /*[B,K,2]: the softmax's (maximum, denominator), what the backward reads*/);
 constexpr int KP_HEAD_SLICES = 8;
 size_t kp_head_workspace_floats(int B, int K);
+// backward of the heads' reduction (kp_head_backward.hip): any of the three gradients may be null; grad_logits is fully written
+constexpr int KP_HEAD_BWD_SLICES = 32;
+size_t kp_head_backward_workspace_floats(int B, int K);
+hipError_t kp_head_backward_launch(const float* logits /*[B,h,w,Cs]*/, const float* stats /*[B,K,2]*/, const float* value /*[B,K,2]*/,
+                                   const float* jacobian /*[B,K,2,2] or null*/, const float* g_value, const float* g_jacobian,
+                                   const float* g_heatmap, int B, int K, int njm, int h, int w, int Cs, int pad, float temperature,
+                                   float* grad_logits /*[B,h,w,Cs]*/, float* ws /* kp_head_backward_workspace_floats(B, K) */, hipStream_t s);
 // ---- training-mode BatchNorm forward (batchnorm.hip; SURVEY.md 8f row N4, first slice)
 size_t bn_workspace_floats(int N, int C, int HW);
 hipError_t bn_local_sums_launch(const float* x /*[N,C,HW]*/, int N, int C, int HW, float* sums /*[6C+2]*/, float* workspace,

@@ -676,7 +676,7 @@ __device__ __forceinline__ float block_reduce(float v, float* red, bool is_max) 
 __global__ __launch_bounds__(256) void kp_head_kernel(const float* __restrict__ logits, int K, int njm, int h, int w,
                                                       int Cs, int off, int oh, int ow, float temperature,
                                                       float* __restrict__ value, float* __restrict__ jacobian,
-                                                      float* __restrict__ heatmap) {
+                                                      float* __restrict__ heatmap, float* __restrict__ stats) {
     __shared__ float red[8];
     const int k = blockIdx.x, b = blockIdx.y;
     const int n = oh * ow;
@@ -718,6 +718,10 @@ __global__ __launch_bounds__(256) void kp_head_kernel(const float* __restrict__ 
         if (njm > 0 && jacobian) {
             float* jo = jacobian + ((size_t)b * K + k) * 4;
             jo[0] = j0 / s; jo[1] = j1 / s; jo[2] = j2 / s; jo[3] = j3 / s;
+        }
+        if (stats) {      // the softmax's maximum and denominator, for the backward (kp_head_backward.hip)
+            stats[((size_t)b * K + k) * 2 + 0] = m;
+            stats[((size_t)b * K + k) * 2 + 1] = s;
         }
     }
     if (heatmap) {
@@ -864,7 +868,7 @@ hipError_t nchw_to_nhwc_pad_launch(const float* src, int B, int C, int H, int W,
 size_t kp_head_workspace_floats(int B, int K) { return (size_t)B * K * (KP_HEAD_SLICES * 8 + 2); }
 
 hipError_t kp_head_launch(const float* logits, int B, int K, int njm, int h, int w, int Cs, int pad, float temperature,
-                          float* value, float* jacobian, float* heatmap, hipStream_t s, float* ws) {
+                          float* value, float* jacobian, float* heatmap, hipStream_t s, float* ws, float* stats_out) {
     const int off = 3 - pad, oh = h - 2 * off, ow = w - 2 * off;
     if (off < 0 || oh < 1 || ow < 1) return hipErrorInvalidValue;
     // batched calls with a workspace: pixel slices over the whole chip + a combine step (round 6, kp_head_slice_kernel above).  Few images
@@ -874,7 +878,7 @@ hipError_t kp_head_launch(const float* logits, int B, int K, int njm, int h, int
         constexpr int KG = 10;
         const int S = KP_HEAD_SLICES;
         float* part = ws;
-        float* stats = ws + (size_t)B * K * S * 8;
+        float* stats = stats_out ? stats_out : ws + (size_t)B * K * S * 8;
         hipLaunchKernelGGL(kp_head_slice_kernel<KG>, dim3(B, S, (K + KG - 1) / KG), dim3(256), 0, s, logits, K, njm, h, w, Cs, off, oh, ow,
                            temperature, S, part);
         hipLaunchKernelGGL(kp_head_combine_kernel, dim3(B), dim3(64), 0, s, part, K, njm, S, value, jacobian, stats);
@@ -883,7 +887,7 @@ hipError_t kp_head_launch(const float* logits, int B, int K, int njm, int h, int
         return hipGetLastError();
     }
     hipLaunchKernelGGL(kp_head_kernel, dim3(K, B), dim3(256), 0, s, logits, K, njm, h, w, Cs, off, oh, ow, temperature,
-                       value, jacobian, heatmap);
+                       value, jacobian, heatmap, stats_out);
     return hipGetLastError();
 }
 

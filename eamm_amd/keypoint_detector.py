@@ -7,6 +7,15 @@ anti-alias down-sampling + hourglass + heads (once per clip on the source, demo.
 forward(feature_map)`` runs only the heads on the audio-driven feature map (once per frame, demo.py:219) -- its
 ``predictor`` hourglass is part of the checkpoint but unused by the reference's forward, and here too.
 The sub-modules only hold parameters; there is no PyTorch fallback.
+
+Training.  The parameters are frozen at construction, and a frozen detector in ``.eval()`` runs the graph-free inference engine.
+``mod.requires_grad_(True)`` opts into training (reference modules/model.py:187-279 trains ``kp_extractor_a`` against
+``kp_extractor``; ``GeneratorFullModel`` back-propagates the reconstruction loss into the detector): ``forward`` is
+differentiable exactly when gradients are enabled and the input or a parameter requires one, or when the module is in
+``.train()`` -- the rule of ``OcclusionAwareGenerator.forward``.  It is then the composition of differentiable HIP operators:
+``motion_ops.antialias_down``, ``train_graph._Graph.hourglass`` (convolutions and BatchNorm + ReLU, batch statistics and
+running-statistics updates in ``.train()``, running statistics in ``.eval()``), ONE 7x7 convolution with the ``kp`` and
+``jacobian`` filters stacked, and ``kp_ops.kp_head`` (softmax / soft-argmax / jacobian reduction, HIP forward and backward).
 """
 from __future__ import annotations
 
@@ -23,7 +32,7 @@ from .weights import hourglass_channels
 
 
 def _refuse_silent_detach(mod: nn.Module, x: torch.Tensor):
-    """These modules are inference-only (no backward kernels: SURVEY.md 8f N1 / N3 are forward rows; their parameters are
+    """For the modules that are inference-only (no backward kernels: SURVEY.md 8f N1 / N3 are forward rows; their parameters are
     frozen at construction).  If the caller nevertheless asks for a gradient -- gradients enabled and the input or a
     re-enabled parameter requires one -- the reference would return a differentiable tensor; returning a detached one
     would silently train nothing, so refuse instead."""
@@ -66,7 +75,10 @@ class _KPBase(nn.Module):
         self.max_batch = int(max_batch)
         self._ctx: Optional[C.c_void_p] = None
         self._key = None
-        for p in self.parameters():
+        # what train_graph._Graph reads for the BatchNorms' replicas (as OcclusionAwareGenerator: None = one process's statistics)
+        self.process_group = None
+        self.sync_batchnorm: Optional[bool] = None
+        for p in self.parameters():          # frozen: training is opted into with mod.requires_grad_(True)
             p.requires_grad_(False)
 
     # -- handle management ----------------------------------------------------------------------------------
@@ -115,6 +127,31 @@ class _KPBase(nn.Module):
             _lib.check(L.eamm_kp_finalize_weights(ctx), ctx, kp=True)
         self._key = key
 
+    # -- differentiable path --------------------------------------------------------------------------------
+    def _wants_graph(self, x: torch.Tensor) -> bool:
+        """OcclusionAwareGenerator.forward's rule: ``.train()`` (batch statistics are the training composition's, with or without
+        gradients), or gradients enabled and the input or a parameter requiring one."""
+        if self.training:
+            return True
+        return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
+
+    def _heads_graph(self, feat_nhwc: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """keypoint_detector.py:86-103 on NHWC features: the ``kp`` and ``jacobian`` 7x7 convolutions read the same features, so they
+        run as ONE "same"-padded convolution with the filters stacked (as the flow head's mask + occlusion in ``train_graph``; autograd
+        splits the stacked gradient back onto the two modules); ``pad`` only moves the window ``kp_head`` reads."""
+        from . import kp_ops, train_graph
+        k = self._cfg["num_kp"]
+        njm = self.num_jacobian_maps if self.jacobian is not None else 0
+        w, b = self.kp.weight, self.kp.bias
+        if njm:
+            w, b = torch.cat([w, self.jacobian.weight], dim=0), torch.cat([b, self.jacobian.bias])
+        logits = train_graph.conv_wb(feat_nhwc, w, b, keep_padded=True)
+        return kp_ops.kp_head(logits, k, njm, self._cfg["pad"], self.temperature, want_heatmap=self._want_heatmap)
+
+    def _need_gpu(self, x: torch.Tensor):
+        if self.kp.weight.device.type != "cuda" or x.device.type != "cuda":
+            raise RuntimeError(f"eamm_amd.{type(self).__name__} runs only on a ROCm GPU (no CPU fallback): call .cuda()")
+
     _want_heatmap = True      # detect(..., heatmap=False) clears it for one call: the clip harness never reads the heat-maps (demo.py:219-281)
 
     def detect(self, x, heatmap: bool = True) -> Dict[str, torch.Tensor]:
@@ -154,14 +191,33 @@ class KPDetector(_KPBase):
                          estimate_jacobian, scale_factor, single_jacobian_map, pad, None, max_batch)
 
     def forward(self, x: torch.Tensor) -> Dict[str, torch.Tensor]:
-        _refuse_silent_detach(self, x)
+        """A frozen detector in ``.eval()`` (the state after construction) runs the inference engine and returns tensors without
+        a graph.  After ``requires_grad_(True)`` (or with an input that requires a gradient, or in ``.train()``) the outputs carry
+        an autograd graph through HIP operators, as the reference module's do."""
+        if self._wants_graph(x):
+            return self._forward_graph(x)
         with torch.no_grad():
             return self._forward(x)
 
-    def _forward(self, x: torch.Tensor) -> Dict[str, torch.Tensor]:
+    def _check_image(self, x: torch.Tensor):
         nc = self._cfg["num_channels"]
         if x.dim() != 4 or x.shape[1] != nc or x.dtype != torch.float32:
             raise RuntimeError(f"expected a float32 [B,{nc},H,W] image batch, got {tuple(x.shape)} {x.dtype}")
+
+    def _forward_graph(self, x: torch.Tensor) -> Dict[str, torch.Tensor]:
+        from . import motion_ops, train_graph
+        self._check_image(x)
+        self._need_gpu(x)
+        inv = self._cfg["inv_scale"]
+        if x.shape[1] == 3 and abs(1.0 / self.scale_factor - inv) < 1e-6 and inv in (1, 4) and x.shape[2] % inv == 0 and x.shape[3] % inv == 0:
+            # NHWC [B,h,w,4] = RGB + a zero channel; the hourglass's last concatenation wants the three real ones
+            small = motion_ops.antialias_down(x, self.down.weight if self.scale_factor != 1 else None, self.scale_factor)[..., :3]
+        else:
+            small = (train_graph._antialias_down(x, self.down.weight, self.scale_factor) if self.scale_factor != 1 else x).permute(0, 2, 3, 1)
+        return self._heads_graph(train_graph._Graph(self).hourglass(small, self.predictor))
+
+    def _forward(self, x: torch.Tensor) -> Dict[str, torch.Tensor]:
+        self._check_image(x)
         b, _, hh, ww = x.shape
         self._ensure(hh, ww, b)
         inv, pad = self._cfg["inv_scale"], self._cfg["pad"]
@@ -181,9 +237,23 @@ class KPDetector_a(_KPBase):
     def forward(self, feature_map) -> Dict[str, torch.Tensor]:
         """``feature_map``: the reference's float32 [B, C, h, w] tensor, or (round 6) the ``SplitFeatureMap`` ``DeconvTail.forward_split``
         hands over (same values, the layout the heads read)."""
-        _refuse_silent_detach(self, feature_map if torch.is_tensor(feature_map) else feature_map.wide)
+        if self._wants_graph(feature_map if torch.is_tensor(feature_map) else feature_map.wide):
+            return self._forward_graph(feature_map)
         with torch.no_grad():
             return self._forward(feature_map)
+
+    def _forward_graph(self, feature_map) -> Dict[str, torch.Tensor]:
+        """The heads on the given feature map with an autograd graph (the unused ``predictor`` gets no gradient, as in the reference)."""
+        if not torch.is_tensor(feature_map) and hasattr(feature_map, "to_nchw"):
+            feature_map = feature_map.to_nchw()
+        self._check_features(feature_map)
+        self._need_gpu(feature_map)
+        return self._heads_graph(feature_map.permute(0, 2, 3, 1))
+
+    def _check_features(self, feature_map):
+        if feature_map.dim() != 4 or feature_map.shape[1] != self.out_filters or feature_map.dtype != torch.float32:
+            raise RuntimeError(f"expected a float32 [B,{self.out_filters},h,w] feature map, got "
+                               f"{tuple(feature_map.shape)} {feature_map.dtype}")
 
     def accepts_split(self, height: int, width: int, batch: int = 1) -> int:
         """``wide`` channel count of the split feature map these heads read directly (``DeconvTail.forward_split``), 0 if they do
@@ -195,9 +265,7 @@ class KPDetector_a(_KPBase):
     def _forward(self, feature_map) -> Dict[str, torch.Tensor]:
         if not torch.is_tensor(feature_map) and hasattr(feature_map, "wide") and hasattr(feature_map, "thin"):
             return self._forward_split(feature_map)
-        if feature_map.dim() != 4 or feature_map.shape[1] != self.out_filters or feature_map.dtype != torch.float32:
-            raise RuntimeError(f"expected a float32 [B,{self.out_filters},h,w] feature map, got "
-                               f"{tuple(feature_map.shape)} {feature_map.dtype}")
+        self._check_features(feature_map)
         b, _, h, w = feature_map.shape
         inv, pad = self._cfg["inv_scale"], self._cfg["pad"]
         self._ensure(h * inv, w * inv, b)

@@ -675,6 +675,33 @@ int eamm_op_motion_head_backward(int device, const float* mask, const float* occ
                                  float* grad_mask_logits, int ld, float* grad_occlusion_logits, int ldo, float* grad_records,
                                  float* workspace, size_t workspace_floats, void* stream);
 
+/*
+ * The key-point heads' reduction as a DIFFERENTIABLE operator (reference modules/keypoint_detector.py:77-105 / :180-205): the
+ * forward is the detectors' own kernels (motion.hip), the backward is kp_head_backward.hip.  Device pointers; asynchronous on `stream`.
+ *   eamm_op_kp_head            logits NHWC [B,h,w,Cs] = the "same"-padded 7x7 convolution's output with the `kp` and `jacobian` filters
+ *                              stacked: channel k is key point k's logit, channel K + 4 m + c entry c of jacobian map m (njm = 0, 1 or
+ *                              K maps).  The reference convolves with padding `pad`: only the window [off, off + oh) x [off, off + ow),
+ *                              off = 3 - pad, oh = h - 2 off, ow = w - 2 off, exists.  heatmap = softmax(logit / temperature) over the
+ *                              window [B,K,oh,ow] (or NULL), value = sum heatmap * grid [B,K,2], jacobian = sum heatmap * map
+ *                              [B,K,2,2] (or NULL), stats [B,K,2] (or NULL) = the softmax's (maximum, denominator), kept for the backward.
+ *                              Always the pixel-sliced kernels with B >= 8, one workgroup per (image, key point) below, as the
+ *                              detectors' inference calls: the same bits.
+ *   eamm_op_kp_head_backward   g_value [B,K,2], g_jacobian [B,K,2,2], g_heatmap [B,K,oh,ow] (any may be NULL) -> grad_logits
+ *                              [B,h,w,Cs], FULLY written: zeros outside the window and in the channels >= K + 4 njm.  With p the
+ *                              heat-map and a_i = g_value . grid_i + sum_c g_jacobian[c] J_c,i + g_heatmap_i:
+ *                                  dL/dl_i = p_i (a_i - sum_j p_j a_j) / temperature,   dL/dJ_c,i = g_jacobian[c] p_i
+ *                              (njm = 1: summed over the key points in their order); sum_j p_j a_j = g_value . value +
+ *                              g_jacobian . jacobian + sum_j p_j g_heatmap_j, the last term summed over pixel slices in a fixed
+ *                              order (deterministic, no float atomics).  Cs a multiple of 4, 16-byte aligned tensors.
+ * `workspace`: eamm_op_kp_head_workspace_floats(B, K) floats, for either call.
+ */
+size_t eamm_op_kp_head_workspace_floats(int B, int K);
+int eamm_op_kp_head(int device, const float* logits, int B, int K, int njm, int h, int w, int Cs, int pad, float temperature, float* value,
+                    float* jacobian, float* heatmap, float* stats, float* workspace, size_t workspace_floats, void* stream);
+int eamm_op_kp_head_backward(int device, const float* logits, const float* stats, const float* value, const float* jacobian,
+                             const float* g_value, const float* g_jacobian, const float* g_heatmap, int B, int K, int njm, int h, int w, int Cs,
+                             int pad, float temperature, float* grad_logits, float* workspace, size_t workspace_floats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
