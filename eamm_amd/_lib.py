@@ -75,15 +75,15 @@ class EammEmoOutputs(C.Structure):
     _fields_ = [("value", C.c_void_p), ("jacobian", C.c_void_p), ("fake", C.c_void_p), ("feature", C.c_void_p)]
 
 
+# The handle families, by symbol prefix, with the config struct their create takes.  All five share one lifecycle (api_common.h
+# on the library's side, _handle.Handle on this one): <prefix>create / load_tensor / finalize_weights / last_error / destroy.
+FAMILIES = {"eamm_": EammConfig, "eamm_kp_": EammKpConfig, "eamm_emo_": EammEmoConfig, "eamm_audio_": EammAudioConfig,
+            "eamm_deconv_": EammDeconvConfig}
+
 # name -> (restype, argtypes); kept in one table so tests can check that every symbol declared in
 # include/eamm_hip.h is exported and bound.
 SIGNATURES = {
     "eamm_abi_version": (C.c_int, []),
-    "eamm_create": (C.c_int, [C.POINTER(EammConfig), C.c_int, C.POINTER(C.c_void_p)]),
-    "eamm_destroy": (None, [C.c_void_p]),
-    "eamm_last_error": (C.c_char_p, [C.c_void_p]),
-    "eamm_load_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
-    "eamm_finalize_weights": (C.c_int, [C.c_void_p]),
     "eamm_encode_source": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "eamm_forward_frames": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.POINTER(EammOutputs), C.c_void_p]),
@@ -111,34 +111,14 @@ SIGNATURES = {
     "eamm_knobs_json": (C.c_int, [C.c_char_p, C.c_int]),
     "eamm_build_experiments": (C.c_int, []),
     "eamm_total_mfma_flops": (C.c_double, []),
-    "eamm_kp_create": (C.c_int, [C.POINTER(EammKpConfig), C.c_int, C.POINTER(C.c_void_p)]),
-    "eamm_kp_destroy": (None, [C.c_void_p]),
-    "eamm_kp_last_error": (C.c_char_p, [C.c_void_p]),
-    "eamm_kp_load_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
-    "eamm_kp_finalize_weights": (C.c_int, [C.c_void_p]),
     "eamm_kp_detect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(EammKpOutputs), C.c_void_p]),
     "eamm_kp_detect_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(EammKpOutputs), C.c_void_p]),
     "eamm_kp_split_channels": (C.c_int, [C.c_void_p]),
     "eamm_kp_detect_features_split": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(EammKpOutputs), C.c_void_p]),
-    "eamm_emo_create": (C.c_int, [C.POINTER(EammEmoConfig), C.c_int, C.POINTER(C.c_void_p)]),
-    "eamm_emo_destroy": (None, [C.c_void_p]),
-    "eamm_emo_last_error": (C.c_char_p, [C.c_void_p]),
-    "eamm_emo_load_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
-    "eamm_emo_finalize_weights": (C.c_int, [C.c_void_p]),
-    "eamm_audio_create": (C.c_int, [C.POINTER(EammAudioConfig), C.c_int, C.POINTER(C.c_void_p)]),
-    "eamm_audio_destroy": (None, [C.c_void_p]),
-    "eamm_audio_last_error": (C.c_char_p, [C.c_void_p]),
-    "eamm_audio_load_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
-    "eamm_audio_finalize_weights": (C.c_int, [C.c_void_p]),
     "eamm_audio_lstm_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "eamm_audio_check": (C.c_int, [C.c_void_p, C.c_void_p]),
     "eamm_emo_detect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(EammEmoOutputs), C.c_void_p]),
-    "eamm_deconv_create": (C.c_int, [C.POINTER(EammDeconvConfig), C.c_int, C.POINTER(C.c_void_p)]),
-    "eamm_deconv_destroy": (None, [C.c_void_p]),
-    "eamm_deconv_last_error": (C.c_char_p, [C.c_void_p]),
-    "eamm_deconv_load_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
-    "eamm_deconv_finalize_weights": (C.c_int, [C.c_void_p]),
     "eamm_deconv_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "eamm_deconv_split_channels": (C.c_int, [C.c_void_p]),
     "eamm_deconv_forward_split": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -218,6 +198,14 @@ SIGNATURES = {
     "eamm_op_conv_wgrad_saved": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
+for _prefix, _config in FAMILIES.items():
+    SIGNATURES.update({
+        _prefix + "create": (C.c_int, [C.POINTER(_config), C.c_int, C.POINTER(C.c_void_p)]),
+        _prefix + "destroy": (None, [C.c_void_p]),
+        _prefix + "last_error": (C.c_char_p, [C.c_void_p]),
+        _prefix + "load_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
+        _prefix + "finalize_weights": (C.c_int, [C.c_void_p]),
+    })
 
 _lib = None
 
@@ -250,8 +238,9 @@ def lib() -> C.CDLL:
     return _lib
 
 
-def check(code: int, ctx=None, kp: bool = False, deconv: bool = False, emo: bool = False, audio: bool = False):
+def check(code: int, ctx=None):
+    """For the generator handle and the handle-less eamm_op_* entries (both report through eamm_last_error); the other families'
+    handles are checked by their ``_handle.Handle``."""
     if code != EAMM_OK:
-        msg = (lib().eamm_audio_last_error if audio else lib().eamm_emo_last_error if emo else lib().eamm_deconv_last_error if deconv else lib().eamm_kp_last_error if kp
-               else lib().eamm_last_error)(ctx)
+        msg = lib().eamm_last_error(ctx)
         raise EammError(code, msg.decode() if msg else "?")

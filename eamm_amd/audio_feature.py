@@ -10,15 +10,14 @@ strict load works).  The sub-modules only hold parameters; there is no PyTorch f
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, Optional
 
 import torch
 from torch import nn
 
 from . import _lib
+from ._handle import HandleOwner, ptr, refuse_silent_detach, stream_ptr, weights_key
 from .deconv_tail import DeconvTail
-from .keypoint_detector import _refuse_silent_detach
 from .weights import AUDIO_DOWN_CHANNELS, _stylegan2_spec
 
 MAX_CLIPS = 8
@@ -60,8 +59,9 @@ def _holder(prefix: str, spec) -> nn.Module:
     return root
 
 
-class AudioFeatureNet(nn.Module):
+class AudioFeatureNet(HandleOwner, nn.Module):
     """reference util.py:514 ``AT_net2`` (forward = util.py:578-612), inference only, ``jaco_net='cnn'``."""
+    _prefix = "eamm_audio_"
 
     def __init__(self, max_batch: int = 256):
         super().__init__()
@@ -78,51 +78,24 @@ class AudioFeatureNet(nn.Module):
         if not 8 <= int(max_batch) <= 4096:
             raise ValueError(f"AudioFeatureNet: max_batch must be 8 .. 4096 (got {max_batch})")
         self.max_batch = int(max_batch)
-        self._ctx: Optional[C.c_void_p] = None
-        self._key = None
         for p in self.parameters():
             p.requires_grad_(False)
 
     # -- handle management ----------------------------------------------------------------------------------
-    def _close(self):
-        if self._ctx is not None:
-            _lib.lib().eamm_audio_destroy(self._ctx)
-            self._ctx = None
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self._close()
-        except Exception:
-            pass
+    def _keyed_tensors(self, dev):
+        """The entries the library reads -- all but the unused StyleGAN2 ``generator`` and ``decon`` (a ``DeconvTail`` with its own
+        handle) -- and the handle's key over them."""
+        named = [(name, t) for name, t in self.state_dict(keep_vars=True).items() if not name.startswith(("generator.", "decon."))]
+        return (dev, weights_key(t for _, t in named), self.max_batch), named
 
     def _ensure(self):
-        dev = self.lstm.weight_hh_l0.device
-        if dev.type != "cuda":
-            raise RuntimeError("eamm_amd.AudioFeatureNet runs only on a ROCm GPU (no CPU fallback): call .cuda()")
-        if self.training:
-            raise RuntimeError("inference-only: call .eval() (BatchNorm uses running statistics)")
-        sd = self.state_dict(keep_vars=True)
-        ver = tuple(t._version for k, t in sd.items() if not k.startswith(("generator.", "decon.")))
-        key = (dev, ver, self.max_batch)
-        if self._ctx is not None and self._key == key:
+        dev = self._inference_device(self.lstm.weight_hh_l0)
+        key, named = self._keyed_tensors(dev)
+        if self._has_handle(key):
             return
-        self._close()
-        L = _lib.lib()
         cs = _lib.EammAudioConfig()
         cs.max_batch = self.max_batch
-        ctx = C.c_void_p()
-        idx = dev.index if dev.index is not None else torch.cuda.current_device()
-        _lib.check(L.eamm_audio_create(C.byref(cs), idx, C.byref(ctx)), None, audio=True)
-        self._ctx = ctx
-        for name, t in sd.items():
-            if name.endswith("num_batches_tracked") or name.startswith(("generator.", "decon.")):
-                continue
-            host = t.detach().to("cpu", torch.float32).contiguous()
-            shape = (C.c_int64 * max(1, host.dim()))(*host.shape)
-            _lib.check(L.eamm_audio_load_tensor(ctx, name.encode(), C.c_void_p(host.data_ptr()), shape, host.dim()), ctx, audio=True)
-        with torch.cuda.device(dev):
-            _lib.check(L.eamm_audio_finalize_weights(ctx), ctx, audio=True)
-        self._key = key
+        self._rebuild_handle(key, self.max_batch, cs, dev, named)
 
     # -- forward ----------------------------------------------------------------------------------------------
     @staticmethod
@@ -155,7 +128,7 @@ class AudioFeatureNet(nn.Module):
 
         The call does not wait for the device.  A recurrence that timed out (a workgroup waited longer than the limit for
         another) is reported by ``check()``, which ``forward`` and ``animate_from_features`` call at their end."""
-        _refuse_silent_detach(self, example_image)
+        refuse_silent_detach(self, example_image)
         n, t = self.check_inputs(example_image, audio, pose)
         self._ensure()
         dev = self.lstm.weight_hh_l0.device
@@ -178,11 +151,9 @@ class AudioFeatureNet(nn.Module):
                 clip = torch.empty(n, 4 * HIDDEN, device=dev)
         h1 = torch.empty(3, n, HIDDEN, device=dev) if state is not None else None
         c1 = torch.empty(3, n, HIDDEN, device=dev) if state is not None else None
-        ptr = lambda x: C.c_void_p(x.data_ptr() if x is not None else None)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        with torch.no_grad(), torch.cuda.device(dev):
-            _lib.check(_lib.lib().eamm_audio_lstm_features(self._ctx, ptr(img_arg), ptr(aud), ptr(pos), n, t, float(weight), ptr(h0),
-                                                           ptr(c0), ptr(h1), ptr(c1), ptr(clip), ptr(out), stream), self._ctx, audio=True)
+        with torch.no_grad():
+            self._handle.call("lstm_features", ptr(img_arg), ptr(aud), ptr(pos), n, t, float(weight), ptr(h0), ptr(c0), ptr(h1), ptr(c1),
+                              ptr(clip), ptr(out), stream_ptr(dev))
         if state is not None:
             state["h"], state["c"], state["clip"] = h1, c1, clip
         return out
@@ -190,12 +161,8 @@ class AudioFeatureNet(nn.Module):
     def check(self):
         """Waits for the current stream and raises ``EammError`` if a recurrence of this module timed out (its results are then
         invalid, and so is every later call)."""
-        if self._ctx is None:
-            return
-        dev = self.lstm.weight_hh_l0.device
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().eamm_audio_check(self._ctx, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), self._ctx,
-                       audio=True)
+        if self._handle is not None and self._handle.ptr is not None:
+            self._handle.call("check", stream_ptr(self._handle.device))
 
     def forward(self, example_image: torch.Tensor, audio: torch.Tensor, pose: torch.Tensor, jaco_net: str, weight: float) -> torch.Tensor:
         """util.py:578-612 -> ``deco_out`` [N,T,35,64,64]."""

@@ -21,7 +21,6 @@ An energy or filter sum of exactly 0 becomes DBL_EPSILON first.
 """
 from __future__ import annotations
 
-import ctypes as C
 import wave
 
 import numpy as np
@@ -150,13 +149,13 @@ def _mfcc(w: torch.Tensor, pad: int) -> torch.Tensor:
         rows = [mfcc_reference(w[i].detach().to(torch.float64).numpy(), pad) for i in range(n)]
         return torch.from_numpy(np.stack(rows).astype(np.float32))
     from . import _lib
+    from ._handle import ptr, stream_ptr
     L = _lib.lib()
     x = w.detach().to(torch.float32).contiguous()
     F = int(L.eamm_op_mfcc_frames(S, int(pad)))
     out = torch.empty((n, F, NCEP), device=x.device, dtype=torch.float32)
     with torch.cuda.device(x.device):
-        _lib.check(L.eamm_op_mfcc(x.device.index, C.c_void_p(x.data_ptr()), S, n, S, int(pad), C.c_void_p(out.data_ptr()),
-                                  C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)), None)
+        _lib.check(L.eamm_op_mfcc(x.device.index, ptr(x), S, n, S, int(pad), ptr(out), stream_ptr(x.device)), None)
     return out
 
 

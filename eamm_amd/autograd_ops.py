@@ -23,18 +23,11 @@ from typing import Optional
 import torch
 
 from . import _lib
+from ._handle import ptr as _ptr, stream_ptr as _stream   # (under the names this module and the tests that bind raw entries use)
 
 _CONV_BK = 32   # channel granule of the implicit-GEMM loaders (conv_common.h CONV_BK)
 _NO_OFFSET = C.c_size_t(-1).value
 _SAVE_TRANSFORM = __import__("os").environ.get("EAMM_SAVE_TRANSFORM", "1") != "0"
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream(dev) -> C.c_void_p:
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 # The weight gradient of a convolution and its data gradient are independent given (x, dY).  EAMM_WGRAD_STREAM=1 runs the weight
@@ -50,7 +43,7 @@ def _wgrad_stream(dev: torch.device):
     import os
     if os.environ.get("EAMM_WGRAD_STREAM", "0") != "1" or torch.cuda.is_current_stream_capturing():
         return None
-    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
+    key = torch.cuda.current_stream(dev)      # (a Stream hashes and compares by device and handle)
     st = _SIDE_STREAMS.get(key)
     if st is None:
         st = _SIDE_STREAMS[key] = torch.cuda.Stream(device=dev)
@@ -185,10 +178,10 @@ class _Conv2dSameFunction(torch.autograd.Function):
                 if saved_work is not None:
                     v = C.c_void_p(saved_work.data_ptr() + 4 * ctx.v_offset)
                     _lib.check(L.eamm_op_conv_wgrad_saved(x.device.index, v, _ptr(grad_out), b, h, w, cin, cout, _ptr(gw), _ptr(gb),
-                                                          _ptr(work), nwork, C.c_void_p((side or cur).cuda_stream)), None)
+                                                          _ptr(work), nwork, _stream(stream=side or cur)), None)
                 else:
                     _lib.check(L.eamm_op_conv_wgrad(x.device.index, _ptr(x), _ptr(grad_out), b, h, w, cin, cout, kh, kw, _ptr(gw), _ptr(gb),
-                                                    _ptr(work), nwork, C.c_void_p((side or cur).cuda_stream)), None)
+                                                    _ptr(work), nwork, _stream(stream=side or cur)), None)
             if zero_gb:
                 gb = gb0
         if ctx.needs_input_grad[0]:

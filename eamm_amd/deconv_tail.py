@@ -10,14 +10,13 @@ fallback.
 """
 from __future__ import annotations
 
-import ctypes as C
-from typing import Optional, Sequence
+from typing import Sequence
 
 import torch
 from torch import nn
 
 from . import _lib
-from .keypoint_detector import _refuse_silent_detach
+from ._handle import HandleOwner, ptr, refuse_silent_detach, stream_ptr, weights_key
 from .weights import DECONV_CHANNELS
 
 
@@ -46,8 +45,9 @@ class SplitFeatureMap:
         return torch.cat([self.wide, self.thin[..., :3]], dim=-1).permute(0, 3, 1, 2).contiguous()
 
 
-class DeconvTail(nn.Sequential):
+class DeconvTail(HandleOwner, nn.Sequential):
     """MI355X-native stand-in for reference modules/util.py:559-576 (``AT_net2.decon``)."""
+    _prefix = "eamm_deconv_"
 
     def __init__(self, channels: Sequence[int] = DECONV_CHANNELS, max_batch: int = 64):
         layers = []
@@ -62,59 +62,22 @@ class DeconvTail(nn.Sequential):
         super().__init__(*layers)
         self.channels = tuple(int(c) for c in channels)
         self.max_batch = int(max_batch)
-        self._ctx: Optional[C.c_void_p] = None
-        self._key = None
-        self._cap = 0
         for p in self.parameters():
             p.requires_grad_(False)
 
-    def _close(self):
-        if self._ctx is not None:
-            _lib.lib().eamm_deconv_destroy(self._ctx)
-            self._ctx = None
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self._close()
-        except Exception:
-            pass
-
     def _ensure(self, batch: int):
-        dev = self[0].weight.device
-        if dev.type != "cuda":
-            raise RuntimeError("eamm_amd.DeconvTail runs only on a ROCm GPU (no CPU fallback): call .cuda()")
-        if self.training:
-            raise RuntimeError("inference-only: call .eval() (BatchNorm uses running statistics)")
-        ver = tuple(t._version for t in self.state_dict(keep_vars=True).values())
-        key = (dev, ver)
-        if self._ctx is not None and self._key == key and batch <= self._cap:
+        dev = self._inference_device(self[0].weight)
+        named = list(self.state_dict(keep_vars=True).items())
+        key = (dev, weights_key(t for _, t in named))
+        if self._has_handle(key, batch):
             return
-        self._close()
-        L = _lib.lib()
-        cs = _lib.EammDeconvConfig()
-        cs.num_layers = len(self.channels) - 1
-        for i, c in enumerate(self.channels):
-            cs.channels[i] = c
-        self._cap = max(batch, self.max_batch)
-        cs.max_batch = self._cap
-        ctx = C.c_void_p()
-        idx = dev.index if dev.index is not None else torch.cuda.current_device()
-        _lib.check(L.eamm_deconv_create(C.byref(cs), idx, C.byref(ctx)), None, deconv=True)
-        self._ctx = ctx
-        for name, t in self.state_dict().items():
-            if name.endswith("num_batches_tracked"):
-                continue
-            host = t.detach().to("cpu", torch.float32).contiguous()
-            shape = (C.c_int64 * max(1, host.dim()))(*host.shape)
-            _lib.check(L.eamm_deconv_load_tensor(ctx, name.encode(), C.c_void_p(host.data_ptr()), shape, host.dim()),
-                       ctx, deconv=True)
-        with torch.cuda.device(dev):
-            _lib.check(L.eamm_deconv_finalize_weights(ctx), ctx, deconv=True)
-        self._key = key
+        cs = _lib.EammDeconvConfig(num_layers=len(self.channels) - 1, max_batch=max(batch, self.max_batch))
+        cs.channels[:len(self.channels)] = self.channels
+        self._rebuild_handle(key, cs.max_batch, cs, dev, named)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """x: [B,C0,1,1] (the reference's call, util.py:603-607) or [B,C0]; returns [B,C_last,S,S]."""
-        _refuse_silent_detach(self, x)
+        refuse_silent_detach(self, x)
         with torch.no_grad():
             return self._forward(x)
 
@@ -124,7 +87,7 @@ class DeconvTail(nn.Sequential):
         [B,C_last,S,S] (util.py:604-607) -- both ends of that tensor live in this library, so the clip harness
         (``driving_keypoints``) skips the NCHW round trip.  Only when C_last = 32 m + 3 (the shipped 35); the values are
         those of ``forward`` bit for bit (``SplitFeatureMap.to_nchw()`` gives the reference's tensor back)."""
-        _refuse_silent_detach(self, x)
+        refuse_silent_detach(self, x)
         with torch.no_grad():
             return self._forward(x, split=True)
 
@@ -142,19 +105,14 @@ class DeconvTail(nn.Sequential):
         self._ensure(b)
         x = x.contiguous()
         side = 4 << (len(self.channels) - 2)
-        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
         if split:
             wide_c = self.split_channels()
             if not wide_c:
                 raise RuntimeError(f"forward_split needs 32 m + 3 output channels, this tail has {self.channels[-1]}")
             wide = torch.empty(b, side, side, wide_c, device=x.device)
             thin = torch.empty(b, side, side, 4, device=x.device)
-            with torch.cuda.device(x.device):
-                _lib.check(_lib.lib().eamm_deconv_forward_split(self._ctx, C.c_void_p(x.data_ptr()), b, C.c_void_p(wide.data_ptr()),
-                                                                C.c_void_p(thin.data_ptr()), stream), self._ctx, deconv=True)
+            self._handle.call("forward_split", ptr(x), b, ptr(wide), ptr(thin), stream_ptr(x.device))
             return SplitFeatureMap(wide, thin)
         out = torch.empty(b, self.channels[-1], side, side, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.lib().eamm_deconv_forward(self._ctx, C.c_void_p(x.data_ptr()), b, C.c_void_p(out.data_ptr()),
-                                                      stream), self._ctx, deconv=True)
+        self._handle.call("forward", ptr(x), b, ptr(out), stream_ptr(x.device))
         return out

@@ -9,14 +9,14 @@ Here one ``eamm_emo_detect`` call computes the trunk once for a whole batch of f
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Optional, Tuple
+from typing import Dict, Tuple
 
 import torch
 from torch import nn
 
 from . import _lib
+from ._handle import HandleOwner, ptr, refuse_silent_detach, stream_ptr, weights_key
 from .generator import _AntiAlias, _ConvNorm, _Stack
-from .keypoint_detector import _refuse_silent_detach
 from .weights import hourglass_channels
 
 NUM_KP = 10          # fc_p takes 10 x 126 embedded numbers (util.py:1251)
@@ -42,8 +42,9 @@ class _Classify(nn.Module):
         self.last_fc = nn.Linear(512, 8)   # util.py:312: eight classes, whatever Emotion_k's num_classes
 
 
-class EmotionDetector(nn.Module):
+class EmotionDetector(HandleOwner, nn.Module):
     """reference util.py:1223 ``Emotion_k`` (forward = util.py:1498-1527, feature = :1477-1496), inference only."""
+    _prefix = "eamm_emo_"
 
     def __init__(self, block_expansion, num_channels, max_features, num_blocks, scale_factor=1, num_classes=8, max_batch=64):
         super().__init__()
@@ -78,54 +79,20 @@ class EmotionDetector(nn.Module):
         self._cfg = dict(block_expansion=int(block_expansion), num_channels=int(num_channels), max_features=int(max_features),
                          num_blocks=int(num_blocks), inv_scale=inv, num_classes=8)
         self.max_batch = int(max_batch)
-        self._ctx: Optional[C.c_void_p] = None
-        self._key = None
-        self._cap = 0
         for p in self.parameters():
             p.requires_grad_(False)
 
     # -- handle management ----------------------------------------------------------------------------------
-    def _close(self):
-        if self._ctx is not None:
-            _lib.lib().eamm_emo_destroy(self._ctx)
-            self._ctx = None
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self._close()
-        except Exception:
-            pass
-
     def _ensure(self, height: int, width: int):
-        dev = self.conv1.weight.device
-        if dev.type != "cuda":
-            raise RuntimeError("eamm_amd.EmotionDetector runs only on a ROCm GPU (no CPU fallback): call .cuda()")
-        if self.training:
-            raise RuntimeError("inference-only: call .eval() (BatchNorm uses running statistics)")
-        ver = tuple(t._version for t in self.state_dict(keep_vars=True).values())
-        key = (dev, height, width, ver, self.max_batch)
-        if self._ctx is not None and self._key == key:
+        dev = self._inference_device(self.conv1.weight)
+        named = list(self.state_dict(keep_vars=True).items())
+        key = (dev, height, width, weights_key(t for _, t in named), self.max_batch)
+        if self._has_handle(key):
             return
-        self._close()
-        L = _lib.lib()
-        cs = _lib.EammEmoConfig()
-        for k, v in self._cfg.items():
-            setattr(cs, k, v)
+        cs = _lib.EammEmoConfig(**self._cfg)
         cs.height, cs.width = int(height), int(width)
-        cs.max_batch = self._cap = self.max_batch
-        ctx = C.c_void_p()
-        idx = dev.index if dev.index is not None else torch.cuda.current_device()
-        _lib.check(L.eamm_emo_create(C.byref(cs), idx, C.byref(ctx)), None, emo=True)
-        self._ctx = ctx
-        for name, t in self.state_dict().items():
-            if name.endswith("num_batches_tracked"):
-                continue
-            host = t.detach().to("cpu", torch.float32).contiguous()
-            shape = (C.c_int64 * max(1, host.dim()))(*host.shape)
-            _lib.check(L.eamm_emo_load_tensor(ctx, name.encode(), C.c_void_p(host.data_ptr()), shape, host.dim()), ctx, emo=True)
-        with torch.cuda.device(dev):
-            _lib.check(L.eamm_emo_finalize_weights(ctx), ctx, emo=True)
-        self._key = key
+        cs.max_batch = self.max_batch
+        self._rebuild_handle(key, self.max_batch, cs, dev, named)
 
     # -- forward ----------------------------------------------------------------------------------------------
     def _check_inputs(self, x, value, jacobian):
@@ -153,33 +120,28 @@ class EmotionDetector(nn.Module):
         x = x.contiguous()
         v = value.to(dev, torch.float32).contiguous() if value is not None else None
         j = jacobian.to(dev, torch.float32).contiguous() if jacobian is not None else None
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        L = _lib.lib()
         for s in range(0, b, self._cap):
             e = min(b, s + self._cap)
             o = _lib.EammEmoOutputs(**{k: t[s:e].data_ptr() for k, t in out.items()})
-            with torch.cuda.device(dev):
-                _lib.check(L.eamm_emo_detect(self._ctx, C.c_void_p(x[s:e].data_ptr()),
-                                             C.c_void_p(v[s:e].data_ptr() if v is not None else None),
-                                             C.c_void_p(j[s:e].data_ptr() if j is not None else None), e - s, C.byref(o), stream),
-                           self._ctx, emo=True)
+            self._handle.call("detect", ptr(x[s:e]), ptr(v[s:e] if v is not None else None), ptr(j[s:e] if j is not None else None),
+                              e - s, C.byref(o), stream_ptr(dev))
         return out
 
     def detect(self, x: torch.Tensor, value: torch.Tensor, jacobian: torch.Tensor) -> Dict[str, torch.Tensor]:
         """forward and feature in one pass: {'value' [B,4,2], 'jacobian' [B,4,2,2], 'fake' [B,8], 'feature' [B,512]}."""
-        _refuse_silent_detach(self, x)
+        refuse_silent_detach(self, x)
         with torch.no_grad():
             return self._detect(x, value, jacobian, ("value", "jacobian", "fake", "feature"))
 
     def forward(self, x: torch.Tensor, value: torch.Tensor, jacobian: torch.Tensor):
         """util.py:1498-1527 -> ({'value', 'jacobian'}, fake)."""
-        _refuse_silent_detach(self, x)
+        refuse_silent_detach(self, x)
         with torch.no_grad():
             out = self._detect(x, value, jacobian, ("value", "jacobian", "fake"))
         return {"value": out["value"], "jacobian": out["jacobian"]}, out["fake"]
 
     def feature(self, x: torch.Tensor) -> torch.Tensor:
         """util.py:1477-1496 -> [B,512]."""
-        _refuse_silent_detach(self, x)
+        refuse_silent_detach(self, x)
         with torch.no_grad():
             return self._detect(x, None, None, ("feature",))["feature"]

@@ -11,6 +11,7 @@ from typing import Dict, Iterable, Optional
 import torch
 
 from . import _lib
+from ._handle import Handle, ptr, stream_ptr
 
 _OUTPUT_KEYS = ("prediction", "mask", "sparse_deformed", "occlusion_map", "deformed", "deformation")
 
@@ -41,10 +42,6 @@ def config_struct(cfg: dict, height: int, width: int, max_frames: int, max_sourc
     s.height, s.width = int(height), int(width)
     s.max_frames, s.max_sources = int(max_frames), int(max_sources)
     return s
-
-
-def _dev_ptr(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 def library_knobs() -> dict:
@@ -78,15 +75,14 @@ class Engine:
         self.h, self.w = self.height // self.inv_scale, self.width // self.inv_scale
         self.has_occlusion = bool(self._cs.estimate_occlusion_map)
         self.has_motion = self._cs.dm_num_blocks > 0
-        ctx = C.c_void_p()
-        _lib.check(self._L.eamm_create(C.byref(self._cs), self.device.index, C.byref(ctx)), None)
-        self._ctx = ctx
+        self._handle = Handle("eamm_", self._cs, self.device)
+        self._ctx = self._handle.ptr     # the forward entries below bind the raw pointer themselves (one-frame latency)
         self._finalized = False
         # training-mode handle (eamm_set_training): raw convolution weights, BatchNorm as separate kernels with batch
         # statistics -- only train_forward() may be used on it
         self.training = bool(training)
         if self.training:
-            _lib.check(self._L.eamm_set_training(self._ctx, 1), self._ctx)
+            self._handle.call("set_training", 1)
         self.ns_cached = 0
         # bumped by every encode / import: lets a caller that caches "my source is the encoded one" (the module's
         # forward()) notice that somebody else (the clip pipeline) has replaced the engine's source cache since
@@ -94,31 +90,16 @@ class Engine:
 
     # -- lifecycle -------------------------------------------------------------------------------
     def close(self):
-        if getattr(self, "_ctx", None):
-            self._L.eamm_destroy(self._ctx)
-            self._ctx = None
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        self._handle.close()
+        self._ctx = None                 # (the second copy of the pointer: kept equal to self._handle.ptr here and in load_state_dict)
 
     # -- weights ---------------------------------------------------------------------------------
     def load_state_dict(self, state_dict: Dict[str, torch.Tensor]):
         """checkpoint['generator'] (reference demo.py:91) -> folded, MFMA-packed device weights."""
-        for key, t in state_dict.items():
-            if key.endswith("num_batches_tracked"):
-                continue
-            host = t.detach().to("cpu", torch.float32).contiguous()
-            shape = (C.c_int64 * max(1, host.dim()))(*host.shape)
-            _lib.check(self._L.eamm_load_tensor(self._ctx, key.encode(), C.c_void_p(host.data_ptr()), shape,
-                                                host.dim()), self._ctx)
-        with torch.cuda.device(self.device):
-            _lib.check(self._L.eamm_finalize_weights(self._ctx), self._ctx)
+        try:
+            self._handle.load(state_dict.items())
+        finally:
+            self._ctx = self._handle.ptr     # (a failed load has destroyed the handle)
         self._finalized = True
 
     # -- forward ---------------------------------------------------------------------------------
@@ -139,7 +120,7 @@ class Engine:
         src = self._check_dev(source, "source_image", (self.num_channels, self.height, self.width))
         ns = src.shape[0]
         with torch.cuda.device(self.device):
-            _lib.check(self._L.eamm_encode_source(self._ctx, _dev_ptr(src), ns, self._stream()), self._ctx)
+            _lib.check(self._L.eamm_encode_source(self._ctx, ptr(src), ns, stream_ptr(self.device)), self._ctx)
         self.ns_cached = ns
         self.cache_generation += 1
         return ns
@@ -196,9 +177,9 @@ class Engine:
         sums = torch.empty(6 * self._L.eamm_train_max_channels(self._ctx) + 2, dtype=torch.float32, device=self.device)
         nfl = C.c_int(0)
         with torch.cuda.device(self.device):
-            _lib.check(self._L.eamm_train_begin(self._ctx, _dev_ptr(src), n, _dev_ptr(kd), _dev_ptr(kdj), _dev_ptr(ks), _dev_ptr(ksj),
-                                                sites, len(names), momentum, eps, int(bool(sync)), _dev_ptr(sums), C.byref(o),
-                                                self._stream()), self._ctx)
+            _lib.check(self._L.eamm_train_begin(self._ctx, ptr(src), n, ptr(kd), ptr(kdj), ptr(ks), ptr(ksj),
+                                                sites, len(names), momentum, eps, int(bool(sync)), ptr(sums), C.byref(o),
+                                                stream_ptr(self.device)), self._ctx)
             while True:
                 rc = self._L.eamm_train_next(self._ctx, C.byref(nfl))
                 if rc < 0:
@@ -248,14 +229,14 @@ class Engine:
             res["frames_u8"] = torch.empty((n, H, W, 3), dtype=torch.uint8, device=self.device)
             o.frames_u8 = res["frames_u8"].data_ptr()
         with torch.cuda.device(self.device):
-            _lib.check(self._L.eamm_forward_frames(self._ctx, n, _dev_ptr(kd), _dev_ptr(kdj), _dev_ptr(ks),
-                                                   _dev_ptr(ksj), C.byref(o), self._stream()), self._ctx)
+            _lib.check(self._L.eamm_forward_frames(self._ctx, n, ptr(kd), ptr(kdj), ptr(ks),
+                                                   ptr(ksj), C.byref(o), stream_ptr(self.device)), self._ctx)
         return res
 
     def check_numeric(self):
         """Synchronise and raise if a singular key-point jacobian was met (torch.inverse semantics)."""
         with torch.cuda.device(self.device):
-            _lib.check(self._L.eamm_check_numeric(self._ctx, self._stream()), self._ctx)
+            _lib.check(self._L.eamm_check_numeric(self._ctx, stream_ptr(self.device)), self._ctx)
 
     # -- source cache (multi-GPU broadcast payload) -------------------------------------------------
     def source_cache_numel(self, ns: int = 1) -> int:
@@ -265,14 +246,14 @@ class Engine:
         ns = self.ns_cached if ns is None else ns
         blob = torch.empty(self.source_cache_numel(ns), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            _lib.check(self._L.eamm_export_source_cache(self._ctx, _dev_ptr(blob), ns, self._stream()), self._ctx)
+            _lib.check(self._L.eamm_export_source_cache(self._ctx, ptr(blob), ns, stream_ptr(self.device)), self._ctx)
         return blob
 
     def import_source_cache(self, blob: torch.Tensor, ns: int = 1):
         if blob.device != self.device or blob.dtype != torch.float32 or blob.numel() != self.source_cache_numel(ns):
             raise RuntimeError("source cache blob has the wrong device, dtype or size")
         with torch.cuda.device(self.device):
-            _lib.check(self._L.eamm_import_source_cache(self._ctx, _dev_ptr(blob.contiguous()), ns, self._stream()),
+            _lib.check(self._L.eamm_import_source_cache(self._ctx, ptr(blob.contiguous()), ns, stream_ptr(self.device)),
                        self._ctx)
         self.ns_cached = ns
         self.cache_generation += 1

@@ -26,23 +26,14 @@ import torch
 from torch import nn
 
 from . import _lib
+from ._handle import HandleOwner, ptr, stream_ptr, weights_key
 from .generator import _AntiAlias, _ConvNorm, _Stack
 from .weights import hourglass_channels
 
 
 
-def _refuse_silent_detach(mod: nn.Module, x: torch.Tensor):
-    """For the modules that are inference-only (no backward kernels: SURVEY.md 8f N1 / N3 are forward rows; their parameters are
-    frozen at construction).  If the caller nevertheless asks for a gradient -- gradients enabled and the input or a
-    re-enabled parameter requires one -- the reference would return a differentiable tensor; returning a detached one
-    would silently train nothing, so refuse instead."""
-    if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in mod.parameters())):
-        raise RuntimeError(f"eamm_amd.{type(mod).__name__} is inference-only (forward kernels, no backward): call it under "
-                           "torch.no_grad() / with frozen parameters and an input that does not require grad; it never "
-                           "returns a silently detached tensor")
-
-
-class _KPBase(nn.Module):
+class _KPBase(HandleOwner, nn.Module):
+    _prefix = "eamm_kp_"
     _with_predictor = True
 
     def __init__(self, block_expansion, num_kp, num_channels, max_features, num_blocks, temperature,
@@ -73,8 +64,6 @@ class _KPBase(nn.Module):
                          inv_scale=int(round(1.0 / scale_factor)), pad=int(pad))
         self.out_filters = out_filters
         self.max_batch = int(max_batch)
-        self._ctx: Optional[C.c_void_p] = None
-        self._key = None
         # what train_graph._Graph reads for the BatchNorms' replicas (as OcclusionAwareGenerator: None = one process's statistics)
         self.process_group = None
         self.sync_batchnorm: Optional[bool] = None
@@ -82,50 +71,18 @@ class _KPBase(nn.Module):
             p.requires_grad_(False)
 
     # -- handle management ----------------------------------------------------------------------------------
-    def _close(self):
-        if self._ctx is not None:
-            _lib.lib().eamm_kp_destroy(self._ctx)
-            self._ctx = None
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self._close()
-        except Exception:
-            pass
-
     def _ensure(self, height: int, width: int, batch: int):
-        dev = self.kp.weight.device
-        if dev.type != "cuda":
-            raise RuntimeError(f"eamm_amd.{type(self).__name__} runs only on a ROCm GPU (no CPU fallback): call .cuda()")
-        if self.training:
-            raise RuntimeError("inference-only: call .eval() (BatchNorm uses running statistics)")
-        ver = tuple(t._version for t in self.state_dict(keep_vars=True).values())
-        key = (dev, height, width, ver)
-        if self._ctx is not None and self._key == key and batch <= self._cap:
-            return
-        self._close()
-        L = _lib.lib()
-        cs = _lib.EammKpConfig()
-        for k, v in self._cfg.items():
-            setattr(cs, k, v)
-        cs.height, cs.width = int(height), int(width)
-        self._cap = max(batch, self.max_batch)
-        cs.max_batch = self._cap
-        cs.with_predictor = int(self._with_predictor)
-        ctx = C.c_void_p()
-        idx = dev.index if dev.index is not None else torch.cuda.current_device()
-        _lib.check(L.eamm_kp_create(C.byref(cs), idx, C.byref(ctx)), None, kp=True)
-        self._ctx = ctx
+        dev = self._inference_device(self.kp.weight)
         needed = ("kp.", "jacobian.") + (("predictor.", "down.") if self._with_predictor else ())
-        for name, t in self.state_dict().items():
-            if name.endswith("num_batches_tracked") or not name.startswith(needed):
-                continue
-            host = t.detach().to("cpu", torch.float32).contiguous()
-            shape = (C.c_int64 * max(1, host.dim()))(*host.shape)
-            _lib.check(L.eamm_kp_load_tensor(ctx, name.encode(), C.c_void_p(host.data_ptr()), shape, host.dim()), ctx, kp=True)
-        with torch.cuda.device(dev):
-            _lib.check(L.eamm_kp_finalize_weights(ctx), ctx, kp=True)
-        self._key = key
+        named = [(name, t) for name, t in self.state_dict(keep_vars=True).items() if name.startswith(needed)]
+        key = (dev, height, width, weights_key(t for _, t in named))
+        if self._has_handle(key, batch):
+            return
+        cs = _lib.EammKpConfig(**self._cfg)
+        cs.height, cs.width = int(height), int(width)
+        cs.max_batch = max(batch, self.max_batch)
+        cs.with_predictor = int(self._with_predictor)
+        self._rebuild_handle(key, cs.max_batch, cs, dev, named)
 
     # -- differentiable path --------------------------------------------------------------------------------
     def _wants_graph(self, x: torch.Tensor) -> bool:
@@ -163,20 +120,19 @@ class _KPBase(nn.Module):
         finally:
             self._want_heatmap = True
 
-    def _run(self, x: torch.Tensor, fn_name: str, hm_h: int, hm_w: int) -> Dict[str, torch.Tensor]:
-        dev, b, k = x.device, x.shape[0], self._cfg["num_kp"]
+    def _outputs(self, b: int, hm_h: int, hm_w: int, dev):
+        """The output dict of one call and the ``EammKpOutputs`` that points into it."""
+        k = self._cfg["num_kp"]
         out = {"value": torch.empty(b, k, 2, device=dev)}
-        o = _lib.EammKpOutputs(value=out["value"].data_ptr())
         if self._want_heatmap:
             out["heatmap"] = torch.empty(b, k, hm_h, hm_w, device=dev)
-            o.heatmap = out["heatmap"].data_ptr()
         if self.jacobian is not None:
             out["jacobian"] = torch.empty(b, k, 2, 2, device=dev)
-            o.jacobian = out["jacobian"].data_ptr()
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        with torch.cuda.device(dev):
-            _lib.check(getattr(_lib.lib(), fn_name)(self._ctx, C.c_void_p(x.data_ptr()), b, C.byref(o), stream),
-                       self._ctx, kp=True)
+        return out, _lib.EammKpOutputs(**{name: t.data_ptr() for name, t in out.items()})
+
+    def _run(self, x: torch.Tensor, fn_name: str, hm_h: int, hm_w: int) -> Dict[str, torch.Tensor]:
+        out, o = self._outputs(x.shape[0], hm_h, hm_w, x.device)
+        self._handle.call(fn_name, ptr(x), x.shape[0], C.byref(o), stream_ptr(x.device))
         return out
 
 
@@ -221,7 +177,7 @@ class KPDetector(_KPBase):
         b, _, hh, ww = x.shape
         self._ensure(hh, ww, b)
         inv, pad = self._cfg["inv_scale"], self._cfg["pad"]
-        return self._run(x.contiguous(), "eamm_kp_detect", hh // inv - 6 + 2 * pad, ww // inv - 6 + 2 * pad)
+        return self._run(x.contiguous(), "detect", hh // inv - 6 + 2 * pad, ww // inv - 6 + 2 * pad)
 
 
 class KPDetector_a(_KPBase):
@@ -260,7 +216,7 @@ class KPDetector_a(_KPBase):
         not run in the wide + thin form (round 6: the private NHWC hand-over).  Builds the handle for (height, width) maps."""
         inv = self._cfg["inv_scale"]
         self._ensure(height * inv, width * inv, batch)
-        return int(_lib.lib().eamm_kp_split_channels(self._ctx))
+        return int(_lib.lib().eamm_kp_split_channels(self._handle.ptr))
 
     def _forward(self, feature_map) -> Dict[str, torch.Tensor]:
         if not torch.is_tensor(feature_map) and hasattr(feature_map, "wide") and hasattr(feature_map, "thin"):
@@ -269,7 +225,7 @@ class KPDetector_a(_KPBase):
         b, _, h, w = feature_map.shape
         inv, pad = self._cfg["inv_scale"], self._cfg["pad"]
         self._ensure(h * inv, w * inv, b)
-        return self._run(feature_map.contiguous(), "eamm_kp_detect_features", h - 6 + 2 * pad, w - 6 + 2 * pad)
+        return self._run(feature_map.contiguous(), "detect_features", h - 6 + 2 * pad, w - 6 + 2 * pad)
 
     def _forward_split(self, fm) -> Dict[str, torch.Tensor]:
         b, c, h, w = fm.shape
@@ -277,20 +233,9 @@ class KPDetector_a(_KPBase):
             raise RuntimeError(f"expected a split [B,{self.out_filters},h,w] feature map, got {tuple(fm.shape)}")
         inv, pad = self._cfg["inv_scale"], self._cfg["pad"]
         self._ensure(h * inv, w * inv, b)
-        if int(_lib.lib().eamm_kp_split_channels(self._ctx)) != c - 3:
+        if int(_lib.lib().eamm_kp_split_channels(self._handle.ptr)) != c - 3:
             return self._forward(fm.to_nchw())          # heads not in the wide + thin form: the reference's tensor
         wide, thin = fm.wide.contiguous(), fm.thin.contiguous()
-        dev, k = wide.device, self._cfg["num_kp"]
-        out = {"value": torch.empty(b, k, 2, device=dev)}
-        o = _lib.EammKpOutputs(value=out["value"].data_ptr())
-        if self._want_heatmap:
-            out["heatmap"] = torch.empty(b, k, h - 6 + 2 * pad, w - 6 + 2 * pad, device=dev)
-            o.heatmap = out["heatmap"].data_ptr()
-        if self.jacobian is not None:
-            out["jacobian"] = torch.empty(b, k, 2, 2, device=dev)
-            o.jacobian = out["jacobian"].data_ptr()
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().eamm_kp_detect_features_split(self._ctx, C.c_void_p(wide.data_ptr()), C.c_void_p(thin.data_ptr()), b,
-                                                               C.byref(o), stream), self._ctx, kp=True)
+        out, o = self._outputs(b, h - 6 + 2 * pad, w - 6 + 2 * pad, wide.device)
+        self._handle.call("detect_features_split", ptr(wide), ptr(thin), b, C.byref(o), stream_ptr(wide.device))
         return out

@@ -14,7 +14,8 @@ from typing import Dict
 import torch
 
 from . import _lib
-from .autograd_ops import _need_gpu, _ptr, _stream
+from ._handle import ptr, stream_ptr
+from .autograd_ops import _need_gpu
 
 
 def _check(code):
@@ -39,8 +40,8 @@ class _KpHeadFunction(torch.autograd.Function):
         stats = new(b, k, 2)
         ws = _workspace(b, k, dev)
         with torch.cuda.device(dev):
-            _check(_lib.lib().eamm_op_kp_head(dev.index, _ptr(logits), b, k, njm, h, w, cs, pad, float(temperature), _ptr(value), _ptr(jac),
-                                              _ptr(heat), _ptr(stats), _ptr(ws), ws.numel(), _stream(dev)))
+            _check(_lib.lib().eamm_op_kp_head(dev.index, ptr(logits), b, k, njm, h, w, cs, pad, float(temperature), ptr(value), ptr(jac),
+                                              ptr(heat), ptr(stats), ptr(ws), ws.numel(), stream_ptr(dev)))
         ctx.save_for_backward(logits, stats, value, jac)
         ctx.cfg = (k, njm, pad, float(temperature))
         ctx.set_materialize_grads(False)      # an output the loss never reads has no gradient: its term is skipped, not a zero tensor
@@ -59,9 +60,9 @@ class _KpHeadFunction(torch.autograd.Function):
         grad = torch.empty_like(logits)
         ws = _workspace(b, k, dev)
         with torch.cuda.device(dev):
-            _check(_lib.lib().eamm_op_kp_head_backward(dev.index, _ptr(logits), _ptr(stats), _ptr(value), _ptr(jac), _ptr(g_value), _ptr(g_jac),
-                                                       _ptr(g_heat), b, k, njm, h, w, cs, pad, temperature, _ptr(grad), _ptr(ws), ws.numel(),
-                                                       _stream(dev)))
+            _check(_lib.lib().eamm_op_kp_head_backward(dev.index, ptr(logits), ptr(stats), ptr(value), ptr(jac), ptr(g_value), ptr(g_jac),
+                                                       ptr(g_heat), b, k, njm, h, w, cs, pad, temperature, ptr(grad), ptr(ws), ws.numel(),
+                                                       stream_ptr(dev)))
         return grad, None, None, None, None, None
 
 

@@ -15,7 +15,8 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from .autograd_ops import _need_gpu, _ptr, _stream
+from ._handle import ptr, stream_ptr
+from .autograd_ops import _need_gpu
 
 
 def _check(code):
@@ -30,8 +31,8 @@ class _AntiAliasDownFunction(torch.autograd.Function):
         b, _, hh, ww = source.shape
         small = torch.empty(b, hh // inv_scale, ww // inv_scale, 4, dtype=torch.float32, device=source.device)
         with torch.cuda.device(source.device):
-            _check(_lib.lib().eamm_op_antialias_down(source.device.index, _ptr(source), _ptr(weight), b, hh, ww, inv_scale, _ptr(small),
-                                                     _stream(source.device)))
+            _check(_lib.lib().eamm_op_antialias_down(source.device.index, ptr(source), ptr(weight), b, hh, ww, inv_scale, ptr(small),
+                                                     stream_ptr(source.device)))
         ctx.save_for_backward(weight)
         ctx.shape, ctx.inv_scale = (b, hh, ww), inv_scale
         return small
@@ -45,8 +46,8 @@ class _AntiAliasDownFunction(torch.autograd.Function):
         grad_small = grad_small.contiguous()
         grad = torch.empty(b, 3, hh, ww, dtype=torch.float32, device=grad_small.device)
         with torch.cuda.device(grad.device):
-            _check(_lib.lib().eamm_op_antialias_down_backward(grad.device.index, _ptr(grad_small), _ptr(weight), b, hh, ww, ctx.inv_scale,
-                                                              _ptr(grad), _stream(grad.device)))
+            _check(_lib.lib().eamm_op_antialias_down_backward(grad.device.index, ptr(grad_small), ptr(weight), b, hh, ww, ctx.inv_scale,
+                                                              ptr(grad), stream_ptr(grad.device)))
         return grad, None, None
 
 
@@ -75,8 +76,8 @@ class _KpRecordsFunction(torch.autograd.Function):
         rec = torch.empty(n, k, 8, dtype=torch.float32, device=kd_val.device)
         flag = torch.zeros(1, dtype=torch.int32, device=kd_val.device)
         with torch.cuda.device(kd_val.device):
-            _check(_lib.lib().eamm_op_kp_records(kd_val.device.index, _ptr(kd_val), _ptr(kd_jac), _ptr(ks_val), _ptr(ks_jac), n, k,
-                                                 _ptr(rec), _ptr(flag), _stream(kd_val.device)))
+            _check(_lib.lib().eamm_op_kp_records(kd_val.device.index, ptr(kd_val), ptr(kd_jac), ptr(ks_val), ptr(ks_jac), n, k,
+                                                 ptr(rec), ptr(flag), stream_ptr(kd_val.device)))
         # torch.inverse raises (and synchronises) on a singular matrix too -- but a host read is illegal while the stream is being
         # captured into a graph: there the flag stays on the device and backward() (or the replay's caller) reads it
         ctx.flag = None
@@ -105,8 +106,8 @@ class _KpRecordsFunction(torch.autograd.Function):
         if g_kdv is None and g_kdj is None and g_ksv is None and g_ksj is None:
             return None, None, None, None
         with torch.cuda.device(dev):
-            _check(_lib.lib().eamm_op_kp_records_backward(dev.index, _ptr(kd_jac), _ptr(ks_jac), _ptr(grad_rec), n, k, _ptr(g_kdv),
-                                                          _ptr(g_ksv), _ptr(g_kdj), _ptr(g_ksj), _stream(dev)))
+            _check(_lib.lib().eamm_op_kp_records_backward(dev.index, ptr(kd_jac), ptr(ks_jac), ptr(grad_rec), n, k, ptr(g_kdv),
+                                                          ptr(g_ksv), ptr(g_kdj), ptr(g_ksj), stream_ptr(dev)))
         return g_kdv, g_kdj, g_ksv, g_ksj
 
 
@@ -137,8 +138,8 @@ class _MotionFrontFunction(torch.autograd.Function):
         hg = torch.empty(n, h, w, cpad, dtype=torch.float32, device=dev)
         sd = torch.empty(n, k + 1, 3, h, w, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            _check(_lib.lib().eamm_op_motion_front(dev.index, _ptr(rec), _ptr(small), n, k, h, w, float(variance), cpad, _ptr(hg), _ptr(sd),
-                                                   _stream(dev)))
+            _check(_lib.lib().eamm_op_motion_front(dev.index, ptr(rec), ptr(small), n, k, h, w, float(variance), cpad, ptr(hg), ptr(sd),
+                                                   stream_ptr(dev)))
         ctx.save_for_backward(rec, small)
         ctx.variance, ctx.cpad = float(variance), cpad
         return hg, sd
@@ -157,9 +158,9 @@ class _MotionFrontFunction(torch.autograd.Function):
         g_small = torch.empty_like(small) if ctx.needs_input_grad[1] else None
         ws = _workspace(n, k, h, w, dev)
         with torch.cuda.device(dev):
-            _check(_lib.lib().eamm_op_motion_front_backward(dev.index, _ptr(rec), _ptr(small), n, k, h, w, ctx.variance, ctx.cpad,
-                                                            _ptr(grad_hg), _ptr(grad_sd), _ptr(g_small), _ptr(g_rec), _ptr(ws), ws.numel(),
-                                                            _stream(dev)))
+            _check(_lib.lib().eamm_op_motion_front_backward(dev.index, ptr(rec), ptr(small), n, k, h, w, ctx.variance, ctx.cpad,
+                                                            ptr(grad_hg), ptr(grad_sd), ptr(g_small), ptr(g_rec), ptr(ws), ws.numel(),
+                                                            stream_ptr(dev)))
         return (g_rec if ctx.needs_input_grad[0] else None), g_small, None, None
 
 
@@ -186,11 +187,11 @@ class _MotionHeadFunction(torch.autograd.Function):
         mask = torch.empty(n, k + 1, h, w, dtype=torch.float32, device=dev)
         defo = torch.empty(n, h, w, 2, dtype=torch.float32, device=dev)
         occ = torch.empty(n, h, w, dtype=torch.float32, device=dev) if (lo is not None or stacked) else None
-        lo_ptr = C.c_void_p(lm.data_ptr() + 4 * (k + 1)) if stacked else _ptr(lo)
+        lo_ptr = C.c_void_p(lm.data_ptr() + 4 * (k + 1)) if stacked else ptr(lo)
         ldo = ld if stacked else (0 if lo is None else lo.shape[3])
         with torch.cuda.device(dev):
-            _check(_lib.lib().eamm_op_motion_head(dev.index, _ptr(lm), ld, lo_ptr, ldo, _ptr(rec), n, k, h, w,
-                                                  _ptr(mask), _ptr(defo), _ptr(occ), _stream(dev)))
+            _check(_lib.lib().eamm_op_motion_head(dev.index, ptr(lm), ld, lo_ptr, ldo, ptr(rec), n, k, h, w,
+                                                  ptr(mask), ptr(defo), ptr(occ), stream_ptr(dev)))
         ctx.save_for_backward(mask, occ, rec)
         ctx.ld, ctx.ldo, ctx.stacked = ld, ldo, bool(stacked)
         return mask, defo, occ
@@ -205,13 +206,13 @@ class _MotionHeadFunction(torch.autograd.Function):
         g_mask, g_defo, g_occ = cont(g_mask), cont(g_defo), cont(g_occ)
         g_lm = torch.empty(n, h, w, ctx.ld, dtype=torch.float32, device=dev)
         g_lo = torch.empty(n, h, w, ctx.ldo, dtype=torch.float32, device=dev) if (occ is not None and not ctx.stacked) else None
-        g_lo_ptr = C.c_void_p(g_lm.data_ptr() + 4 * (k + 1)) if ctx.stacked else _ptr(g_lo)
+        g_lo_ptr = C.c_void_p(g_lm.data_ptr() + 4 * (k + 1)) if ctx.stacked else ptr(g_lo)
         g_rec = torch.empty_like(rec)
         ws = _workspace(n, k, h, w, dev)
         with torch.cuda.device(dev):
-            _check(_lib.lib().eamm_op_motion_head_backward(dev.index, _ptr(mask), _ptr(occ), _ptr(rec), n, k, h, w, _ptr(g_mask), _ptr(g_defo),
-                                                           _ptr(g_occ), _ptr(g_lm), ctx.ld, g_lo_ptr, ctx.ldo, _ptr(g_rec), _ptr(ws),
-                                                           ws.numel(), _stream(dev)))
+            _check(_lib.lib().eamm_op_motion_head_backward(dev.index, ptr(mask), ptr(occ), ptr(rec), n, k, h, w, ptr(g_mask), ptr(g_defo),
+                                                           ptr(g_occ), ptr(g_lm), ctx.ld, g_lo_ptr, ctx.ldo, ptr(g_rec), ptr(ws),
+                                                           ws.numel(), stream_ptr(dev)))
         return g_lm, g_lo, (g_rec if ctx.needs_input_grad[2] else None), None
 
 

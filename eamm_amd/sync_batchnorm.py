@@ -20,7 +20,6 @@ stay identical on all ranks without a broadcast (the reference keeps them on the
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional
 
 import torch
@@ -28,6 +27,7 @@ import torch.distributed as dist
 from torch.nn.modules.batchnorm import _BatchNorm
 
 from . import _lib
+from ._handle import ptr, stream_ptr
 
 BN_SYNC, BN_SINGLE, BN_EVAL = 0, 1, 2
 
@@ -56,8 +56,7 @@ class HipBatchNormOps:
         sums = torch.empty(6 * c + 2, dtype=torch.float32, device=x.device)   # [2C+2] exchanged floats + 2C doubles
         work = torch.empty(max(1, L.eamm_bn_workspace_floats(n, c, hw)), dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
-            _check(L.eamm_bn_local_sums(C.c_void_p(x.data_ptr()), n, c, hw, C.c_void_p(sums.data_ptr()),
-                                        C.c_void_p(work.data_ptr()), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+            _check(L.eamm_bn_local_sums(ptr(x), n, c, hw, ptr(sums), ptr(work), stream_ptr()))
         return sums
 
     def finalize(self, sums: Optional[torch.Tensor], mod: "SynchronizedBatchNorm2d", mode: int):
@@ -65,11 +64,9 @@ class HipBatchNormOps:
         mean = torch.empty(c, dtype=torch.float32, device=dev)
         scale = torch.empty(c, dtype=torch.float32, device=dev)
         inv_std = torch.empty(c, dtype=torch.float32, device=dev)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         with torch.cuda.device(dev):
             _check(_lib.lib().eamm_bn_finalize(ptr(sums), c, float(mod.eps), float(mod.momentum), mode, ptr(mod.weight),
-                                               ptr(mod.running_mean), ptr(mod.running_var), ptr(mean), ptr(scale), ptr(inv_std),
-                                               C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+                                               ptr(mod.running_mean), ptr(mod.running_var), ptr(mean), ptr(scale), ptr(inv_std), stream_ptr()))
         return mean, scale, inv_std
 
     # ---- backward: eamm_bn_backward_sums / _finalize / _apply ------------------------------------------------------
@@ -80,9 +77,7 @@ class HipBatchNormOps:
         sums = torch.empty(6 * c + 2, dtype=torch.float32, device=x.device)
         work = torch.empty(max(1, L.eamm_bn_workspace_floats(n, c, hw)), dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
-            _check(L.eamm_bn_backward_sums(C.c_void_p(x.data_ptr()), C.c_void_p(dy.data_ptr()), C.c_void_p(mean.data_ptr()), n, c, hw,
-                                           C.c_void_p(sums.data_ptr()), C.c_void_p(work.data_ptr()),
-                                           C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+            _check(L.eamm_bn_backward_sums(ptr(x), ptr(dy), ptr(mean), n, c, hw, ptr(sums), ptr(work), stream_ptr()))
         return sums
 
     def backward_finalize(self, local: torch.Tensor, reduced: torch.Tensor, inv_std: torch.Tensor, weight: Optional[torch.Tensor],
@@ -91,10 +86,9 @@ class HipBatchNormOps:
         coef = torch.empty(3 * c, dtype=torch.float32, device=inv_std.device)
         dw = torch.empty(c, dtype=torch.float32, device=inv_std.device) if want_wb else None
         db = torch.empty(c, dtype=torch.float32, device=inv_std.device) if want_wb else None
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         with torch.cuda.device(inv_std.device):
             _check(_lib.lib().eamm_bn_backward_finalize(ptr(local), ptr(reduced), c, ptr(inv_std), ptr(weight), float(eps), mode,
-                                                        ptr(dw), ptr(db), ptr(coef), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+                                                        ptr(dw), ptr(db), ptr(coef), stream_ptr()))
         return coef, dw, db
 
     def backward_apply(self, x: torch.Tensor, dy: torch.Tensor, mean: torch.Tensor, coef: torch.Tensor) -> torch.Tensor:
@@ -102,9 +96,7 @@ class HipBatchNormOps:
         hw = x.numel() // (n * c)
         dx = torch.empty_like(x)
         with torch.cuda.device(x.device):
-            _check(_lib.lib().eamm_bn_backward_apply(C.c_void_p(x.data_ptr()), C.c_void_p(dy.data_ptr()), C.c_void_p(mean.data_ptr()),
-                                                     C.c_void_p(coef.data_ptr()), n, c, hw, C.c_void_p(dx.data_ptr()),
-                                                     C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+            _check(_lib.lib().eamm_bn_backward_apply(ptr(x), ptr(dy), ptr(mean), ptr(coef), n, c, hw, ptr(dx), stream_ptr()))
         return dx
 
     def apply(self, x: torch.Tensor, mean: torch.Tensor, scale: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
@@ -112,9 +104,7 @@ class HipBatchNormOps:
         hw = x.numel() // (n * c)
         y = torch.empty_like(x)
         with torch.cuda.device(x.device):
-            _check(_lib.lib().eamm_bn_apply(C.c_void_p(x.data_ptr()), C.c_void_p(mean.data_ptr()), C.c_void_p(scale.data_ptr()),
-                                            None if bias is None else C.c_void_p(bias.data_ptr()), n, c, hw,
-                                            C.c_void_p(y.data_ptr()), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+            _check(_lib.lib().eamm_bn_apply(ptr(x), ptr(mean), ptr(scale), ptr(bias), n, c, hw, ptr(y), stream_ptr()))
         return y
 
 
@@ -175,8 +165,7 @@ class _BatchNormNHWCFunction(torch.autograd.Function):
         b, h, w, c = x.shape
         m = b * h * w
         dev = x.device
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        st = stream_ptr(dev)
         world = mod._replicas()
         parallel = world > 1 if mod.sync is None else bool(mod.sync)
         sums = torch.empty(6 * c + 2, dtype=torch.float32, device=dev)
@@ -207,8 +196,7 @@ class _BatchNormNHWCFunction(torch.autograd.Function):
         b, h, w, c = x.shape
         dev = x.device
         dy = dy.contiguous()
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        st = stream_ptr(dev)
         local = torch.empty(6 * c + 2, dtype=torch.float32, device=dev)
         work = torch.empty(max(1, L.eamm_bn_nhwc_workspace_floats(b * h * w, c)), dtype=torch.float32, device=dev)
         want_wb = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]

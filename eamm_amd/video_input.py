@@ -46,6 +46,7 @@ from typing import Optional
 import numpy as np
 import torch
 
+from ._handle import ptr, stream_ptr
 from .config import emotion_augmentation_config
 
 OUT = 256
@@ -468,14 +469,6 @@ def _device(device, frames):
     return d
 
 
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr() if t is not None else None)
-
-
 def _upload_u8(frames, dev) -> torch.Tensor:
     x = torch.from_numpy(np.ascontiguousarray(frames)) if isinstance(frames, np.ndarray) else frames
     return x.to(dev).contiguous()
@@ -493,8 +486,8 @@ def _resize_device(x: torch.Tensor) -> torch.Tensor:
     with torch.cuda.device(x.device):
         for a in range(0, n, MAX_LAUNCH):
             b = min(n, a + MAX_LAUNCH)
-            _lib.check(L.eamm_op_resize_aa(x.device.index, _ptr(x[a:b]), b - a, H, W, Ch, ty, len(wy) // 2, tx, len(wx) // 2,
-                                           _ptr(out[a:b]), _stream(x.device)), None)
+            _lib.check(L.eamm_op_resize_aa(x.device.index, ptr(x[a:b]), b - a, H, W, Ch, ty, len(wy) // 2, tx, len(wx) // 2,
+                                           ptr(out[a:b]), stream_ptr(x.device)), None)
     return out
 
 
@@ -508,8 +501,8 @@ def _warp_device(x: torch.Tensor, maps: np.ndarray, mode: int) -> torch.Tensor:
     with torch.cuda.device(x.device):
         for a in range(0, n, MAX_LAUNCH):
             b = min(n, a + MAX_LAUNCH)
-            _lib.check(L.eamm_op_similarity_warp(x.device.index, _ptr(x[a:b]), b - a, H, W, Ch, _ptr(m[a:b]), mode, _ptr(out[a:b]),
-                                                 _stream(x.device)), None)
+            _lib.check(L.eamm_op_similarity_warp(x.device.index, ptr(x[a:b]), b - a, H, W, Ch, ptr(m[a:b]), mode, ptr(out[a:b]),
+                                                 stream_ptr(x.device)), None)
     return out
 
 
@@ -636,7 +629,7 @@ class EmotionVideo:
         with torch.cuda.device(dev):
             for a in range(t0, t1, MAX_LAUNCH):
                 b = min(t1, a + MAX_LAUNCH)
-                _lib.check(L.eamm_op_emotion_augment(dev.index, _ptr(self.aligned), self.n_frames, a, b - a, int(self.draw["flip"]),
-                                                     self._rot, _ptr(self._hinv), _ptr(self._noise), self.draw.get("noise_seed", 0),
-                                                     x0, y0, w, h, _ptr(out[a - t0:b - t0]), C.c_void_p(stream.cuda_stream)), None)
+                _lib.check(L.eamm_op_emotion_augment(dev.index, ptr(self.aligned), self.n_frames, a, b - a, int(self.draw["flip"]),
+                                                     self._rot, ptr(self._hinv), ptr(self._noise), self.draw.get("noise_seed", 0),
+                                                     x0, y0, w, h, ptr(out[a - t0:b - t0]), stream_ptr(stream=stream)), None)
         return out
