@@ -465,6 +465,13 @@ __global__ __launch_bounds__(256) void conv_bias_grad_final_kernel(const float* 
 
 size_t conv_wgrad_workspace_floats(int B, int H, int W, int Cin, int Cout, int kh, int kw);
 
+hipError_t conv_wgrad_reduce_launch(const float* partial, int splits, int taps, int Mpad, int Npad, int Cout, int Cin, float* dw, hipStream_t s) {
+    const size_t total = (size_t)Cout * Cin * taps;
+    hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 65535)), dim3(256), 0, s, partial, splits,
+                       taps, Mpad, Npad, Cout, Cin, dw);
+    return hipGetLastError();
+}
+
 namespace {
 // F(3x3,4x4) form: 3x3, map sides multiples of 4, enough tiles for the GEMMs' K (EAMM_WGRAD_WINO4 = 0 turns it off)
 bool wgrad_wino4_applies(int B, int H, int W, int Cin, int Cout, int kh, int kw) {
@@ -551,9 +558,7 @@ hipError_t conv_wgrad_launch(const float* x, const float* dy, int B, int H, int 
         else if (row && kw == 3) hipLaunchKernelGGL(conv_wgrad_row_kernel<3>, grid, dim3(256), 0, s, a);
         else if (row) hipLaunchKernelGGL(conv_wgrad_row_kernel<7>, grid, dim3(256), 0, s, a);
         else hipLaunchKernelGGL(conv_wgrad_kernel<32>, grid, dim3(256), 0, s, a);
-        const size_t total = (size_t)Cout * Cin * taps;
-        hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 65535)), dim3(256), 0, s, workspace,
-                           a.splits, taps, a.mt * 64, a.nt * 64, Cout, Cin, dweight);
+        if (hipError_t e = conv_wgrad_reduce_launch(workspace, a.splits, taps, a.mt * 64, a.nt * 64, Cout, Cin, dweight, s); e != hipSuccess) return e;
     }
     if (dbias != nullptr) {
         const long long P = (long long)B * H * W;

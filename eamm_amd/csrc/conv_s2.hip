@@ -8,6 +8,9 @@
 // pixel (oy, ox) reads input pixel (2 oy + ky - KS/2, 2 ox + kx - KS/2).  The weights are pack_conv's plain image
 // ([ntiles][nchunks][BN][BK]), the epilogue (bias, residual, activation) and split-K slabs are conv_common.h's, so nothing of
 // the stride-1 kernels changes.
+//
+// This file is the FORWARD (the engine's eamm_emo_detect and, on a filter packed on the device, the differentiable operator
+// eamm_op_conv_s2); its data and weight gradients are conv_s2_backward.hip.
 #include "conv_common.h"
 
 #include <algorithm>

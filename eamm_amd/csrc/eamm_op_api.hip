@@ -623,6 +623,111 @@ int eamm_op_kp_head_backward(int device, const float* logits, const float* stats
     OP_DONE(e, "eamm_op_kp_head_backward");
 }
 
+// ---- the stride-2 convolution of Emotion_k's ResNet trunk as a differentiable operator (conv_s2.hip, conv_s2_backward.hip) ------------
+namespace {
+// forward: pack_conv's plain image + a zero bias + the split-K slabs, in 256-byte aligned sections of the caller's workspace
+struct ConvS2Plan {
+    ConvLayer L;
+    size_t packed = 0, bias = 0, partial = 0;
+};
+bool conv_s2_plan(int B, int Hin, int Win, int Cin, int Cout, int k, ConvS2Plan* P) {
+    if (!conv_s2_backward_supported(B, Hin, Win, Cin, Cout, k)) return false;
+    ConvLayer& L = P->L;
+    L.kh = L.kw = k;
+    L.C0 = Cin;
+    L.Cout = Cout;
+    L.BN = conv_tile_n(Cout);
+    L.ntiles = (Cout + L.BN - 1) / L.BN;
+    L.nchunks = k * k * (Cin / CONV_BK);
+    auto up = [](size_t n) { return (n + 63) / 64 * 64; };
+    P->packed = up(conv_packed_elems(k * k, Cin, Cout, L.BN, 1));
+    P->bias = up((size_t)L.ntiles * L.BN);
+    P->partial = up(conv_s2_partial_elems(L, B, Hin, Win));
+    return true;
+}
+}  // namespace
+
+size_t eamm_op_conv_s2_workspace_floats(int B, int Hin, int Win, int Cin, int Cout, int k) {
+    ConvS2Plan P;
+    return conv_s2_plan(B, Hin, Win, Cin, Cout, k, &P) ? P.packed + P.bias + P.partial : 0;
+}
+
+int eamm_op_conv_s2(int device, const float* x, int B, int Hin, int Win, int Cin, const float* weight, int Cout, int k, float* out,
+                    float* workspace, size_t workspace_floats, void* stream_) {
+    ConvS2Plan P;
+    OP_ENTRY(!x || !weight || !out || !workspace || !conv_s2_plan(B, Hin, Win, Cin, Cout, k, &P) ||
+                 workspace_floats < P.packed + P.bias + P.partial || (reinterpret_cast<uintptr_t>(workspace) & 15),
+             "eamm_op_conv_s2: bad argument (k 1 | 3, Hin and Win even, Cin and Cout multiples of 32, workspace of "
+             "eamm_op_conv_s2_workspace_floats, 16-byte aligned)");
+    ConvLayer& L = P.L;
+    L.w = workspace;
+    L.bias = workspace + P.packed;
+    hipError_t e = conv_pack_dev_launch(weight, Cout, Cin, k * k, L.BN, 0, L.w, s);
+    if (e == hipSuccess) e = bias_pad_dev_launch(nullptr, Cout, L.ntiles * L.BN, L.bias, s);
+    if (e == hipSuccess)
+        e = conv_s2_launch(L, x, B, Hin, Win, ACT_NONE, nullptr, out, P.partial ? workspace + P.packed + P.bias : nullptr, P.partial, s);
+    OP_DONE(e, "eamm_op_conv_s2");
+}
+
+size_t eamm_op_conv_s2_dgrad_workspace_floats(int B, int Hin, int Win, int Cin, int Cout, int k) {
+    return conv_s2_dgrad_workspace_floats(B, Hin, Win, Cin, Cout, k);
+}
+
+int eamm_op_conv_s2_dgrad(int device, const float* grad_out, int B, int Hin, int Win, int Cin, const float* weight, int Cout, int k,
+                          float* grad_x, float* workspace, size_t workspace_floats, void* stream_) {
+    const size_t need = conv_s2_dgrad_workspace_floats(B, Hin, Win, Cin, Cout, k);
+    OP_ENTRY(!grad_out || !weight || !grad_x || !workspace || need == 0 || workspace_floats < need || (reinterpret_cast<uintptr_t>(workspace) & 15),
+             "eamm_op_conv_s2_dgrad: bad argument (k 1 | 3, Hin and Win even, Cin and Cout multiples of 32, workspace of "
+             "eamm_op_conv_s2_dgrad_workspace_floats, 16-byte aligned)");
+    const hipError_t e = conv_s2_dgrad_launch(grad_out, weight, B, Hin, Win, Cin, Cout, k, grad_x, workspace, workspace_floats, s);
+    OP_DONE(e, "eamm_op_conv_s2_dgrad");
+}
+
+size_t eamm_op_conv_s2_wgrad_workspace_floats(int B, int Hin, int Win, int Cin, int Cout, int k) {
+    return conv_s2_wgrad_workspace_floats(B, Hin, Win, Cin, Cout, k);
+}
+
+int eamm_op_conv_s2_wgrad(int device, const float* x, const float* grad_out, int B, int Hin, int Win, int Cin, int Cout, int k,
+                          float* grad_weight, float* workspace, size_t workspace_floats, void* stream_) {
+    const size_t need = conv_s2_wgrad_workspace_floats(B, Hin, Win, Cin, Cout, k);
+    OP_ENTRY(!x || !grad_out || !grad_weight || !workspace || need == 0 || workspace_floats < need || (reinterpret_cast<uintptr_t>(workspace) & 15),
+             "eamm_op_conv_s2_wgrad: bad argument (k 1 | 3, Hin and Win even, Cin and Cout multiples of 32, workspace of "
+             "eamm_op_conv_s2_wgrad_workspace_floats, 16-byte aligned)");
+    const hipError_t e = conv_s2_wgrad_launch(x, grad_out, B, Hin, Win, Cin, Cout, k, grad_weight, workspace, workspace_floats, s);
+    OP_DONE(e, "eamm_op_conv_s2_wgrad");
+}
+
+// ---- Emotion_k's stem max-pool and `final` Conv1d stack as differentiable operators (emotion.hip, emotion_backward.hip) ----------------
+int eamm_op_emo_maxpool(int device, const float* x, int B, int H, int W, int C, float* out, void* stream_) {
+    OP_ENTRY(!x || !out || B < 1 || H < 2 || W < 2 || (H & 1) || (W & 1) || C < 1 || (long long)B * H * W * C >= (1ll << 31),
+             "eamm_op_emo_maxpool: bad argument (H and W even, fewer than 2^31 elements)");
+    const hipError_t e = emo_maxpool_launch(x, B, H, W, C, out, s);
+    OP_DONE(e, "eamm_op_emo_maxpool");
+}
+
+int eamm_op_emo_maxpool_backward(int device, const float* x, const float* grad_out, int B, int H, int W, int C, float* grad_x, void* stream_) {
+    OP_ENTRY(!x || !grad_out || !grad_x || B < 1 || H < 2 || W < 2 || (H & 1) || (W & 1) || C < 1 || (long long)B * H * W * C >= (1ll << 31),
+             "eamm_op_emo_maxpool_backward: bad argument (H and W even, fewer than 2^31 elements)");
+    const hipError_t e = emo_maxpool_backward_launch(x, grad_out, B, H, W, C, grad_x, s);
+    OP_DONE(e, "eamm_op_emo_maxpool_backward");
+}
+
+int eamm_op_emo_final(int device, const float* a, const float* w98, int B, float* value, float* jacobian, void* stream_) {
+    OP_ENTRY(!a || !w98 || (!value && !jacobian) || B < 1, "eamm_op_emo_final: bad argument");
+    const hipError_t e = emo_final_launch(a, w98, B, value, jacobian, s);
+    OP_DONE(e, "eamm_op_emo_final");
+}
+
+size_t eamm_op_emo_final_workspace_floats(int B) { return B < 1 ? 0 : emo_final_backward_workspace_floats(B); }
+
+int eamm_op_emo_final_backward(int device, const float* a, const float* w98, const float* g_value, const float* g_jacobian, int B,
+                               float* grad_a, float* grad_w98, float* workspace, size_t workspace_floats, void* stream_) {
+    OP_ENTRY(!a || !w98 || !grad_a || !grad_w98 || !workspace || B < 1 || workspace_floats < emo_final_backward_workspace_floats(B),
+             "eamm_op_emo_final_backward: bad argument (workspace of eamm_op_emo_final_workspace_floats)");
+    const hipError_t e = emo_final_backward_launch(a, w98, g_value, g_jacobian, B, grad_a, grad_w98, workspace, s);
+    OP_DONE(e, "eamm_op_emo_final_backward");
+}
+
 }  // extern "C"
 
 #undef OP_ENTRY

@@ -265,6 +265,8 @@ size_t conv_wgrad_workspace_floats(int B, int H, int W, int Cin, int Cout, int k
 hipError_t conv_wgrad_launch(const float* x, const float* dy, int B, int H, int W, int Cin, int Cout, int kh, int kw, float* dweight,
                              float* dbias, float* workspace, size_t workspace_floats, hipStream_t s, const float* x_transformed = nullptr);
 bool conv_wgrad_takes_transformed(int B, int H, int W, int Cin, int Cout, int kh, int kw);
+// dW [Cout,Cin,taps] = the pixel-split slabs partial[splits][taps][Mpad][Npad] added in slice order (also the stride-2 weight gradient's)
+hipError_t conv_wgrad_reduce_launch(const float* partial, int splits, int taps, int Mpad, int Npad, int Cout, int Cin, float* dw, hipStream_t s);
 
 // conv_pack_dev.hip: the packings of conv_pack_host (register-staged kernel) and wino4_pack_host from a DEVICE OIHW tensor;
 // transposed = 1 reads the forward filter [Cin][Cout][kh][kw] transposed and flipped (the data gradient's filter)
@@ -309,6 +311,25 @@ hipError_t emo_embed_launch(const float* value /*[B,10,2]*/, const float* jacobi
 hipError_t emo_linear_launch(const float* x0, int K0, const float* x1, int K1, const float* wt /*[K0+K1][O]*/, const float* bias, int O,
                              int B, int relu, float* out /*[B,O]*/, hipStream_t s);
 hipError_t emo_final_launch(const float* a /*[B,64]*/, const float* w /*98 floats*/, int B, float* value, float* jacobian, hipStream_t s);
+
+// conv_s2_backward.hip: data and weight gradient of the stride-2 convolution above from DEVICE tensors (OIHW filter [Cout,Cin,ks,ks],
+// ks 1 | 3, no bias; Hin, Win even; Cin, Cout multiples of 32).  *_workspace_floats is 0 for an unsupported shape; the data
+// gradient packs its filter into the workspace, the weight gradient keeps its pixel-split slabs there.  dx / dweight fully written.
+bool conv_s2_backward_supported(int B, int Hin, int Win, int Cin, int Cout, int ks);
+size_t conv_s2_dgrad_workspace_floats(int B, int Hin, int Win, int Cin, int Cout, int ks);
+hipError_t conv_s2_dgrad_launch(const float* dy /*[B,Hin/2,Win/2,Cout]*/, const float* weight, int B, int Hin, int Win, int Cin, int Cout,
+                                int ks, float* dx /*[B,Hin,Win,Cin]*/, float* workspace, size_t workspace_floats, hipStream_t s);
+size_t conv_s2_wgrad_workspace_floats(int B, int Hin, int Win, int Cin, int Cout, int ks);
+hipError_t conv_s2_wgrad_launch(const float* x /*[B,Hin,Win,Cin]*/, const float* dy /*[B,Hin/2,Win/2,Cout]*/, int B, int Hin, int Win, int Cin,
+                                int Cout, int ks, float* dweight /*[Cout,Cin,ks,ks]*/, float* workspace, size_t workspace_floats, hipStream_t s);
+// emotion_backward.hip: MaxPool2d(3, 2, 1) backward (the winner recomputed from the saved input, ATen's first-maximum rule) and the
+// backward of emo_final_kernel: da [B,64], dw [98] summed over the frames in their order (workspace: B * 98 floats)
+hipError_t emo_maxpool_backward_launch(const float* in /*[B,H,W,C]*/, const float* dy /*[B,H/2,W/2,C]*/, int B, int H, int W, int C,
+                                       float* dx /*[B,H,W,C]*/, hipStream_t s);
+size_t emo_final_backward_workspace_floats(int B);
+hipError_t emo_final_backward_launch(const float* a /*[B,64]*/, const float* w /*98 floats*/, const float* g_value /*[B,4,2] or null*/,
+                                     const float* g_jacobian /*[B,4,2,2] or null*/, int B, float* da /*[B,64]*/, float* dw /*[98]*/,
+                                     float* workspace, hipStream_t s);
 
 // Audio network AT_net2 (audio.hip): the first audio convolution 1 -> 64 (BatchNorm folded: w [9][64], b [64]) + ReLU from the raw
 // [F,H,W] MFCC windows to NHWC [F,H,W,64]; MaxPool2d(3, (sy, sx)) without padding on NHWC (C % 4 == 0); x *= scale.

@@ -5,13 +5,25 @@ The reference's emotional pass (``demo.py:221-228``, ``--type linear_3``) calls 
 Here one ``eamm_emo_detect`` call computes the trunk once for a whole batch of frames and returns every output
 (``detect``).  Same constructor keywords, same ``state_dict`` keys (the 223 entries of the reference, including the unused
 ``fc``, ``fc_n``, ``final_4`` and ``final_10``), same outputs.  The sub-modules only hold parameters; there is no PyTorch fallback.
+
+Training.  ``Emotion_k`` is the network the reference's second stage trains (modules/model.py:312-413: ``emo_feature(x, value,
+jacobian)`` per frame, an L1 loss on the key-point offsets and a cross-entropy on ``fake``; the gradient also reaches
+``KPDetector_a`` through ``value`` / ``jacobian``).  The parameters are frozen at construction and a frozen detector in ``.eval()``
+runs the graph-free engine; ``mod.requires_grad_(True)`` opts in.  ``forward`` is then differentiable exactly when the module is
+in ``.train()``, or gradients are enabled and the image, ``value``, ``jacobian`` or a parameter requires one -- ``KPDetector.forward``'s
+rule -- as the composition of differentiable HIP operators: ``motion_ops.antialias_down``, ``train_graph._Graph.hourglass``
+(BatchNorms following ``process_group`` / ``sync_batchnorm``), the stem convolution + BatchNorm + ``emo_ops.maxpool3s2_nhwc``, eight
+``_Graph.basic_block`` (plain ``nn.BatchNorm2d`` statistics: this process only; stride-2 convolutions ``emo_ops.conv2d_s2_nhwc``),
+and ``emo_ops.emo_final``; the linear layers, the positional embedding, the global average and the residual adds are torch-ROCm
+ops with their own autograd.  ``feature`` and ``detect`` stay the demo's inference entries.
 """
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Tuple
+from typing import Dict, Optional, Tuple
 
 import torch
+import torch.nn.functional as F
 from torch import nn
 
 from . import _lib
@@ -43,7 +55,7 @@ class _Classify(nn.Module):
 
 
 class EmotionDetector(HandleOwner, nn.Module):
-    """reference util.py:1223 ``Emotion_k`` (forward = util.py:1498-1527, feature = :1477-1496), inference only."""
+    """reference util.py:1223 ``Emotion_k`` (forward = util.py:1498-1527, feature = :1477-1496); ``feature`` / ``detect`` are inference only."""
     _prefix = "eamm_emo_"
 
     def __init__(self, block_expansion, num_channels, max_features, num_blocks, scale_factor=1, num_classes=8, max_batch=64):
@@ -79,7 +91,10 @@ class EmotionDetector(HandleOwner, nn.Module):
         self._cfg = dict(block_expansion=int(block_expansion), num_channels=int(num_channels), max_features=int(max_features),
                          num_blocks=int(num_blocks), inv_scale=inv, num_classes=8)
         self.max_batch = int(max_batch)
-        for p in self.parameters():
+        # what train_graph._Graph reads for the hourglass's BatchNorms (as KPDetector: None = one process's statistics)
+        self.process_group = None
+        self.sync_batchnorm: Optional[bool] = None
+        for p in self.parameters():          # frozen: training is opted into with mod.requires_grad_(True)
             p.requires_grad_(False)
 
     # -- handle management ----------------------------------------------------------------------------------
@@ -133,9 +148,53 @@ class EmotionDetector(HandleOwner, nn.Module):
         with torch.no_grad():
             return self._detect(x, value, jacobian, ("value", "jacobian", "fake", "feature"))
 
+    def _wants_graph(self, *inputs) -> bool:
+        """KPDetector.forward's rule: ``.train()``, or gradients enabled and an input or a parameter requiring one."""
+        if self.training:
+            return True
+        return torch.is_grad_enabled() and (any(torch.is_tensor(t) and t.requires_grad for t in inputs) or
+                                            any(p.requires_grad for p in self.parameters()))
+
+    def _forward_graph(self, x, value, jacobian):
+        """util.py:1498-1527 as a composition of differentiable operators (NHWC between them); ``.train()`` takes batch statistics
+        and updates the running ones, ``.eval()`` the running statistics."""
+        from . import emo_ops, motion_ops, train_graph
+        self._check_inputs(x, value, jacobian)
+        if value is None:
+            raise ValueError("EmotionDetector.forward needs value and jacobian")
+        if self.conv1.weight.device.type != "cuda" or x.device.type != "cuda":
+            raise RuntimeError("eamm_amd.EmotionDetector runs only on a ROCm GPU (no CPU fallback): call .cuda()")
+        g = train_graph._Graph(self)
+        inv = self._cfg["inv_scale"]
+        if x.shape[1] == 3 and inv in (1, 4) and x.shape[2] % inv == 0 and x.shape[3] % inv == 0:
+            small = motion_ops.antialias_down(x, self.down.weight if inv != 1 else None, self.scale_factor)[..., :3]
+        else:
+            small = (train_graph._antialias_down(x, self.down.weight, self.scale_factor) if inv != 1 else x).permute(0, 2, 3, 1)
+        f = g.hourglass(small, self.predictor)
+        f = g.norm(train_graph.conv(f, self.conv1, feeds_norm=g.training), self.bn1, relu=True)
+        f = emo_ops.maxpool3s2_nhwc(f)
+        for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
+            for blk in layer:
+                f = g.basic_block(f, blk)
+        out = f.mean(dim=(1, 2))                                                             # AdaptiveAvgPool2d(1): [B,512]
+        fake = F.linear(out, self.classify.last_fc.weight, self.classify.last_fc.bias)
+        d = torch.cat([value.to(out), jacobian.to(out).reshape(jacobian.shape[0], NUM_KP, 4)], dim=2)   # [B,10,6]
+        emb = torch.cat([d] + [fn(d * float(2 ** i)) for i in range(10) for fn in (torch.sin, torch.cos)], dim=-1)   # util.py:97-145
+        ner = emb.reshape(emb.shape[0], -1)
+        for i in (0, 2):
+            ner = torch.relu(F.linear(ner, self.fc_p[i].weight, self.fc_p[i].bias))
+        a = torch.cat([out, ner], dim=1)
+        for i in (0, 2, 4):
+            a = torch.relu(F.linear(a, self.fc_all[i].weight, self.fc_all[i].bias))
+        e_value, e_jacobian = emo_ops.emo_final(a, emo_ops.final_weights(self.final))
+        return {"value": e_value, "jacobian": e_jacobian}, fake
+
     def forward(self, x: torch.Tensor, value: torch.Tensor, jacobian: torch.Tensor):
-        """util.py:1498-1527 -> ({'value', 'jacobian'}, fake)."""
-        refuse_silent_detach(self, x)
+        """util.py:1498-1527 -> ({'value', 'jacobian'}, fake).  A frozen detector in ``.eval()`` (the state after construction) runs
+        the inference engine; in ``.train()``, or when gradients are enabled and the image, ``value``, ``jacobian`` or a parameter
+        requires one, the outputs carry an autograd graph through HIP operators, as the reference module's do."""
+        if self._wants_graph(x, value, jacobian):
+            return self._forward_graph(x, value, jacobian)
         with torch.no_grad():
             out = self._detect(x, value, jacobian, ("value", "jacobian", "fake"))
         return {"value": out["value"], "jacobian": out["jacobian"]}, out["fake"]

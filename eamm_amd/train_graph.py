@@ -100,13 +100,26 @@ class _Graph:
 
     def norm_relu(self, x: torch.Tensor, holder: torch.nn.BatchNorm2d, pool: bool = False) -> torch.Tensor:
         """[avgpool2x2](relu(BatchNorm(x))) in one fused operator (every BatchNorm of the generator is followed by a ReLU)."""
+        return self._norm(x, holder, True, pool, False)
+
+    def norm(self, x: torch.Tensor, holder: torch.nn.BatchNorm2d, relu: bool = False) -> torch.Tensor:
+        """[relu](BatchNorm(x)) for a holder that is a plain ``nn.BatchNorm2d`` in the reference (the ResNet trunk of Emotion_k,
+        util.py:1075-1078, :1243): this process's statistics only, whatever the replicas' settings, and ``num_batches_tracked``
+        counts the training-mode calls as ``nn.BatchNorm2d`` does.  ``relu=False``: the BatchNorm in front of a residual add."""
+        if self.training and getattr(holder, "num_batches_tracked", None) is not None:
+            holder.num_batches_tracked.add_(1)
+        return self._norm(x, holder, relu, False, True)
+
+    def _norm(self, x: torch.Tensor, holder: torch.nn.BatchNorm2d, relu: bool, pool: bool, local: bool) -> torch.Tensor:
         if x.shape[3] != holder.num_features:
             raise RuntimeError(f"expected {holder.num_features} channels, got {x.shape[3]}")
         if not self.training:
             # evaluation mode (batchnorm.py:48-53): a per-channel affine map from the running statistics -- a few element-wise
             # torch ops with their own autograd (differentiable in x, weight and bias; the statistics are buffers)
             scale = holder.weight * torch.rsqrt(holder.running_var + holder.eps)
-            y = torch.relu(x * scale + (holder.bias - holder.running_mean * scale))
+            y = x * scale + (holder.bias - holder.running_mean * scale)
+            if relu:
+                y = torch.relu(y)
             if pool:
                 b, h, w, c = y.shape
                 y = y.view(b, h // 2, 2, w // 2, 2, c).mean(dim=(2, 4))
@@ -121,11 +134,11 @@ class _Graph:
         a._parameters["weight"], a._parameters["bias"] = holder.weight, holder.bias
         a._buffers["running_mean"], a._buffers["running_var"] = holder.running_mean, holder.running_var
         a.training = True
-        a.process_group, a.sync = self.gen.process_group, self.gen.sync_batchnorm
+        a.process_group, a.sync = (None, False) if local else (self.gen.process_group, self.gen.sync_batchnorm)
         a._ops.check(x, a)
-        if a._replicas() == 1 and x.numel() // x.shape[3] <= 1:      # batchnorm.py:112
+        if (local or a._replicas() == 1) and x.numel() // x.shape[3] <= 1:      # batchnorm.py:112
             raise AssertionError("BatchNorm computes unbiased standard-deviation, which requires size > 1.")
-        return _BatchNormNHWCFunction.apply(x.contiguous(), holder.weight, holder.bias, a, True, pool)
+        return _BatchNormNHWCFunction.apply(x.contiguous(), holder.weight, holder.bias, a, relu, pool)
 
     # ---- blocks: modules/util.py:858-938 --------------------------------------------------------------------------------
     # (feeds_norm -- "the bias gradient is exactly zero" -- holds for BATCH statistics only: training mode)
@@ -142,6 +155,20 @@ class _Graph:
         y = conv(self.norm_relu(x, blk.norm1), blk.conv1, feeds_norm=self.training)      # conv1 -> norm2
         y = conv(self.norm_relu(y, blk.norm2), blk.conv2)
         return y + x
+
+    def basic_block(self, x, blk):                                 # util.py:1069-1099 (ResNet BasicBlock, plain nn.BatchNorm2d)
+        """relu(bn2(conv2(relu(bn1(conv1(x))))) + shortcut(x)); a block with a ``downsample`` halves the map: its first 3x3 and the
+        1x1 shortcut are the stride-2 operators of ``emo_ops``.  The add and the last ReLU stay torch ops with their own autograd."""
+        from . import emo_ops
+        down = getattr(blk, "downsample", None)
+        if down is not None:
+            y = emo_ops.conv2d_s2_nhwc(x, blk.conv1.weight)
+            shortcut = self.norm(emo_ops.conv2d_s2_nhwc(x, down[0].weight), down[1])
+        else:
+            y = conv(x, blk.conv1, feeds_norm=self.training)
+            shortcut = x
+        y = conv(self.norm(y, blk.bn1, relu=True), blk.conv2, feeds_norm=self.training)
+        return torch.relu(self.norm(y, blk.bn2) + shortcut)
 
     def hourglass(self, x, hg):                                    # util.py:941-1002
         skips = [x]

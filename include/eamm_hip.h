@@ -702,6 +702,50 @@ int eamm_op_kp_head_backward(int device, const float* logits, const float* stats
                              const float* g_value, const float* g_jacobian, const float* g_heatmap, int B, int K, int njm, int h, int w, int Cs,
                              int pad, float temperature, float* grad_logits, float* workspace, size_t workspace_floats, void* stream);
 
+/*
+ * The stride-2 convolution of Emotion_k's ResNet-18 trunk as a DIFFERENTIABLE operator (reference modules/util.py:1069-1099: the first
+ * 3x3 convolution of a down-sampling BasicBlock and its 1x1 `downsample` shortcut).  Additive entries (ABI 6 unchanged).  Common
+ * contract: NHWC fp32 activations, OIHW filter [Cout,Cin,k,k] ON THE DEVICE with k 1 | 3, padding k / 2, no bias; Hin and Win
+ * even; Cin and Cout multiples of 32; anything else is refused before any launch and the *_workspace_floats query returns 0.
+ * `workspace`: the query's floats, 16-byte aligned (the packed filter and the split slabs live there).  Asynchronous on `stream`.
+ *   eamm_op_conv_s2        x [B,Hin,Win,Cin] -> out [B,Hin/2,Win/2,Cout]: the emotion engine's fp32-MFMA kernel (conv_s2.hip) on a
+ *                          filter packed on the device.
+ *   eamm_op_conv_s2_dgrad  grad_out [B,Hin/2,Win/2,Cout], weight -> grad_x [B,Hin,Win,Cin], a gather: one implicit GEMM on
+ *                          v_mfma_f32_32x32x2_f32 per input-pixel parity class (1, 2, 2 or 4 of the nine taps reach a pixel; for k = 1
+ *                          only the even / even pixels).  No atomics; EVERY element is written (exact zeros where no tap reaches);
+ *                          bit-identical from run to run.
+ *   eamm_op_conv_s2_wgrad  x, grad_out -> grad_weight [Cout,Cin,k,k]: one GEMM per tap over the output pixels, split over the pixel
+ *                          range, the slabs summed in a fixed order (deterministic).
+ */
+size_t eamm_op_conv_s2_workspace_floats(int B, int Hin, int Win, int Cin, int Cout, int k);
+int eamm_op_conv_s2(int device, const float* x, int B, int Hin, int Win, int Cin, const float* weight, int Cout, int k, float* out,
+                    float* workspace, size_t workspace_floats, void* stream);
+size_t eamm_op_conv_s2_dgrad_workspace_floats(int B, int Hin, int Win, int Cin, int Cout, int k);
+int eamm_op_conv_s2_dgrad(int device, const float* grad_out, int B, int Hin, int Win, int Cin, const float* weight, int Cout, int k,
+                          float* grad_x, float* workspace, size_t workspace_floats, void* stream);
+size_t eamm_op_conv_s2_wgrad_workspace_floats(int B, int Hin, int Win, int Cin, int Cout, int k);
+int eamm_op_conv_s2_wgrad(int device, const float* x, const float* grad_out, int B, int Hin, int Win, int Cin, int Cout, int k,
+                          float* grad_weight, float* workspace, size_t workspace_floats, void* stream);
+
+/*
+ * Emotion_k's small steps as DIFFERENTIABLE operators (reference modules/util.py:1245, :1287-1295).  Device pointers; asynchronous.
+ *   eamm_op_emo_maxpool           MaxPool2d(3, 2, 1) on NHWC x [B,H,W,C] (H, W even) -> out [B,H/2,W/2,C].
+ *   eamm_op_emo_maxpool_backward  grad_x [B,H,W,C], fully written: the winner of each window is recomputed from x; the FIRST maximum
+ *                                 in (ky, kx) raster order takes the gradient (ATen's rule); each input pixel sums the up-to-four
+ *                                 windows that chose it (no atomics).
+ *   eamm_op_emo_final             the `final` stack Conv1d(1,2,4,2,1) - MaxPool1d(2,2) - ReLU - Conv1d(2,4,4,2,1) - ReLU - Conv1d(4,4,3)
+ *                                 on a [B,64] -> value [B,4,2], jacobian [B,4,2,2] (either may be NULL); w98 = the six parameter
+ *                                 tensors flattened in state_dict order (8 + 2 + 32 + 4 + 48 + 4 floats).
+ *   eamm_op_emo_final_backward    g_value, g_jacobian (either may be NULL) -> grad_a [B,64] and grad_w98 [98], summed over the frames
+ *                                 in their order; workspace: eamm_op_emo_final_workspace_floats(B) floats.
+ */
+int eamm_op_emo_maxpool(int device, const float* x, int B, int H, int W, int C, float* out, void* stream);
+int eamm_op_emo_maxpool_backward(int device, const float* x, const float* grad_out, int B, int H, int W, int C, float* grad_x, void* stream);
+int eamm_op_emo_final(int device, const float* a, const float* w98, int B, float* value, float* jacobian, void* stream);
+size_t eamm_op_emo_final_workspace_floats(int B);
+int eamm_op_emo_final_backward(int device, const float* a, const float* w98, const float* g_value, const float* g_jacobian, int B,
+                               float* grad_a, float* grad_w98, float* workspace, size_t workspace_floats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
