@@ -213,6 +213,26 @@ SIGNATURES = {
     "eamm_op_emo_final_workspace_floats": (C.c_size_t, [C.c_int]),
     "eamm_op_emo_final_backward": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_size_t, C.c_void_p]),
+    # AT_net2's LSTM layer, max-pools and ConvTranspose2d(k4, s2, p1) as differentiable operators (audio_ops.py); additive
+    "eamm_op_lstm_workspace_floats": (C.c_size_t, [C.c_int, C.c_int]),
+    "eamm_op_lstm_forward": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "eamm_op_lstm_scan": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "eamm_op_lstm_backward_workspace_floats": (C.c_size_t, [C.c_int, C.c_int]),
+    "eamm_op_lstm_backward": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                        C.c_size_t, C.c_void_p]),
+    "eamm_op_lstm_check": (C.c_int, [C.c_int, C.c_void_p]),
+    "eamm_op_audio_maxpool": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "eamm_op_audio_maxpool_backward": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                 C.c_void_p, C.c_void_p]),
+    "eamm_op_deconv4s2_workspace_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "eamm_op_deconv4s2": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                    C.c_void_p, C.c_size_t, C.c_void_p]),
+    "eamm_op_deconv4s2_dgrad_workspace_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "eamm_op_deconv4s2_dgrad": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                          C.c_void_p, C.c_size_t, C.c_void_p]),
+    "eamm_op_deconv4s2_wgrad_workspace_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "eamm_op_deconv4s2_wgrad": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 for _prefix, _config in FAMILIES.items():
     SIGNATURES.update({

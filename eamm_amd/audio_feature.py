@@ -7,12 +7,27 @@ encoder once per clip, the per-step encoders batched over ``max_batch`` frames, 
 launch.  ``decon`` is the existing ``DeconvTail`` (so ``animate_from_features(..., deconv_tail=net.decon)`` keeps working).  Same
 ``state_dict`` keys as the reference (its 235 entries, the 99 of the unused StyleGAN2 ``generator`` included, held only so that a
 strict load works).  The sub-modules only hold parameters; there is no PyTorch fallback.
+
+Training.  ``AT_net2`` is what the reference's first stage trains together with ``KPDetector_a`` (train.py ``train_part1``, an L1
+distance between the audio-driven and the image-driven key points, modules/model.py:187-221).  The parameters are frozen at
+construction and a frozen network runs the graph-free engine whatever ``.training`` says (a fresh ``nn.Module`` is in training
+mode); ``mod.requires_grad_(True)`` opts in.  ``forward`` and ``lstm_features`` then take the GRAPH ROUTE when the module is in
+``.train()``, or gradients are enabled and an input or a parameter requires one: util.py:580-614 as a composition of differentiable
+HIP operators -- ``train_graph._Graph.down_block`` eight times; per step ``train_graph.conv`` + ``_Graph.norm`` (plain
+``nn.BatchNorm2d``) + ``audio_ops.maxpool3_nhwc``; three ``audio_ops.lstm_layer`` (persistent forward and backward recurrences);
+``DeconvTail``'s graph route -- with the linear layers, the ``* weight`` scale and the LSTM's input projections as torch-ROCm ops
+with their own autograd.  In ``.train()`` every BatchNorm of ``audio_eocder`` and ``decon`` takes its batch statistics over the N
+clips of ONE step and updates its running statistics T times in step order, as the reference's per-step calls do (the
+convolutions are batched over N x T); in ``.eval()`` every BatchNorm uses its running statistics.  Under ``torch.no_grad()`` in
+``.train()`` the route is the same composition without a graph.  ``state=`` (chunked clips) is an inference feature: with the graph
+route it raises ``ValueError`` (no truncated back-propagation through time).  The op-level composition, not a tuned path.
 """
 from __future__ import annotations
 
 from typing import Dict, Optional
 
 import torch
+import torch.nn.functional as F
 from torch import nn
 
 from . import _lib
@@ -60,7 +75,7 @@ def _holder(prefix: str, spec) -> nn.Module:
 
 
 class AudioFeatureNet(HandleOwner, nn.Module):
-    """reference util.py:514 ``AT_net2`` (forward = util.py:578-612), inference only, ``jaco_net='cnn'``."""
+    """reference util.py:514 ``AT_net2`` (forward = util.py:578-612), ``jaco_net='cnn'``; trainable after ``requires_grad_(True)``."""
     _prefix = "eamm_audio_"
 
     def __init__(self, max_batch: int = 256):
@@ -78,7 +93,10 @@ class AudioFeatureNet(HandleOwner, nn.Module):
         if not 8 <= int(max_batch) <= 4096:
             raise ValueError(f"AudioFeatureNet: max_batch must be 8 .. 4096 (got {max_batch})")
         self.max_batch = int(max_batch)
-        for p in self.parameters():
+        # what train_graph._Graph reads for the image encoder's BatchNorms (as KPDetector: None = one process's statistics)
+        self.process_group = None
+        self.sync_batchnorm: Optional[bool] = None
+        for p in self.parameters():          # frozen: training is opted into with mod.requires_grad_(True)
             p.requires_grad_(False)
 
     # -- handle management ----------------------------------------------------------------------------------
@@ -128,6 +146,12 @@ class AudioFeatureNet(HandleOwner, nn.Module):
 
         The call does not wait for the device.  A recurrence that timed out (a workgroup waited longer than the limit for
         another) is reported by ``check()``, which ``forward`` and ``animate_from_features`` call at their end."""
+        if self._wants_graph(example_image, audio, pose):
+            n, t = self.check_inputs(example_image, audio, pose)
+            if state is not None:
+                raise ValueError("AudioFeatureNet: state= (chunked clips) is an inference feature; the differentiable route has no "
+                                 "truncated back-propagation through time")
+            return self._lstm_features_graph(example_image, audio, pose, weight)
         refuse_silent_detach(self, example_image)
         n, t = self.check_inputs(example_image, audio, pose)
         self._ensure()
@@ -158,11 +182,64 @@ class AudioFeatureNet(HandleOwner, nn.Module):
             state["h"], state["c"], state["clip"] = h1, c1, clip
         return out
 
+    def _wants_graph(self, *inputs) -> bool:
+        """Opted in (``requires_grad_(True)``: a parameter requires a gradient) and either in ``.train()`` or with gradients enabled
+        (the parameter requires one).  A frozen network never takes the graph route, whatever ``.training`` says."""
+        return any(p.requires_grad for p in self.parameters()) and (self.training or torch.is_grad_enabled())
+
+    def _lstm_features_graph(self, example_image, audio, pose, weight) -> torch.Tensor:
+        """util.py:580-598 as a composition of differentiable operators (NHWC between the convolutions) -> ``lstm_out`` [N,T,256]."""
+        from . import audio_ops, train_graph
+        dev = self.lstm.weight_hh_l0.device
+        if dev.type != "cuda":
+            raise RuntimeError("eamm_amd.AudioFeatureNet runs only on a ROCm GPU (no CPU fallback): call .cuda()")
+        n, t = audio.shape[:2]
+        f32 = lambda x: x.to(dev, torch.float32)
+        g = train_graph._Graph(self)
+        out = f32(example_image).permute(0, 2, 3, 1)                                    # util.py:583-587
+        for blk in self.down_blocks:
+            out = g.down_block(out, blk)
+        image_feature = out.reshape(n, -1)                                               # [N,512] (1x1 map)
+        # the per-step encoders on a TIME-MAJOR batch (row s * N + clip): the convolutions see all N * T frames at once; in
+        # .train() each BatchNorm call sees the N clips of one step, in step order (util.py:589-591 runs audio_eocder per step)
+        per_step = g.training and t > 1
+
+        def norm(y, holder):
+            if not per_step:
+                return g.norm(y, holder, relu=True)
+            return torch.cat([g.norm(y[s * n:(s + 1) * n], holder, relu=True) for s in range(t)], dim=0)
+
+        a = f32(audio).transpose(0, 1).reshape(t * n, MFCC_SHAPE[0], MFCC_SHAPE[1], 1)
+        for idx in range(7):
+            layer = self.audio_eocder[idx]
+            if isinstance(layer, nn.MaxPool2d):
+                a = audio_ops.maxpool3_nhwc(a, *layer.stride)
+            else:
+                a = norm(train_graph.conv(a, layer[0], feeds_norm=g.training), layer[1])
+        a = a.permute(0, 3, 1, 2).reshape(t * n, -1)                                     # the reference flattens NCHW [512,12,2]
+        for i in (0, 2):
+            a = torch.relu(F.linear(a, self.audio_eocder_fc[i].weight, self.audio_eocder_fc[i].bias))
+        a = a * float(weight)                                                            # util.py:593
+        pf = f32(pose).transpose(0, 1).reshape(t * n, POSE_DIM)
+        for i in (0, 2):
+            pf = torch.relu(F.linear(pf, self.pose_encoder[i].weight, self.pose_encoder[i].bias))
+        x = torch.cat([image_feature[None].expand(t, n, image_feature.shape[1]), a.view(t, n, -1), pf.view(t, n, -1)], dim=2)
+        x = x.transpose(0, 1)                                                            # [N,T,1024]: batch_first
+        for l in range(3):                                                               # util.py:598, from the zero state
+            w_ih, w_hh = getattr(self.lstm, f"weight_ih_l{l}"), getattr(self.lstm, f"weight_hh_l{l}")
+            bias = getattr(self.lstm, f"bias_ih_l{l}") + getattr(self.lstm, f"bias_hh_l{l}")
+            x = audio_ops.lstm_layer(F.linear(x, w_ih, bias), w_hh)
+        return x
+
     def check(self):
         """Waits for the current stream and raises ``EammError`` if a recurrence of this module timed out (its results are then
-        invalid, and so is every later call)."""
+        invalid, and so is every later call) -- the engine's, or an ``audio_ops.lstm_layer`` of the graph route."""
         if self._handle is not None and self._handle.ptr is not None:
             self._handle.call("check", stream_ptr(self._handle.device))
+        dev = self.lstm.weight_hh_l0.device
+        if dev.type == "cuda":
+            from . import audio_ops
+            audio_ops.lstm_check(dev)
 
     def forward(self, example_image: torch.Tensor, audio: torch.Tensor, pose: torch.Tensor, jaco_net: str, weight: float) -> torch.Tensor:
         """util.py:578-612 -> ``deco_out`` [N,T,35,64,64]."""
@@ -173,6 +250,11 @@ class AudioFeatureNet(HandleOwner, nn.Module):
             raise Exception("jaco_net type wrong")   # the reference's own error (util.py:610)
         lstm_out = self.lstm_features(example_image, audio, pose, weight)
         n, t = lstm_out.shape[:2]
+        if self._wants_graph(example_image, audio, pose):
+            # decon per step (util.py:601-607): time-major rows, so that a .train() BatchNorm call sees one step's N clips
+            deco = self.decon._forward_graph(lstm_out.transpose(0, 1).reshape(t * n, HIDDEN), steps=t)
+            self.check()
+            return deco.view(t, n, *deco.shape[1:]).transpose(0, 1)
         deco = self.decon(lstm_out.reshape(n * t, HIDDEN))
         self.check()
         return deco.view(n, t, *deco.shape[1:])

@@ -730,5 +730,198 @@ int eamm_op_emo_final_backward(int device, const float* a, const float* w98, con
 
 }  // extern "C"
 
+// ---- AT_net2's LSTM layer, max-pools and ConvTranspose2d(k4, s2, p1) as differentiable operators (audio.hip, lstm_backward.hip,
+// audio_backward.hip) ------------------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int LSTM_OP_MAXN = 8, LSTM_OP_HID = 256, LSTM_OP_GATES = 1024;
+constexpr size_t LSTM_OP_PACKED = (size_t)LSTM_WG * LSTM_OP_HID * 64;                  // lstm_rec_kernel's W_hh image
+constexpr size_t LSTM_OP_STATE = (size_t)3 * LSTM_OP_MAXN * LSTM_OP_HID;               // h0, hT, c
+constexpr size_t LSTM_OP_GRAN_F = (size_t)2 * 2 * LSTM_OP_MAXN * LSTM_OP_HID;          // [2][8][256] 8-byte words, in floats
+constexpr size_t LSTM_OP_GRAN_B = (size_t)2 * 2 * LSTM_OP_MAXN * LSTM_OP_GATES;        // [2][8][1024] 8-byte words, in floats
+
+// The operators' timeout word (pinned, device-mapped) and wall-clock limit, one per device of the process: an operator call has no
+// handle to keep them on.  Sticky, as a handle's: after a timed-out recurrence every later call and eamm_op_lstm_check fail.
+struct LstmOpState {
+    int* err_host = nullptr;
+    int* err_dev = nullptr;
+    unsigned long long limit = 0;
+};
+std::mutex g_lstm_mu;
+LstmOpState g_lstm[64];
+
+hipError_t lstm_op_state(int device, LstmOpState** out) {   // the device is selected (DeviceGuard)
+    if (device < 0 || device >= 64) return hipErrorInvalidDevice;
+    std::lock_guard<std::mutex> lock(g_lstm_mu);
+    LstmOpState& st = g_lstm[device];
+    if (!st.err_host) {
+        int* host = nullptr;
+        if (hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&host), sizeof(int), hipHostMallocMapped | hipHostMallocCoherent); e != hipSuccess)
+            return e;
+        *host = 0;
+        if (hipError_t e = hipHostGetDevicePointer(reinterpret_cast<void**>(&st.err_dev), host, 0); e != hipSuccess) {
+            (void)hipHostFree(host);
+            return e;
+        }
+        int khz = 100000;   // a wait may take 10 s of wall clock, as the audio handle's (eamm_audio_api.hip)
+        if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device) != hipSuccess || khz <= 0) khz = 100000;
+        st.limit = (unsigned long long)khz * 1000ull * 10ull;
+        st.err_host = host;
+    }
+    *out = &st;
+    return hipSuccess;
+}
+
+bool lstm_op_shape_ok(int N, int T) { return N >= 1 && N <= LSTM_OP_MAXN && T >= 1 && (long long)N * T * LSTM_OP_GATES < (1ll << 31); }
+
+const char* const kLstmTimedOut = "an LSTM operator's recurrence timed out waiting for another workgroup: its results are invalid (NaN from "
+                                  "the step it stopped at) and the LSTM operators of this device are unusable";
+
+}  // namespace
+
+extern "C" {
+
+size_t eamm_op_lstm_workspace_floats(int N, int T) { return lstm_op_shape_ok(N, T) ? LSTM_OP_PACKED + LSTM_OP_STATE + LSTM_OP_GRAN_F : 0; }
+
+int eamm_op_lstm_forward(int device, const float* xproj, const float* w_hh, int N, int T, float* y, float* workspace, size_t workspace_floats,
+                         void* stream_) {
+    OP_ENTRY(!xproj || !w_hh || !y || !workspace || !lstm_op_shape_ok(N, T) || workspace_floats < eamm_op_lstm_workspace_floats(N, T) ||
+                 (reinterpret_cast<uintptr_t>(workspace) & 15),
+             "eamm_op_lstm_forward: bad argument (1 to 8 clips, T >= 1, workspace of eamm_op_lstm_workspace_floats, 16-byte aligned)");
+    LstmOpState* st = nullptr;
+    hipError_t e = lstm_op_state(device, &st);
+    if (e == hipSuccess && __atomic_load_n(st->err_host, __ATOMIC_ACQUIRE)) return fail(nullptr, EAMM_ERR_HIP, "%s", kLstmTimedOut);
+    float* state = workspace + LSTM_OP_PACKED;
+    if (e == hipSuccess) e = lstm_pack_whh_dev_launch(w_hh, workspace, s);
+    // zero state, and a granule buffer of this call's own zeroed on the stream: tags start at 1, so no stale word can match
+    if (e == hipSuccess) e = hipMemsetAsync(state, 0, sizeof(float) * (LSTM_OP_STATE + LSTM_OP_GRAN_F), s);
+    // a timed-out workgroup leaves without writing: the steps it did not reach stay NaN
+    if (e == hipSuccess) e = hipMemsetAsync(y, 0xFF, sizeof(float) * (size_t)N * T * LSTM_OP_HID, s);
+    if (e == hipSuccess) {
+        LstmArgs a{};
+        a.whh = workspace;
+        a.xproj = xproj;
+        a.clipb = nullptr;
+        a.N = N;
+        a.S = T;
+        a.h0 = state;
+        a.hT = state + LSTM_OP_MAXN * LSTM_OP_HID;
+        a.c = state + 2 * LSTM_OP_MAXN * LSTM_OP_HID;
+        a.y = y;
+        a.ystride = (long long)T * LSTM_OP_HID;
+        a.gran = reinterpret_cast<unsigned long long*>(state + LSTM_OP_STATE);
+        a.epoch0 = 1;
+        a.limit = st->limit;
+        a.err = st->err_dev;
+        e = lstm_rec_launch(a, s);
+    }
+    OP_DONE(e, "eamm_op_lstm_forward");
+}
+
+int eamm_op_lstm_scan(int device, float* gates, int N, int T, float* c, void* stream_) {
+    OP_ENTRY(!gates || !c || !lstm_op_shape_ok(N, T), "eamm_op_lstm_scan: bad argument (1 to 8 clips, T >= 1)");
+    const hipError_t e = lstm_scan_launch(gates, N, T, c, s);
+    OP_DONE(e, "eamm_op_lstm_scan");
+}
+
+size_t eamm_op_lstm_backward_workspace_floats(int N, int T) { return lstm_op_shape_ok(N, T) ? LSTM_OP_GRAN_B : 0; }
+
+int eamm_op_lstm_backward(int device, const float* acts, const float* c, const float* w_hh, const float* grad_y, int N, int T,
+                          float* grad_xproj, float* workspace, size_t workspace_floats, void* stream_) {
+    OP_ENTRY(!acts || !c || !w_hh || !grad_y || !grad_xproj || !workspace || !lstm_op_shape_ok(N, T) ||
+                 workspace_floats < eamm_op_lstm_backward_workspace_floats(N, T) || (reinterpret_cast<uintptr_t>(workspace) & 15),
+             "eamm_op_lstm_backward: bad argument (1 to 8 clips, T >= 1, workspace of eamm_op_lstm_backward_workspace_floats, 16-byte "
+             "aligned)");
+    LstmOpState* st = nullptr;
+    hipError_t e = lstm_op_state(device, &st);
+    if (e == hipSuccess && __atomic_load_n(st->err_host, __ATOMIC_ACQUIRE)) return fail(nullptr, EAMM_ERR_HIP, "%s", kLstmTimedOut);
+    if (e == hipSuccess) e = hipMemsetAsync(workspace, 0, sizeof(float) * LSTM_OP_GRAN_B, s);
+    if (e == hipSuccess) {
+        LstmBwdArgs a{};
+        a.whh = w_hh;
+        a.acts = acts;
+        a.c = c;
+        a.dy = grad_y;
+        a.dx = grad_xproj;
+        a.N = N;
+        a.T = T;
+        a.gran = reinterpret_cast<unsigned long long*>(workspace);
+        a.limit = st->limit;
+        a.err = st->err_dev;
+        e = lstm_bwd_launch(a, s);
+    }
+    OP_DONE(e, "eamm_op_lstm_backward");
+}
+
+int eamm_op_lstm_check(int device, void* stream_) {
+    OP_ENTRY(false, "");
+    LstmOpState* st = nullptr;
+    hipError_t e = lstm_op_state(device, &st);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e == hipSuccess && __atomic_load_n(st->err_host, __ATOMIC_ACQUIRE)) return fail(nullptr, EAMM_ERR_HIP, "%s", kLstmTimedOut);
+    OP_DONE(e, "eamm_op_lstm_check");
+}
+
+int eamm_op_audio_maxpool(int device, const float* x, int B, int H, int W, int C, int sy, int sx, float* out, void* stream_) {
+    OP_ENTRY(!x || !out || B < 1 || H < 3 || W < 3 || C < 4 || C % 4 || sy < 1 || sy > 2 || sx < 1 || sx > 2 ||
+                 (long long)B * H * W * C >= (1ll << 31),
+             "eamm_op_audio_maxpool: bad argument (map sides >= 3, strides 1 | 2, C a multiple of 4, fewer than 2^31 elements)");
+    const hipError_t e = audio_maxpool_launch(x, B, H, W, C, sy, sx, out, s);
+    OP_DONE(e, "eamm_op_audio_maxpool");
+}
+
+int eamm_op_audio_maxpool_backward(int device, const float* x, const float* grad_out, int B, int H, int W, int C, int sy, int sx,
+                                   float* grad_x, void* stream_) {
+    OP_ENTRY(!x || !grad_out || !grad_x || B < 1 || H < 3 || W < 3 || C < 4 || C % 4 || sy < 1 || sy > 2 || sx < 1 || sx > 2 ||
+                 (long long)B * H * W * C >= (1ll << 31),
+             "eamm_op_audio_maxpool_backward: bad argument (map sides >= 3, strides 1 | 2, C a multiple of 4, fewer than 2^31 elements)");
+    const hipError_t e = audio_maxpool_backward_launch(x, grad_out, B, H, W, C, sy, sx, grad_x, s);
+    OP_DONE(e, "eamm_op_audio_maxpool_backward");
+}
+
+size_t eamm_op_deconv4s2_workspace_floats(int B, int H, int W, int Cin, int Cout) { return deconv4s2_workspace_floats(B, H, W, Cin, Cout, 0); }
+
+int eamm_op_deconv4s2(int device, const float* x, int B, int H, int W, int Cin, const float* weight, const float* bias, int Cout, float* out,
+                      float* workspace, size_t workspace_floats, void* stream_) {
+    const size_t need = deconv4s2_workspace_floats(B, H, W, Cin, Cout, 0);
+    OP_ENTRY(!x || !weight || !out || !workspace || need == 0 || workspace_floats < need || (reinterpret_cast<uintptr_t>(workspace) & 15),
+             "eamm_op_deconv4s2: bad argument (Cin and Cout multiples of 32, workspace of eamm_op_deconv4s2_workspace_floats, 16-byte "
+             "aligned)");
+    const hipError_t e = deconv4s2_forward_launch(x, weight, bias, B, H, W, Cin, Cout, out, workspace, workspace_floats, s);
+    OP_DONE(e, "eamm_op_deconv4s2");
+}
+
+size_t eamm_op_deconv4s2_dgrad_workspace_floats(int B, int H, int W, int Cin, int Cout) {
+    return deconv4s2_workspace_floats(B, H, W, Cin, Cout, 1);
+}
+
+int eamm_op_deconv4s2_dgrad(int device, const float* grad_out, int B, int H, int W, int Cin, const float* weight, int Cout, float* grad_x,
+                            float* workspace, size_t workspace_floats, void* stream_) {
+    const size_t need = deconv4s2_workspace_floats(B, H, W, Cin, Cout, 1);
+    OP_ENTRY(!grad_out || !weight || !grad_x || !workspace || need == 0 || workspace_floats < need ||
+                 (reinterpret_cast<uintptr_t>(workspace) & 15),
+             "eamm_op_deconv4s2_dgrad: bad argument (Cin and Cout multiples of 32, workspace of eamm_op_deconv4s2_dgrad_workspace_floats, "
+             "16-byte aligned)");
+    const hipError_t e = deconv4s2_dgrad_launch(grad_out, weight, B, H, W, Cin, Cout, grad_x, workspace, workspace_floats, s);
+    OP_DONE(e, "eamm_op_deconv4s2_dgrad");
+}
+
+size_t eamm_op_deconv4s2_wgrad_workspace_floats(int B, int H, int W, int Cin, int Cout) {
+    return deconv4s2_workspace_floats(B, H, W, Cin, Cout, 2);
+}
+
+int eamm_op_deconv4s2_wgrad(int device, const float* x, const float* grad_out, int B, int H, int W, int Cin, int Cout, float* grad_weight,
+                            float* grad_bias, float* workspace, size_t workspace_floats, void* stream_) {
+    const size_t need = deconv4s2_workspace_floats(B, H, W, Cin, Cout, 2);
+    OP_ENTRY(!x || !grad_out || !grad_weight || !workspace || need == 0 || workspace_floats < need ||
+                 (reinterpret_cast<uintptr_t>(workspace) & 15),
+             "eamm_op_deconv4s2_wgrad: bad argument (Cin and Cout multiples of 32, workspace of eamm_op_deconv4s2_wgrad_workspace_floats, "
+             "16-byte aligned)");
+    const hipError_t e = deconv4s2_wgrad_launch(x, grad_out, B, H, W, Cin, Cout, grad_weight, grad_bias, workspace, workspace_floats, s);
+    OP_DONE(e, "eamm_op_deconv4s2_wgrad");
+}
+
+}  // extern "C"
+
 #undef OP_ENTRY
 #undef OP_DONE

@@ -355,6 +355,35 @@ struct LstmArgs {
 };
 void lstm_pack_whh_host(const float* whh /*[1024][256]*/, float* dst /*[16][256][64]*/);
 hipError_t lstm_rec_launch(const LstmArgs& a, hipStream_t s);
+// lstm_backward.hip: what the differentiable LSTM operator needs around lstm_rec_kernel.  lstm_pack_whh_dev_launch:
+// lstm_pack_whh_host on a DEVICE W_hh.  lstm_scan_launch: gate pre-activations [N,T,1024] -> activated gates in place + c [N,T,256].
+// lstm_bwd_launch: the backward recurrence (one persistent launch of LSTM_WG workgroups), dx = the gate gradients [N,T,1024].
+struct LstmBwdArgs {
+    const float* whh;            // W_hh [1024][256] as nn.LSTM keeps it
+    const float* acts;           // [N,T,1024] activated gates i f g o (lstm_scan_launch)
+    const float* c;              // [N,T,256] cell states (lstm_scan_launch)
+    const float* dy;             // [N,T,256] gradient of the layer's output
+    float* dx;                   // [N,T,1024] gradient of the input projection, fully written (NaN after a timed-out wait)
+    int N, T;
+    unsigned long long* gran;    // [2][8][1024] tagged hand-off words, ZEROED before the launch (tags are 1 .. T)
+    unsigned long long limit;    // wall-clock ticks one wait may take before the error word is set
+    int* err;                    // host-visible error word
+};
+hipError_t lstm_pack_whh_dev_launch(const float* whh /*[1024][256]*/, float* dst /*[16][256][64]*/, hipStream_t s);
+hipError_t lstm_scan_launch(float* gates, int N, int T, float* c, hipStream_t s);
+hipError_t lstm_bwd_launch(const LstmBwdArgs& a, hipStream_t s);
+// audio_backward.hip: MaxPool2d(3, (sy, sx)) backward (each window's winner recomputed, first maximum in row-major order; a gather
+// per input pixel, no atomics) and ConvTranspose2d(k4, s2, p1) on NHWC with the reference's filter [Cin,Cout,4,4] ON THE DEVICE
+// (Cin, Cout multiples of 32): forward (+ bias, nullable), data gradient, weight (+ bias, nullable) gradient.  *_workspace_floats
+// is 0 for an unsupported shape.
+hipError_t audio_maxpool_backward_launch(const float* in, const float* dy, int F, int H, int W, int C, int sy, int sx, float* dx, hipStream_t s);
+size_t deconv4s2_workspace_floats(int B, int H, int W, int Cin, int Cout, int which /*0 forward, 1 data gradient, 2 weight gradient*/);
+hipError_t deconv4s2_forward_launch(const float* x, const float* weight, const float* bias, int B, int H, int W, int Cin, int Cout, float* out,
+                                    float* workspace, size_t workspace_floats, hipStream_t s);
+hipError_t deconv4s2_dgrad_launch(const float* dy, const float* weight, int B, int H, int W, int Cin, int Cout, float* dx, float* workspace,
+                                  size_t workspace_floats, hipStream_t s);
+hipError_t deconv4s2_wgrad_launch(const float* x, const float* dy, int B, int H, int W, int Cin, int Cout, float* dweight, float* dbias,
+                                  float* workspace, size_t workspace_floats, hipStream_t s);
 
 hipError_t one_euro_launch(const float* x, int T, int E, float mincutoff, float beta, float dcutoff, float freq, float scale,
                            float* out, hipStream_t stream, float* state = nullptr, int resume = 0);

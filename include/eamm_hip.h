@@ -746,6 +746,53 @@ size_t eamm_op_emo_final_workspace_floats(int B);
 int eamm_op_emo_final_backward(int device, const float* a, const float* w98, const float* g_value, const float* g_jacobian, int B,
                                float* grad_a, float* grad_w98, float* workspace, size_t workspace_floats, void* stream);
 
+/*
+ * AT_net2's LSTM layer, max-pools and ConvTranspose2d(k4, s2, p1) as DIFFERENTIABLE operators (reference modules/util.py:539-576,
+ * :596-598; what train.py's first stage back-propagates through).  Additive entries (ABI 6 unchanged).  Device pointers, fp32;
+ * asynchronous on `stream`; a bad shape is refused before any launch and the *_workspace_floats query returns 0 for it.
+ * `workspace`: the query's floats, 16-byte aligned.
+ *   eamm_op_lstm_forward    one nn.LSTM layer (hidden 256, gates i f g o) from a zero state: xproj [N,T,1024] = x W_ih^T + b_ih + b_hh,
+ *                           w_hh [1024,256] -> y [N,T,256]; 1 <= N <= 8, T >= 1.  The inference engine's persistent recurrence
+ *                           kernel, on a W_hh image packed on the device; the call zeroes its own hand-off words on the stream.
+ *   eamm_op_lstm_scan       gate pre-activations [N,T,1024] -> the activated gates IN PLACE and the cell states c [N,T,256].
+ *   eamm_op_lstm_backward   acts, c (eamm_op_lstm_scan), w_hh, grad_y [N,T,256] -> grad_xproj [N,T,1024] (= the gate gradients): one
+ *                           persistent launch of 16 workgroups stepping t = T-1 .. 0, each owning 16 hidden units with its
+ *                           1024 x 16 slice of W_hh in LDS, exchanging the gate gradients of a step through tagged 8-byte words.
+ *   eamm_op_lstm_check      waits for `stream`; EAMM_ERR_HIP if a recurrence of either direction timed out on this device (a
+ *                           workgroup waited more than 10 s for another): the outputs hold NaN from the step it stopped at, and
+ *                           the LSTM operators of the device refuse further calls.
+ *   eamm_op_audio_maxpool / _backward   MaxPool2d(3, (sy, sx)) without padding on NHWC x [B,H,W,C] (C a multiple of 4, strides 1 | 2)
+ *                           -> [B,(H-3)/sy+1,(W-3)/sx+1,C]; backward: grad_x fully written, a gather per input pixel over the windows
+ *                           that contain it, each window's winner recomputed (first maximum in row-major order); no atomics.
+ *   eamm_op_deconv4s2       ConvTranspose2d(Cin, Cout, 4, 2, 1): x [B,H,W,Cin], weight [Cin,Cout,4,4] (the reference's layout), bias
+ *                           [Cout] or NULL -> out [B,2H,2W,Cout]; Cin and Cout multiples of 32.  The four-phase 2x2 form: one
+ *                           implicit GEMM on v_mfma_f32_32x32x2_f32 per output-pixel parity class.
+ *   eamm_op_deconv4s2_dgrad grad_out [B,2H,2W,Cout], weight -> grad_x [B,H,W,Cin]: the 4x4 stride-2 pad-1 convolution of grad_out as a
+ *                           gather per input pixel on the matrix cores; no atomics, every element written.
+ *   eamm_op_deconv4s2_wgrad x, grad_out -> grad_weight [Cin,Cout,4,4] (one GEMM per tap, split over the pixels, the slabs summed in
+ *                           a fixed order) and, unless NULL, grad_bias [Cout].
+ */
+size_t eamm_op_lstm_workspace_floats(int N, int T);
+int eamm_op_lstm_forward(int device, const float* xproj, const float* w_hh, int N, int T, float* y, float* workspace, size_t workspace_floats,
+                         void* stream);
+int eamm_op_lstm_scan(int device, float* gates, int N, int T, float* c, void* stream);
+size_t eamm_op_lstm_backward_workspace_floats(int N, int T);
+int eamm_op_lstm_backward(int device, const float* acts, const float* c, const float* w_hh, const float* grad_y, int N, int T,
+                          float* grad_xproj, float* workspace, size_t workspace_floats, void* stream);
+int eamm_op_lstm_check(int device, void* stream);
+int eamm_op_audio_maxpool(int device, const float* x, int B, int H, int W, int C, int sy, int sx, float* out, void* stream);
+int eamm_op_audio_maxpool_backward(int device, const float* x, const float* grad_out, int B, int H, int W, int C, int sy, int sx,
+                                   float* grad_x, void* stream);
+size_t eamm_op_deconv4s2_workspace_floats(int B, int H, int W, int Cin, int Cout);
+int eamm_op_deconv4s2(int device, const float* x, int B, int H, int W, int Cin, const float* weight, const float* bias, int Cout, float* out,
+                      float* workspace, size_t workspace_floats, void* stream);
+size_t eamm_op_deconv4s2_dgrad_workspace_floats(int B, int H, int W, int Cin, int Cout);
+int eamm_op_deconv4s2_dgrad(int device, const float* grad_out, int B, int H, int W, int Cin, const float* weight, int Cout, float* grad_x,
+                            float* workspace, size_t workspace_floats, void* stream);
+size_t eamm_op_deconv4s2_wgrad_workspace_floats(int B, int H, int W, int Cin, int Cout);
+int eamm_op_deconv4s2_wgrad(int device, const float* x, const float* grad_out, int B, int H, int W, int Cin, int Cout, float* grad_weight,
+                            float* grad_bias, float* workspace, size_t workspace_floats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
