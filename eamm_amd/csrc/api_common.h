@@ -279,8 +279,9 @@ int pack_patch(CtxBase* c, const HostConv& f, const int* map, int C0_packed, int
     return upload_bias(c, &P->bias, f.b, (size_t)((f.Cout + 63) / 64) * 64);
 }
 
-// -> WinoLayer: Winograd-domain weights U = G g G^T of a 3x3 convolution, F(2x2,3x3) (tile 2) or F(4x4,3x3) (tile 4)
-int pack_wino(CtxBase* c, const HostConv& f, int tile, WinoLayer* L) {
+// -> WinoLayer: Winograd-domain weights U = G g G^T of a 3x3 convolution, F(2x2,3x3) (tile 2) or F(4x4,3x3) (tile 4);
+// split_planes: also the three-plane bf16 image of a tile-4 layer (a layer that only runs split over workgroups needs none)
+int pack_wino(CtxBase* c, const HostConv& f, int tile, WinoLayer* L, bool split_planes = true) {
     L->Cin = f.Cin;
     L->Cout = f.Cout;
     L->tile = tile;
@@ -292,6 +293,11 @@ int pack_wino(CtxBase* c, const HostConv& f, int tile, WinoLayer* L) {
     else
         wino_pack_host(f.w.data(), f.Cout, f.Cin, L->BN, packed.data());
     if (int rc = upload(c, &L->u, packed)) return rc;
+    if (split_planes && tile == 4 && f.Cin % (4 * CONV_BK) == 0) {   // the whole-tile launches of such a layer run the split-bf16 form (conv_winograd4.hip)
+        std::vector<float> planes(wino4_split_packed_elems(f.Cout, f.Cin, L->BN));
+        wino4_pack_split_host(f.w.data(), f.Cout, f.Cin, L->BN, reinterpret_cast<uint16_t*>(planes.data()));
+        if (int rc = upload(c, &L->u3, planes)) return rc;
+    }
     return upload_bias(c, &L->bias, f.b, (size_t)L->ntiles * L->BN);
 }
 
@@ -382,7 +388,7 @@ int build_wino4_rect(CtxBase* c, const std::string& conv, const std::string& nor
     p.w.assign((size_t)f.Cout * Cin_packed * 9, 0.f);
     for (int o = 0; o < f.Cout; ++o)
         std::copy_n(f.w.begin() + (size_t)o * Cin_real * 9, (size_t)Cin_real * 9, p.w.begin() + (size_t)o * Cin_packed * 9);
-    return pack_wino(c, p, 4, L);
+    return pack_wino(c, p, 4, L, false);   // the hourglass encoder's launches are variant 0: fp32 form
 }
 
 // Tile choice per launch (measured on MI355X, profiles/r01_convbench_*): M is the per-phase pixel count.

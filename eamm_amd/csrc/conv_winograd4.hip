@@ -1,8 +1,14 @@
 // Winograd F(4x4, 3x3) form of the 3x3 / pad 1 convolution for the bottleneck ResBlock2d stack
 // (reference modules/util.py:858-880, generator.py:89): 36 multiplies per 16 outputs and input channel instead of
-// 144 (direct) or 64 (F(2x2,3x3), conv_winograd.hip) -- 4x fewer MFMA passes than the direct form, still plain fp32
-// arithmetic (v_mfma_f32_16x16x4_f32 + fp32 VALU), only the summation order / rounding differs (measured at the
-// prediction: tools/wino_numerics.py).
+// 144 (direct) or 64 (F(2x2,3x3), conv_winograd.hip) -- 4x fewer MFMA passes than the direct form.  The transforms and the
+// folds are fp32 VALU arithmetic; the products come in two forms (template parameter SPLIT of wino4_gemm_kernel):
+//   SPLIT 0: v_mfma_f32_16x16x4_f32 on the fp32 operands (every launch but the ones below), only the summation order /
+//            rounding differs from the direct form (measured at the prediction: tools/wino_numerics.py);
+//   SPLIT 1: (groups == 1, Cin % 128 == 0, pipeline variants 3 / 6: the bottleneck from 10 frames per call) every fp32 operand
+//            is the EXACT sum of three bf16 values taken by truncation, a = a1 + a2 + a3, and a*b is the six products
+//            a1b3, a2b2, a3b1, a1b2, a2b1, a1b1 on v_mfma_f32_16x16x32_bf16 with fp32 accumulation (the dropped terms are
+//            <= 2^-24 relative): fp32 accuracy at 6/16 of the fp32 matrix-pipe time.  U is split once on the host
+//            (wino4_pack_split_host), V stays fp32 in HBM and LDS and is split in registers after the LDS read.
 //
 //   Y = A^T [ sum_c (G g G^T) (.) (B^T d B) ] A        d: 6x6 input patch (stride 4), Y: 4x4 outputs
 //
@@ -25,7 +31,9 @@
 #include "conv_common.h"
 
 #include <algorithm>
+#include <cstdint>
 #include <cstdlib>
+#include <cstring>
 
 namespace eamm {
 
@@ -165,7 +173,8 @@ __global__ __launch_bounds__(256) void wino4_input_transform_kernel(const float*
 // ---------------------------------------------------------------------------------------------------------
 struct Wino4Args {
     const float* V;        // [36][Mq][C]
-    const float* U;        // packed [ntiles][36 * C/32][BN][32] (swizzled), xi outer / channel chunk inner
+    const float* U;        // packed [ntiles][36 * C/32][BN][32] (swizzled), xi outer / channel chunk inner; SPLIT: the three-plane
+                           // bf16 image of wino4_pack_split_host, [ntiles][36 * C/32][BN/16][3][64 lanes][8]
     const float* bias;     // [ntiles*BN]
     unsigned v_bytes, u_bytes;
     int Mq, C, Cout;       // tiles (= pixels / 16), input channels, output channels
@@ -184,15 +193,45 @@ __constant__ float WINO4_AT[4][8] = {{1.f, 1.f, 1.f, 1.f, 1.f, 0.f, 0.f, 0.f},
                                      {0.f, 1.f, 1.f, 4.f, 4.f, 0.f, 0.f, 0.f},
                                      {0.f, 1.f, -1.f, 8.f, -8.f, 1.f, 0.f, 0.f}};
 
+typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
+
+// bf16 pair {hi16(lo), hi16(hi)}: one v_perm_b32
+__device__ __forceinline__ unsigned wino4_hi_pair(unsigned lo, unsigned hi) { return __builtin_amdgcn_perm(hi, lo, 0x07060302u); }
+
+// Eight fp32 values -> three planes of eight bf16, by truncation: a1 = top 16 bits of a, r = a - a1 (exact), a2 = top 16 bits
+// of r, a3 = r - a2 (exact, at most 8 significant bits: its low half is zero).  a1 + a2 + a3 == a; inf / NaN give NaN residuals.
+__device__ __forceinline__ void wino4_split3(const f32x4_t& x0, const f32x4_t& x1, u32x4 (&pl)[3]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {   // a pair at a time: few temporaries
+        unsigned b1[2], b2[2], b3[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const float x = i < 2 ? x0[2 * i + h] : x1[2 * i - 4 + h];
+            b1[h] = __float_as_uint(x);
+            const float r = x - __uint_as_float(b1[h] & 0xFFFF0000u);
+            b2[h] = __float_as_uint(r);
+            b3[h] = __float_as_uint(r - __uint_as_float(b2[h] & 0xFFFF0000u));
+        }
+        pl[0][i] = wino4_hi_pair(b1[0], b1[1]);
+        pl[1][i] = wino4_hi_pair(b2[0], b2[1]);
+        pl[2][i] = wino4_hi_pair(b3[0], b3[1]);
+    }
+}
+
 // A wave owns 16 Winograd tiles x NT*16 output channels; WM x WN waves per block.  SUB: 32-channel chunks per
 // barrier interval; NST: LDS ring depth in intervals; PE: one DMA piece every PE MFMAs from the start of an interval.
-template <int NT, int WM, int WN, int SUB, int NST, int PE, int DBG = 0>
+// SPLIT: the product form (file header): 0 fp32 MFMA, 1 six bf16 MFMAs on the three-way split operands.
+template <int NT, int WM, int WN, int SUB, int NST, int PE, int DBG = 0, int SPLIT = 0>
 __global__ __launch_bounds__(WM* WN * 64) void wino4_gemm_kernel(const Wino4Args p) {
     constexpr int NW = WM * WN, NTHR = NW * 64;
     constexpr int BM = WM * 16, BN = WN * NT * 16, BK = CONV_BK;
-    constexpr int A_STAGE = SUB * BM * BK, B_STAGE = SUB * BN * BK;  // floats per stage
+    constexpr int B_CHUNK = SPLIT ? BN * BK * 3 / 2 : BN * BK;        // floats of U per chunk: fp32, or three bf16 planes (x 1.5)
+    constexpr int A_STAGE = SUB * BM * BK, B_STAGE = SUB * B_CHUNK;   // floats per stage
     constexpr int A_INSTR = BM / 8 / NW, B_INSTR = BN / 8 / NW;       // DMA instructions per wave per chunk
-    constexpr int NPIECE = SUB * (A_INSTR + B_INSTR);
+    // SPLIT: a stage's U is one contiguous image in HBM and in LDS, copied in 1 KB pieces, U_INSTR per wave and interval
+    constexpr int U_INSTR = SUB * B_CHUNK / 256 / NW;
+    constexpr int NPIECE = SPLIT ? SUB * A_INSTR + U_INSTR : SUB * (A_INSTR + B_INSTR);
+    static_assert(!SPLIT || (SUB * B_CHUNK) % (256 * NW) == 0, "the stage's U must split evenly into 1 KB pieces per wave");
     constexpr bool TRACE = DBG == 8 || DBG == 9;   // DBG: 0 product; 1 no DMA in the loop; 8/9 interval trace (with/without DMA);
                                                    // 30 V-sized extra output; 40 non-temporal V loads
     static_assert(BM % (8 * NW) == 0 && BN % (8 * NW) == 0, "tile rows must split evenly over the waves");
@@ -239,8 +278,8 @@ __global__ __launch_bounds__(WM* WN * 64) void wino4_gemm_kernel(const Wino4Args
 
     // uniform state of the interval whose pieces are issued next
     unsigned sa_off = (unsigned)xi0 * plane_bytes;                                                 // (xi, cc) in V
-    unsigned sb_off = (unsigned)((ntile * 36 * cchunks + ci_base) * BN * BK) * 4u +               // chunk ci in U
-                      (unsigned)(wave * B_INSTR * 8 * BK) * 4u;                                    // + this wave's rows
+    unsigned sb_off = (unsigned)((ntile * 36 * cchunks + ci_base) * B_CHUNK) * 4u +               // chunk ci in U
+                      (unsigned)(wave * (SPLIT ? U_INSTR * 256 : B_INSTR * 8 * BK)) * 4u;          // + this wave's rows (SPLIT: pieces)
     int dma_cc = 0, n_st = 0;
     auto dma_advance = [&]() {
         dma_cc += SUB;
@@ -249,12 +288,13 @@ __global__ __launch_bounds__(WM* WN * 64) void wino4_gemm_kernel(const Wino4Args
             dma_cc = 0;
             sa_off += a_wrap;
         }
-        sb_off += SUB * BN * BK * 4;
+        sb_off += SUB * B_CHUNK * 4;
         n_st = n_st + 1 == NST ? 0 : n_st + 1;
     };
     auto dma_piece = [&](auto kc) {
         constexpr int k = decltype(kc)::value;
-        constexpr int sub = k / (A_INSTR + B_INSTR), r = k % (A_INSTR + B_INSTR);
+        constexpr int sub = SPLIT ? (k < SUB * A_INSTR ? k / A_INSTR : 0) : k / (A_INSTR + B_INSTR);
+        constexpr int r = SPLIT ? (k < SUB * A_INSTR ? k % A_INSTR : A_INSTR + k - SUB * A_INSTR) : k % (A_INSTR + B_INSTR);
         if constexpr (r < A_INSTR) {
             // the instruction's immediate offset moves the LDS address as well as the global one: take it off the LDS side
             float* dst = As + n_st * A_STAGE + sub * (BM * BK) + (wave * A_INSTR + r) * (8 * BK) - sub * BK;
@@ -262,6 +302,10 @@ __global__ __launch_bounds__(WM* WN * 64) void wino4_gemm_kernel(const Wino4Args
             // kernel's stub without a diagnostic -- the library then fails to load with an undefined kernel symbol)
             const unsigned vo = arow_off[r];
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rsv, (lds_ptr_t)dst, 16, vo, sa_off, sub * BK * 4, DBG == 40 ? 2 : 0);   // 40 (variant 6): V is streamed once per XCD -- non-temporal
+        } else if constexpr (SPLIT) {
+            constexpr int j = r - A_INSTR;   // the wave's j-th 1 KB piece of the stage image: a straight copy
+            float* dst = Bs + n_st * B_STAGE + (wave * U_INSTR + j) * 256;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsu, (lds_ptr_t)dst, 16, b_lane, sb_off + (unsigned)(j * 1024), 0, 0);
         } else {
             constexpr int j = r - A_INSTR;
             float* dst = Bs + n_st * B_STAGE + sub * (BN * BK) + (wave * B_INSTR + j) * (8 * BK);
@@ -286,7 +330,8 @@ __global__ __launch_bounds__(WM* WN * 64) void wino4_gemm_kernel(const Wino4Args
     const int sw = (r16 >> 1) & 7;
     constexpr int STEPS = SUB * 2;               // 16-wide K steps per barrier interval
     constexpr int MF = 4 * NT;                   // MFMAs per step
-    constexpr int TOTAL_MF = STEPS * MF;
+    constexpr int MF_SPLIT = 6 * NT;             // SPLIT: MFMAs per 32-channel chunk
+    constexpr int TOTAL_MF = SPLIT ? SUB * MF_SPLIT : STEPS * MF;
     static_assert(PE >= 1 && NPIECE * PE <= TOTAL_MF, "DMA pieces must fit in the interval");
     // MORE: the interval issues the DMA pieces of the interval D ahead; YOUNG: all of them before the first MFMA.
     // Both are wave-uniform and resolved ONCE per interval (interval() below), so the MFMA stream carries no branches.
@@ -327,14 +372,81 @@ __global__ __launch_bounds__(WM* WN * 64) void wino4_gemm_kernel(const Wino4Args
             });
         });
     };
+    // SPLIT form of compute(): per 32-channel chunk two ds_read_b128 of the fp32 V row (the lane's k = 4g + e and 16 + 4g + e, e < 4:
+    // the two 16-byte slots the fp32 form reads in its two steps), split in registers into three bf16x8 planes, and six
+    // ds_read_b128 of U (plane x column block; lane-linear 1 KB images: conflict-free).  The k order inside the MFMA is the lane's
+    // own on both operands.
+    auto compute_split = [&](int st, auto more_c, auto young_c) {
+        constexpr bool MORE = decltype(more_c)::value && DBG != 1 && DBG != 9, YOUNG = decltype(young_c)::value;
+        f32x4_t araw[2];
+        u32x4 ap[3], ub[3][NT];
+        auto fetch_a = [&](int sub) {
+            const float* a_base = As + st * A_STAGE + sub * (BM * BK) + (wm * 16 + r16) * BK;
+            araw[0] = *reinterpret_cast<const f32x4_t*>(a_base + ((g ^ sw) << 2));
+            araw[1] = *reinterpret_cast<const f32x4_t*>(a_base + (((4 + g) ^ sw) << 2));
+        };
+        auto fetch_u = [&](int sub, int pl) {
+            const float* u_base = Bs + st * B_STAGE + sub * B_CHUNK + ((wn * NT) * 3 + pl) * 256 + lane * 4;
+#pragma unroll
+            for (int j = 0; j < NT; ++j) ub[pl][j] = *reinterpret_cast<const u32x4*>(u_base + j * 3 * 256);
+        };
+        // the MFMAs of one term (NT of them), with the older half's DMA pieces interleaved by MFMA count as in compute()
+        auto term = [&](auto sc, auto tc) {
+            constexpr int sub = decltype(sc)::value, t = decltype(tc)::value;
+            constexpr int pa = t == 0 ? 0 : t == 1 ? 2 : t == 2 ? 1 : t == 3 ? 0 : t == 4 ? 1 : 0;   // a1b3 | a3b1 a2b1 a1b1 | a2b2 a1b2
+            constexpr int pb = t == 0 ? 2 : t <= 3 ? 0 : 1;
+            static_for<NT>([&](auto jc) {
+                constexpr int j = decltype(jc)::value;
+                acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, ap[pa]), __builtin_bit_cast(bf16x8_t, ub[pb][j]),
+                                                                  acc[j], 0, 0, 0);
+                constexpr int gi = sub * MF_SPLIT + t * NT + j;
+                if constexpr (MORE && !YOUNG && gi % PE == PE - 1 && gi / PE < NPIECE) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    dma_piece(std::integral_constant<int, gi / PE>{});
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            });
+        };
+        fetch_a(0);
+        if constexpr (MORE && YOUNG) static_for<NPIECE>([&](auto kc) { dma_piece(kc); });
+        // Register budget (the accumulators and the epilogue's addresses leave about 30 registers): the raw A row 8 -> its planes 12,
+        // and at most two U planes (16), or one U plane and the next chunk's raw A -- the scheduling barriers keep the loads in
+        // these slots: U3 is read before the split (8 + 8 + 12), U1 behind it, U2 while U1's terms issue, the next A while U2's do.
+        static_for<SUB>([&](auto sc) {
+            constexpr int sub = decltype(sc)::value;
+            fetch_u(sub, 2);
+            __builtin_amdgcn_sched_barrier(0);
+            wino4_split3(araw[0], araw[1], ap);
+            __builtin_amdgcn_sched_barrier(0);
+            fetch_u(sub, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            term(sc, std::integral_constant<int, 0>{});
+            __builtin_amdgcn_sched_barrier(0);
+            fetch_u(sub, 1);
+            __builtin_amdgcn_sched_barrier(0);
+            term(sc, std::integral_constant<int, 1>{});
+            term(sc, std::integral_constant<int, 2>{});
+            term(sc, std::integral_constant<int, 3>{});
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (sub + 1 < SUB) fetch_a(sub + 1);
+            __builtin_amdgcn_sched_barrier(0);
+            term(sc, std::integral_constant<int, 4>{});
+            term(sc, std::integral_constant<int, 5>{});
+            __builtin_amdgcn_sched_barrier(0);
+        });
+    };
     const bool young = wave >= NW / 2;
+    auto run = [&](int st, auto more_c, auto young_c) {
+        if constexpr (SPLIT) compute_split(st, more_c, young_c);
+        else compute(st, more_c, young_c);
+    };
     auto interval = [&](int st, bool more) {
         if (more) {
-            if (young) compute(st, std::true_type{}, std::true_type{});
-            else compute(st, std::true_type{}, std::false_type{});
+            if (young) run(st, std::true_type{}, std::true_type{});
+            else run(st, std::true_type{}, std::false_type{});
             dma_advance();
         } else {
-            compute(st, std::false_type{}, std::false_type{});
+            run(st, std::false_type{}, std::false_type{});
         }
     };
 
@@ -589,36 +701,70 @@ __global__ __launch_bounds__(256) void wino4_output_transform_kernel(const float
 // ---------------------------------------------------------------------------------------------------------
 // U[xi][o][c] = (G g G^T)[xi]; w: [Cout][Cin][3][3] (BN folded).  Packed [ntiles][36*Cin/32][BN][32],
 // chunk = xi*(Cin/32) + cc, 16-byte slots XOR-swizzled like conv_mfma_dma.
-void wino4_pack_host(const float* w, int Cout, int Cin, int BN, float* dst) {
+namespace {
+// calls put(o, c, xi, (float)u) for every U element
+template <typename F>
+void wino4_for_each_u(const float* w, int Cout, int Cin, F&& put) {
     static const double G[6][3] = {{1.0 / 4, 0, 0},           {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
                                    {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6},  {0, 0, 1}};
-    const int BK = CONV_BK, cch = Cin / BK;
-    const int ntiles = (Cout + BN - 1) / BN;
-    const size_t total = (size_t)ntiles * 36 * cch * BN * BK;
-    for (size_t i = 0; i < total; ++i) dst[i] = 0.f;
     for (int o = 0; o < Cout; ++o) {
-        const int nt = o / BN, nl = o % BN;
         for (int c = 0; c < Cin; ++c) {
             const float* gw = w + ((size_t)o * Cin + c) * 9;
             double tmp[6][3];
             for (int i = 0; i < 6; ++i)
                 for (int k = 0; k < 3; ++k)
                     tmp[i][k] = G[i][0] * gw[0 * 3 + k] + G[i][1] * gw[1 * 3 + k] + G[i][2] * gw[2 * 3 + k];
-            const int cc = c / BK, kl = c % BK;
-            const int kk = ((((kl >> 2) ^ ((nl >> 1) & 7)) << 2) | (kl & 3));
             for (int i = 0; i < 6; ++i)
                 for (int j = 0; j < 6; ++j) {
                     const double u = tmp[i][0] * G[j][0] + tmp[i][1] * G[j][1] + tmp[i][2] * G[j][2];
-                    const int xi = i * 6 + j;
-                    dst[(((size_t)nt * 36 * cch + (size_t)xi * cch + cc) * BN + nl) * BK + kk] = (float)u;
+                    put(o, c, i * 6 + j, (float)u);
                 }
         }
     }
+}
+}  // namespace
+
+void wino4_pack_host(const float* w, int Cout, int Cin, int BN, float* dst) {
+    const int BK = CONV_BK, cch = Cin / BK;
+    const size_t total = wino4_packed_elems(Cout, Cin, BN);
+    for (size_t i = 0; i < total; ++i) dst[i] = 0.f;
+    wino4_for_each_u(w, Cout, Cin, [&](int o, int c, int xi, float u) {
+        const int nt = o / BN, nl = o % BN;
+        const int cc = c / BK, kl = c % BK;
+        const int kk = ((((kl >> 2) ^ ((nl >> 1) & 7)) << 2) | (kl & 3));
+        dst[(((size_t)nt * 36 * cch + (size_t)xi * cch + cc) * BN + nl) * BK + kk] = u;
+    });
 }
 
 size_t wino4_packed_elems(int Cout, int Cin, int BN) {
     return (size_t)((Cout + BN - 1) / BN) * 36 * (Cin / CONV_BK) * BN * CONV_BK;
 }
+
+// The same U as three bf16 planes for the SPLIT form of wino4_gemm_kernel: the fp32-ROUNDED value of wino4_pack_host is split by
+// truncation, u1 = top 16 bits of u, u2 = top 16 bits of u - u1, u3 = u - u1 - u2 (both differences exact), so u1 + u2 + u3 is
+// today's float exactly.  Image [ntiles][36 * Cin/32][BN/16][3 planes][64 lanes][8]: a chunk's (column block, plane) is the 1 KB a
+// wave reads with ONE ds_read_b128 per lane, lane-linear (conflict-free).  Lane = 16 g + (column % 16) holds the channels
+// 4 g + e (e < 4) and 16 + 4 g + (e - 4) (e >= 4) of the chunk -- the lane's two 16-byte slots of the fp32 V row.
+void wino4_pack_split_host(const float* w, int Cout, int Cin, int BN, uint16_t* dst) {
+    const int BK = CONV_BK, cch = Cin / BK;
+    const size_t total = 3 * wino4_packed_elems(Cout, Cin, BN);
+    for (size_t i = 0; i < total; ++i) dst[i] = 0;
+    auto bits = [](float f) { uint32_t b; memcpy(&b, &f, 4); return b; };
+    auto top = [](uint32_t b) { b &= 0xFFFF0000u; float f; memcpy(&f, &b, 4); return f; };
+    wino4_for_each_u(w, Cout, Cin, [&](int o, int c, int xi, float u) {
+        const int nt = o / BN, nl = o % BN;
+        const int cc = c / BK, kl = c % BK;
+        const int lane = ((kl & 15) >> 2) * 16 + (nl & 15), e = (kl >> 4) * 4 + (kl & 3);
+        const float r = u - top(bits(u)), r2 = r - top(bits(r));
+        uint16_t* blk = dst + ((((size_t)nt * 36 * cch + (size_t)xi * cch + cc) * (BN / 16) + nl / 16) * 3) * 512 + lane * 8 + e;
+        blk[0] = (uint16_t)(bits(u) >> 16);
+        blk[512] = (uint16_t)(bits(r) >> 16);
+        blk[1024] = (uint16_t)(bits(r2) >> 16);
+    });
+}
+
+// floats of device memory the three-plane image takes (six bytes per U element)
+size_t wino4_split_packed_elems(int Cout, int Cin, int BN) { return wino4_packed_elems(Cout, Cin, BN) * 3 / 2; }
 
 hipError_t wino4_transform_launch(const float* x, const float* s, const float* t, int B, int H, int W, int C, float* V,
                                   hipStream_t stream) {
@@ -646,17 +792,19 @@ hipError_t wino4_transform_launch(const float* x, const float* s, const float* t
     return hipGetLastError();
 }
 
-template <int SUB, int NST, int PE, int DBG = 0, int WM = 4>
+template <int SUB, int NST, int PE, int DBG = 0, int WM = 4, int SPLIT = 0>
 static hipError_t wino4_launch_variant(const Wino4Args& a, hipStream_t stream) {
     constexpr int NT = 2, WN = 2;
     constexpr int BM = WM * 16, BN = WN * NT * 16;
-    constexpr size_t lds_loop = sizeof(float) * NST * SUB * (BM + BN) * CONV_BK;
+    constexpr size_t lds_loop = sizeof(float) * NST * SUB * (BM + (SPLIT ? BN * 3 / 2 : BN)) * CONV_BK;   // SPLIT, 4 x 2: exactly 160 KB
     constexpr size_t lds_epi = sizeof(float) * 4 * BM * (BN + 4);
     constexpr size_t lds = lds_loop > lds_epi ? lds_loop : lds_epi;
     static_assert(lds <= 160 * 1024, "LDS budget");
-    auto kern = wino4_gemm_kernel<NT, WM, WN, SUB, NST, PE, DBG>;
+    auto kern = wino4_gemm_kernel<NT, WM, WN, SUB, NST, PE, DBG, SPLIT>;
     static lds_once_mask configured{0};  // per-device bit mask
     if (hipError_t e = ensure_dynamic_lds(kern, lds, &configured); e != hipSuccess) return e;
+    // the fp32-equivalent multiply-adds the GEMM stands for, whatever the product form: the SPLIT form issues six bf16 MFMAs per
+    // product and is still counted once, against the fp32 peak
     note_mfma_flops(2.0 * 36.0 * a.mtiles * BM * (double)a.ntiles * BN * a.C);
     hipLaunchKernelGGL(kern, dim3(a.mtiles * a.ntiles * a.groups), dim3(WM * WN * 64), lds, stream, a);
     return hipGetLastError();
@@ -698,11 +846,16 @@ hipError_t wino4_gemm_launch(const WinoLayer& L, const float* V, int B, int H, i
     // extra output): they exist only in a -DEAMM_EXPERIMENTS build (make EXPERIMENTS=1); the product library refuses them
     if (variant == 10 || variant == 16 || variant == 17 || variant == 50) return hipErrorInvalidValue;
 #endif
-    const size_t vb = (size_t)36 * a.Mq * a.C * sizeof(float), ub = wino4_packed_elems(L.Cout, L.Cin, BN) * sizeof(float);
+    const bool sub4 = L.Cin % (4 * CONV_BK) == 0;
+    // the split-bf16 product form: the whole-tile launches of variants 3 / 6 (the bottleneck chains) on four-chunk intervals, for a layer
+    // packed with its three-plane image; everything else (groups > 1, narrow, Cin = 192, variant 0, device-packed weights) is fp32
+    const bool split = groups == 1 && sub4 && L.u3 != nullptr && (variant == 3 || variant == 6);
+    if (split) a.U = L.u3;
+    const size_t vb = (size_t)36 * a.Mq * a.C * sizeof(float),
+                 ub = (split ? wino4_split_packed_elems(L.Cout, L.Cin, BN) : wino4_packed_elems(L.Cout, L.Cin, BN)) * sizeof(float);
     if (vb >= 0xFFFFF000ull || ub >= 0xFFFFF000ull) return hipErrorInvalidValue;
     a.v_bytes = (unsigned)vb;
     a.u_bytes = (unsigned)ub;
-    const bool sub4 = L.Cin % (4 * CONV_BK) == 0;
     hipError_t e = hipErrorInvalidValue;
     // (round 6: a three-stage ring for the narrow launches -- two intervals of operands in flight -- measured 21.8 us per launch against 21.5:
     //  the one-frame launch is not DMA-latency bound; its 12 intervals cost what the steady-state kernel's cost, 1.2 us each, + ~7 us fixed)
@@ -716,8 +869,8 @@ hipError_t wino4_gemm_launch(const WinoLayer& L, const float* V, int B, int H, i
         case 17: e = wino4_launch_variant<4, 2, 4, 9>(a, stream); break;
 #endif
         case 0: e = sub4 ? wino4_launch_variant<4, 2, 4>(a, stream) : wino4_launch_variant<2, 2, 4>(a, stream); break;
-        case 3: e = sub4 ? wino4_launch_variant<4, 2, 8>(a, stream) : wino4_launch_variant<2, 2, 4>(a, stream); break;
-        case 6: e = sub4 ? wino4_launch_variant<4, 2, 8, 40>(a, stream) : wino4_launch_variant<2, 2, 4>(a, stream); break;   // variant 3 with non-temporal V loads (the default since round 5: 4034 -> 4048 frames/s)
+        case 3: e = split ? wino4_launch_variant<4, 2, 4, 0, 4, 1>(a, stream) : sub4 ? wino4_launch_variant<4, 2, 8>(a, stream) : wino4_launch_variant<2, 2, 4>(a, stream); break;
+        case 6: e = split ? wino4_launch_variant<4, 2, 4, 40, 4, 1>(a, stream) : sub4 ? wino4_launch_variant<4, 2, 8, 40>(a, stream) : wino4_launch_variant<2, 2, 4>(a, stream); break;   // variant 3 with non-temporal V loads (the default since round 5: 4034 -> 4048 frames/s)
         default: break;   // (eamm_create admits 0, 3, 6 only)
     }
     if (e != hipSuccess || groups == 1) return e;

@@ -137,6 +137,8 @@ struct WinoLayer {
     int Cin = 0, Cout = 0, BN = 128, ntiles = 0;
     int tile = 2;           // output tile side: 2 -> 16 transform points, BN 128; 4 -> 36 points, BN 64
     float* u = nullptr;     // device, packed [ntiles][(tile+2)^2*Cin/32][BN][32]
+    float* u3 = nullptr;    // device, tile 4 and Cin % 128 == 0 (host-packed layers): the same U as three bf16 planes
+                            // (wino4_pack_split_host) for the split-bf16 product form; nullptr: fp32 form only
     float* bias = nullptr;  // device, [ntiles*BN]
 };
 size_t wino_packed_elems(int Cout, int Cin, int BN);
@@ -149,6 +151,9 @@ hipError_t wino_gemm_launch(const WinoLayer& L, const float* V, int B, int H, in
 
 size_t wino4_packed_elems(int Cout, int Cin, int BN);
 void wino4_pack_host(const float* w_oihw, int Cout, int Cin, int BN, float* dst);
+// U as three bf16 planes whose sum is wino4_pack_host's float exactly; wino4_split_packed_elems: its size in FLOATS (x 1.5)
+size_t wino4_split_packed_elems(int Cout, int Cin, int BN);
+void wino4_pack_split_host(const float* w_oihw, int Cout, int Cin, int BN, uint16_t* dst);
 // V[36][B*H/4*W/4][C] = B^T d B of x (optionally of relu(x*s + t)); H, W multiples of 4
 hipError_t wino4_transform_launch(const float* x, const float* s, const float* t, int B, int H, int W, int C, float* V,
                                   hipStream_t stream);
