@@ -510,9 +510,10 @@ int eamm_op_conv_wgrad_saved(int device, const float* x_transformed, const float
 // ---- differentiable dense-motion front end and flow head (motion.hip forward kernels, motion_backward.hip) -----------------------
 int eamm_op_antialias_down(int device, const float* source, const float* aa_weight, int B, int H, int W, int inv_scale, float* small,
                            void* stream_) {
-    OP_ENTRY(!source || !small || B < 1 || H < 1 || W < 1 || (inv_scale != 1 && inv_scale != 4) || (inv_scale == 4 && !aa_weight) ||
-                     H % inv_scale || W % inv_scale,
-                 "eamm_op_antialias_down: bad argument (inv_scale 1 | 4: the 13x13 kernel of scale_factor 0.25)");
+    // (inv_scale 2: forward only -- the engines' once-per-clip launch at that scale is compared with this one; the backward entry keeps 1 | 4)
+    OP_ENTRY(!source || !small || B < 1 || H < 1 || W < 1 || (inv_scale != 1 && inv_scale != 2 && inv_scale != 4) ||
+                     (inv_scale != 1 && !aa_weight) || H % inv_scale || W % inv_scale,
+                 "eamm_op_antialias_down: bad argument (inv_scale 1 | 2 | 4: the 13x13 sigma-1.5 buffer at every scale)");
     hipError_t e = antialias_down_launch(source, aa_weight, B, H, W, inv_scale, 4, small, s);
     OP_DONE(e, "eamm_op_antialias_down");
 }
@@ -919,6 +920,138 @@ int eamm_op_deconv4s2_wgrad(int device, const float* x, const float* grad_out, i
              "16-byte aligned)");
     const hipError_t e = deconv4s2_wgrad_launch(x, grad_out, B, H, W, Cin, Cout, grad_weight, grad_bias, workspace, workspace_floats, s);
     OP_DONE(e, "eamm_op_deconv4s2_wgrad");
+}
+
+}  // extern "C"
+
+// ---- the frozen inference path's small kernels, one launch each (conv_first.hip, motion.hip, emotion.hip, audio.hip): what the engines
+// call per frame or once per clip, on the caller's buffers.  Nothing here but the argument checks and the engines' own *_launch calls.
+namespace {
+constexpr int OP_GRID_YZ = 65535;   // a grid's y / z extent
+bool op_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+bool op_count_ok(long long a, long long b, long long c = 1, long long d = 1) {   // positive factors, product below 2^31
+    if (a < 1 || b < 1 || c < 1 || d < 1) return false;
+    const long long lim = 1ll << 31;
+    return a < lim && b < lim && c < lim && d < lim && a * b < lim && a * b * c < lim && a * b * c * d < lim;
+}
+}  // namespace
+
+extern "C" {
+
+int eamm_op_first7(int device, const float* source, int ns, int H, int W, const float* w_host, const float* b_host, int Cout, float* out,
+                   void* stream_) {
+    OP_ENTRY(!source || !w_host || !b_host || !out || !first7_supported(Cout) || !op_count_ok(ns, H, W, Cout),
+             "eamm_op_first7: bad argument (Cout 32 | 64 | 96 | 128, fewer than 2^31 output elements)");
+    OpBuffers t(device, s);
+    std::vector<float> packed((size_t)196 * Cout);
+    first7_pack_host(w_host, Cout, packed.data());
+    float *w = nullptr, *b = nullptr;
+    int rc = upload(&t, &w, packed);
+    if (!rc) rc = upload(&t, &b, std::vector<float>(b_host, b_host + Cout));
+    if (rc) return fail(nullptr, rc, "%s", t.err.c_str());
+    const hipError_t e = first7_launch(source, w, b, ns, H, W, Cout, out, s);
+    OP_DONE(e, "eamm_op_first7");
+}
+
+int eamm_op_motion_head_infer(int device, const float* logits, const float* records, int n, int K, int h, int w, int has_occ,
+                              float* deformation, float* occlusion, float* mask_out, float* occ_out, void* stream_) {
+    OP_ENTRY(!logits || !records || !deformation || n < 1 || n > OP_GRID_YZ || K < 1 || K > 30 || h < 2 || w < 2 || !op_count_ok(n, h, w, 32) ||
+                 (has_occ != 0 && has_occ != 1) || (has_occ && !occlusion) || !op_aligned16(logits) || (reinterpret_cast<uintptr_t>(deformation) & 7),
+             "eamm_op_motion_head_infer: bad argument (1 <= K <= 30, h and w >= 2, n <= 65535, occlusion where has_occ)");
+    const hipError_t e = motion_head_launch(logits, records, n, K, h, w, has_occ, deformation, occlusion, mask_out, occ_out, s);
+    OP_DONE(e, "eamm_op_motion_head_infer");
+}
+
+int eamm_op_motion_head_rowsplit(int device, const float* part, int PS, int NC, const float* bias, const float* records, int n, int K, int h,
+                                 int w, int has_occ, float* deformation, float* occlusion, float* mask_out, float* occ_out, void* stream_) {
+    OP_ENTRY(!part || !bias || !records || !deformation || n < 1 || n > OP_GRID_YZ || K < 1 || K > 30 || h < 2 || h > OP_GRID_YZ || w < 2 ||
+                 (has_occ != 0 && has_occ != 1) || (has_occ && !occlusion) || NC > 32 || NC < K + 1 + has_occ || PS < 7 * NC ||
+                 !op_count_ok(n, h, w, PS) || !op_aligned16(part) || (reinterpret_cast<uintptr_t>(deformation) & 7),
+             "eamm_op_motion_head_rowsplit: bad argument (1 <= K <= 30, K + 1 + has_occ <= NC <= 32, PS >= 7 NC, h and w >= 2, n and h <= "
+             "65535, occlusion where has_occ)");
+    const hipError_t e = motion_head_rowsplit_launch(part, PS, NC, bias, records, n, K, h, w, has_occ, deformation, occlusion, mask_out, occ_out, s);
+    OP_DONE(e, "eamm_op_motion_head_rowsplit");
+}
+
+int eamm_op_final_shift_sum(int device, const float* part, const float* bias, int n, int H, int W, float* out, void* stream_) {
+    OP_ENTRY(!part || !bias || !out || n < 1 || n > OP_GRID_YZ || H < 1 || H > OP_GRID_YZ || W < 1 || !op_count_ok(n, H, W, 32) || !op_aligned16(part),
+             "eamm_op_final_shift_sum: bad argument (n and H <= 65535, fewer than 2^31 partial products)");
+    const hipError_t e = final_shift_sum_launch(part, bias, n, H, W, out, s);
+    OP_DONE(e, "eamm_op_final_shift_sum");
+}
+
+int eamm_op_to_u8(int device, const float* prediction, int n, int H, int W, uint8_t* out, void* stream_) {
+    OP_ENTRY(!prediction || !out || !op_count_ok(n, H, W, 3), "eamm_op_to_u8: bad argument");
+    const hipError_t e = to_u8_launch(prediction, n, H, W, out, s);
+    OP_DONE(e, "eamm_op_to_u8");
+}
+
+int eamm_op_warp_image(int device, const float* source, const float* deformation, int n, int ns, int H, int W, int h, int w, int src_planes,
+                       int channels, float* out, void* stream_) {
+    OP_ENTRY(!source || !deformation || !out || n < 1 || (ns != 1 && ns != n) || channels < 1 || channels > src_planes ||
+                 !op_count_ok(n, H, W, src_planes) || !op_count_ok(n, h, w, 2) || (reinterpret_cast<uintptr_t>(deformation) & 7),
+             "eamm_op_warp_image: bad argument (ns 1 | n, 1 <= channels <= src_planes)");
+    const hipError_t e = warp_image_launch(source, deformation, n, ns, H, W, h, w, out, s, src_planes, channels);
+    OP_DONE(e, "eamm_op_warp_image");
+}
+
+int eamm_op_source_prepare(int device, const float* source, const float* aa_weight, int ns, int H, int W, int inv_scale, int Cpad,
+                           float* source_nhwc, float* small, void* stream_) {
+    OP_ENTRY(!source || !source_nhwc || !small || (inv_scale != 1 && inv_scale != 2 && inv_scale != 4) || (inv_scale != 1 && !aa_weight) ||
+                 Cpad < 4 || (Cpad & 3) || !op_count_ok(ns, H, W, Cpad) || H % inv_scale || W % inv_scale || !op_aligned16(source_nhwc) ||
+                 !op_aligned16(small),
+             "eamm_op_source_prepare: bad argument (inv_scale 1 | 2 | 4 dividing H and W, Cpad a multiple of 4)");
+    const hipError_t e = source_prepare_launch(source, aa_weight, ns, H, W, inv_scale, Cpad, source_nhwc, small, s);
+    OP_DONE(e, "eamm_op_source_prepare");
+}
+
+int eamm_op_broadcast_features(int device, const float* feat, int n, int ns, int hf, int wf, int C, float* out, float* out2, const float* scale,
+                               const float* shift, void* stream_) {
+    OP_ENTRY(!feat || !out || n < 1 || (ns != 1 && ns != n) || C < 4 || (C & 3) || !op_count_ok(n, hf, wf, C) || (out2 && (!scale || !shift)) ||
+                 !op_aligned16(feat) || !op_aligned16(out) || !op_aligned16(out2) || !op_aligned16(scale) || !op_aligned16(shift),
+             "eamm_op_broadcast_features: bad argument (ns 1 | n, C a multiple of 4, scale and shift where out2, 16-byte aligned)");
+    const hipError_t e = broadcast_features_launch(feat, n, ns, hf, wf, C, out, out2, scale, shift, s);
+    OP_DONE(e, "eamm_op_broadcast_features");
+}
+
+int eamm_op_nchw_to_nhwc_pad(int device, const float* src, int B, int C, int planes, int H, int W, int Cpad, float* dst, void* stream_) {
+    OP_ENTRY(!src || !dst || C < 1 || planes < C || Cpad < C || !op_count_ok(B, H, W, Cpad) || !op_count_ok(B, H, W, planes),
+             "eamm_op_nchw_to_nhwc_pad: bad argument (1 <= C <= planes, C <= Cpad)");
+    const hipError_t e = nchw_to_nhwc_pad_launch(src, B, C, H, W, Cpad, dst, s, planes);
+    OP_DONE(e, "eamm_op_nchw_to_nhwc_pad");
+}
+
+int eamm_op_emo_avgpool(int device, const float* x, int B, int P, int C, float* out, void* stream_) {
+    OP_ENTRY(!x || !out || !op_count_ok(B, P, C), "eamm_op_emo_avgpool: bad argument");
+    const hipError_t e = emo_avgpool_launch(x, B, P, C, out, s);
+    OP_DONE(e, "eamm_op_emo_avgpool");
+}
+
+int eamm_op_emo_embed(int device, const float* value, const float* jacobian, int B, float* out, void* stream_) {
+    OP_ENTRY(!value || !jacobian || !out || !op_count_ok(B, 1260), "eamm_op_emo_embed: bad argument");
+    const hipError_t e = emo_embed_launch(value, jacobian, B, out, s);
+    OP_DONE(e, "eamm_op_emo_embed");
+}
+
+int eamm_op_emo_linear(int device, const float* x0, int K0, const float* x1, int K1, const float* wt, const float* bias, int O, int B, int relu,
+                       float* out, void* stream_) {
+    OP_ENTRY(!x0 || !wt || !bias || !out || K0 < 1 || K1 < 0 || (K1 > 0 && !x1) || K0 > 2048 || K1 > 2048 || K0 + K1 > 2048 || B < 1 ||
+                 B > 8 * OP_GRID_YZ || !op_count_ok(K0 + K1, O) || !op_count_ok(B, O) || (relu != 0 && relu != 1),
+             "eamm_op_emo_linear: bad argument (K0 >= 1, K1 >= 0 with x1 where K1 > 0, K0 + K1 <= 2048)");
+    const hipError_t e = emo_linear_launch(x0, K0, x1, K1, wt, bias, O, B, relu, out, s);
+    OP_DONE(e, "eamm_op_emo_linear");
+}
+
+int eamm_op_audio_conv1(int device, const float* x, const float* w, const float* b, int F, int H, int W, float* out, void* stream_) {
+    OP_ENTRY(!x || !w || !b || !out || !op_count_ok(F, H, W, 64), "eamm_op_audio_conv1: bad argument");
+    const hipError_t e = audio_conv1_launch(x, w, b, F, H, W, out, s);
+    OP_DONE(e, "eamm_op_audio_conv1");
+}
+
+int eamm_op_audio_scale(int device, float* x, size_t n, float scale, void* stream_) {
+    OP_ENTRY(!x || n < 1 || n > ((size_t)1 << 39), "eamm_op_audio_scale: bad argument (1 <= n <= 2^39)");
+    const hipError_t e = audio_scale_launch(x, n, scale, s);
+    OP_DONE(e, "eamm_op_audio_scale");
 }
 
 }  // extern "C"

@@ -634,8 +634,8 @@ int eamm_op_conv_wgrad_saved(int device, const float* x_transformed, const float
  * pointers, per-pair sources (n sources for n driving frames, the training batch of train.py:133); asynchronous on `stream`.
  *   eamm_op_antialias_down            AntiAliasInterpolation2d (modules/util.py:1044-1052): source NCHW [B,3,H,W], the module's
  *                                     [3,1,13,13] buffer -> small NHWC [B,H/s,W/s,4] (RGB + a zero); inv_scale 4 (scale_factor 0.25)
- *                                     or 1 (a copy, util.py:1047-1048)
- *   eamm_op_antialias_down_backward   grad_small [B,h,w,4] -> grad_source [B,3,H,W]
+ *                                     or 1 (a copy, util.py:1047-1048); the forward also takes 2 (the same buffer: its sigma is fixed)
+ *   eamm_op_antialias_down_backward   grad_small [B,h,w,4] -> grad_source [B,3,H,W]; inv_scale 4 | 1
  *   eamm_op_kp_records                records [n,K,8] = kp_driving.xy, kp_source.xy, J = jac_source inverse(jac_driving)
  *                                     (dense_motion.py:47-67; jacobians NULL: identity); *singular_flag (device int) is set when
  *                                     a driving jacobian is singular (torch.inverse raises)
@@ -792,6 +792,63 @@ int eamm_op_deconv4s2_dgrad(int device, const float* grad_out, int B, int H, int
 size_t eamm_op_deconv4s2_wgrad_workspace_floats(int B, int H, int W, int Cin, int Cout);
 int eamm_op_deconv4s2_wgrad(int device, const float* x, const float* grad_out, int B, int H, int W, int Cin, int Cout, float* grad_weight,
                             float* grad_bias, float* workspace, size_t workspace_floats, void* stream);
+
+/*
+ * The frozen inference path's small kernels at OPERATOR level: one launch each of what the engines run per frame or once per clip,
+ * on the caller's device buffers (the tests compare each with a float64 reference at shapes the whole-model fixtures do not
+ * reach).  Additive entries (ABI 6 unchanged).  fp32, device pointers unless named *_host; asynchronous on `stream`; a bad argument
+ * is refused with EAMM_ERR_ARG before any launch.
+ *   eamm_op_first7                the generator's first block, relu(conv7x7_same(source NCHW [ns,3,H,W], w_host [Cout,3,7,7]) + b_host
+ *                                 [Cout]) -> out NHWC [ns,H,W,Cout] on the dedicated 3-channel kernel; the HOST filter (BatchNorm
+ *                                 folded) is packed as the engine packs it; Cout 32 | 64 | 96 | 128.  Waits for `stream` before it
+ *                                 returns (it frees its packed filter).
+ *   eamm_op_motion_head_infer     the flow head's inference kernel on logits NHWC [n,h,w,32] (channels 0..K the mask logits, K + 1 the
+ *                                 occlusion logit, the rest unread), records [n,K,8] (eamm_op_kp_records): deformation [n,h,w,2],
+ *                                 occlusion [n,h,w] (has_occ), and, unless NULL, mask_out [n,K+1,h,w] and occ_out [n,1,h,w].  K <= 30.
+ *   eamm_op_motion_head_rowsplit  the same from the 7x1 convolution's partial products part [n,h,w,PS], channel dx * NC + co (channels
+ *                                 >= 7 NC unread): logit co = bias[co] + sum_dx part[y, x + dx - 3, dx * NC + co], zero outside the row.
+ *                                 K + 1 + has_occ <= NC <= 32, PS >= 7 NC.
+ *   eamm_op_final_shift_sum       out NCHW [n,3,H,W] = sigmoid(bias[co] + sum_dx part[y, x + dx - 3, dx * 3 + co]) from part [n,H,W,32]
+ *                                 (channels 21..31 unread).
+ *   eamm_op_to_u8                 prediction NCHW [n,3,H,W] -> out uint8 [n,H,W,3]: rint(p * 255) clamped to 0..255.
+ *   eamm_op_warp_image            the `deformed` output: deformation [n,h,w,2] resized bilinearly to (H,W) unless equal, then
+ *                                 grid_sample(bilinear, zeros, align_corners=False) of the first `channels` of source's src_planes
+ *                                 planes, source [ns,src_planes,H,W] with ns 1 | n -> out [n,channels,H,W].
+ *   eamm_op_source_prepare        once per clip: source NCHW [ns,3,H,W] -> source_nhwc [ns,H,W,Cpad] (RGB + zeros) and `small`
+ *                                 [ns,H/s,W/s,4] = eamm_op_antialias_down's result; inv_scale s 1 | 2 | 4, aa_weight [3,1,13,13].
+ *   eamm_op_broadcast_features    a generator without a motion network: out [n,hf,wf,C] = feat [ns,hf,wf,C] frame i (ns = n) or frame 0
+ *                                 (ns = 1); out2 (or NULL) = relu(out * scale[c] + shift[c]), one fused multiply-add.  C a multiple of 4.
+ *   eamm_op_nchw_to_nhwc_pad      src [B,planes,H,W] -> dst [B,H,W,Cpad]: the first C planes, zeros in channels C..Cpad-1.
+ *   eamm_op_emo_avgpool           NHWC x [B,P,C] -> out [B,C], the mean over the P pixels.
+ *   eamm_op_emo_embed             value [B,10,2], jacobian [B,10,2,2] -> out [B,1260]: per key point the six numbers d, then sin / cos of
+ *                                 d * 2^f, f = 0..9, interleaved over the six ([d6, sin6, cos6, sin6 (2d), ...]).
+ *   eamm_op_emo_linear            out [B,O] = act(bias + [x0 [B,K0] | x1 [B,K1]] wt), wt TRANSPOSED [K0+K1][O]; x1 NULL with K1 = 0;
+ *                                 relu 0 | 1; K0 + K1 <= 2048.
+ *   eamm_op_audio_conv1           AT_net2's first block: relu(conv3x3_same(x [F,H,W], w) + b) -> out NHWC [F,H,W,64]; w is the folded
+ *                                 filter TRANSPOSED [9][64] (tap dy * 3 + dx major), b [64].
+ *   eamm_op_audio_scale           x[i] *= scale in place, n floats.
+ */
+int eamm_op_first7(int device, const float* source, int ns, int H, int W, const float* w_host, const float* b_host, int Cout, float* out,
+                   void* stream);
+int eamm_op_motion_head_infer(int device, const float* logits, const float* records, int n, int K, int h, int w, int has_occ,
+                              float* deformation, float* occlusion, float* mask_out, float* occ_out, void* stream);
+int eamm_op_motion_head_rowsplit(int device, const float* part, int PS, int NC, const float* bias, const float* records, int n, int K, int h,
+                                 int w, int has_occ, float* deformation, float* occlusion, float* mask_out, float* occ_out, void* stream);
+int eamm_op_final_shift_sum(int device, const float* part, const float* bias, int n, int H, int W, float* out, void* stream);
+int eamm_op_to_u8(int device, const float* prediction, int n, int H, int W, uint8_t* out, void* stream);
+int eamm_op_warp_image(int device, const float* source, const float* deformation, int n, int ns, int H, int W, int h, int w, int src_planes,
+                       int channels, float* out, void* stream);
+int eamm_op_source_prepare(int device, const float* source, const float* aa_weight, int ns, int H, int W, int inv_scale, int Cpad,
+                           float* source_nhwc, float* small, void* stream);
+int eamm_op_broadcast_features(int device, const float* feat, int n, int ns, int hf, int wf, int C, float* out, float* out2, const float* scale,
+                               const float* shift, void* stream);
+int eamm_op_nchw_to_nhwc_pad(int device, const float* src, int B, int C, int planes, int H, int W, int Cpad, float* dst, void* stream);
+int eamm_op_emo_avgpool(int device, const float* x, int B, int P, int C, float* out, void* stream);
+int eamm_op_emo_embed(int device, const float* value, const float* jacobian, int B, float* out, void* stream);
+int eamm_op_emo_linear(int device, const float* x0, int K0, const float* x1, int K1, const float* wt, const float* bias, int O, int B, int relu,
+                       float* out, void* stream);
+int eamm_op_audio_conv1(int device, const float* x, const float* w, const float* b, int F, int H, int W, float* out, void* stream);
+int eamm_op_audio_scale(int device, float* x, size_t n, float scale, void* stream);
 
 #ifdef __cplusplus
 }
