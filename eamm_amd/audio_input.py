@@ -148,14 +148,11 @@ def _mfcc(w: torch.Tensor, pad: int) -> torch.Tensor:
     if not w.is_cuda:
         rows = [mfcc_reference(w[i].detach().to(torch.float64).numpy(), pad) for i in range(n)]
         return torch.from_numpy(np.stack(rows).astype(np.float32))
-    from . import _lib
-    from ._handle import ptr, stream_ptr
-    L = _lib.lib()
+    from . import _lib, _op
     x = w.detach().to(torch.float32).contiguous()
-    F = int(L.eamm_op_mfcc_frames(S, int(pad)))
+    F = int(_lib.lib().eamm_op_mfcc_frames(S, int(pad)))
     out = torch.empty((n, F, NCEP), device=x.device, dtype=torch.float32)
-    with torch.cuda.device(x.device):
-        _lib.check(L.eamm_op_mfcc(x.device.index, ptr(x), S, n, S, int(pad), ptr(out), stream_ptr(x.device)), None)
+    _op.call("mfcc", x.device, x, S, n, S, int(pad), out)
     return out
 
 

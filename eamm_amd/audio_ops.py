@@ -24,39 +24,20 @@ from typing import Optional
 import torch
 import torch.nn.functional as F
 
-from . import _lib
-from ._handle import ptr, stream_ptr
+from . import _lib, _op
+from ._op import CHANNEL_GRANULE, round_up
 
-_G = 32          # channel granule of the convolution kernels
 HIDDEN = 256     # the LSTM kernels' hidden size
 MAX_CLIPS = 8    # ... and their largest batch
-
-
-def _need_gpu(t: torch.Tensor, what: str):
-    if t.device.type != "cuda":
-        raise RuntimeError(f"eamm_amd.audio_ops.{what} runs only on a ROCm GPU (there is no CPU fallback)")
-    if t.dtype != torch.float32:
-        raise RuntimeError(f"{what}: float32 tensors only, got {t.dtype}")
-
-
-def _check(code):
-    _lib.check(code, None)
-
-
-def _work(n: int, dev) -> torch.Tensor:
-    return torch.empty(max(1, n), dtype=torch.float32, device=dev)
-
-
-def _round_up(n: int, m: int) -> int:
-    return (n + m - 1) // m * m
 
 
 def lstm_check(device) -> None:
     """Waits for the current stream of ``device`` and raises ``EammError`` if an LSTM operator's recurrence timed out on it (a
     workgroup waited longer than the limit for another; the outputs then hold NaN from the step it stopped at)."""
     device = torch.device(device)
-    with torch.cuda.device(device):
-        _check(_lib.lib().eamm_op_lstm_check(device.index if device.index is not None else torch.cuda.current_device(), stream_ptr(device)))
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    _op.call("lstm_check", device)
 
 
 class _LstmLayerFunction(torch.autograd.Function):
@@ -65,13 +46,11 @@ class _LstmLayerFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xproj, w_hh):
         n, t, _ = xproj.shape
-        L = _lib.lib()
         dev = xproj.device
         y = torch.empty(n, t, HIDDEN, dtype=torch.float32, device=dev)
-        work = _work(L.eamm_op_lstm_workspace_floats(n, t), dev)     # the call's own W_hh image, state and hand-off words
+        work = _op.workspace("lstm", dev, n, t)     # the call's own W_hh image, state and hand-off words
         w = w_hh.detach().contiguous()
-        with torch.cuda.device(dev):
-            _check(L.eamm_op_lstm_forward(dev.index, ptr(xproj), ptr(w), n, t, ptr(y), ptr(work), work.numel(), stream_ptr(dev)))
+        _op.call("lstm_forward", dev, xproj, w, n, t, y, work=work)
         ctx.save_for_backward(xproj, w_hh, y)
         return y
 
@@ -79,7 +58,6 @@ class _LstmLayerFunction(torch.autograd.Function):
     def backward(ctx, grad_y):
         xproj, w_hh, y = ctx.saved_tensors
         n, t, _ = xproj.shape
-        L = _lib.lib()
         dev = xproj.device
         w = w_hh.detach().contiguous()
         grad_y = grad_y.contiguous()
@@ -87,11 +65,9 @@ class _LstmLayerFunction(torch.autograd.Function):
         gates = torch.addmm(xproj.detach().reshape(n * t, 4 * HIDDEN), h_prev, w.t()).view(n, t, 4 * HIDDEN).contiguous()
         c = torch.empty(n, t, HIDDEN, dtype=torch.float32, device=dev)
         gx = torch.empty(n, t, 4 * HIDDEN, dtype=torch.float32, device=dev)
-        work = _work(L.eamm_op_lstm_backward_workspace_floats(n, t), dev)
-        with torch.cuda.device(dev):
-            _check(L.eamm_op_lstm_scan(dev.index, ptr(gates), n, t, ptr(c), stream_ptr(dev)))
-            _check(L.eamm_op_lstm_backward(dev.index, ptr(gates), ptr(c), ptr(w), ptr(grad_y), n, t, ptr(gx), ptr(work), work.numel(),
-                                           stream_ptr(dev)))
+        work = _op.workspace("lstm_backward", dev, n, t)
+        _op.call("lstm_scan", dev, gates, n, t, c)
+        _op.call("lstm_backward", dev, gates, c, w, grad_y, n, t, gx, work=work)
         gw = torch.matmul(gx.reshape(n * t, 4 * HIDDEN).t(), h_prev) if ctx.needs_input_grad[1] else None
         return (gx if ctx.needs_input_grad[0] else None), gw
 
@@ -103,15 +79,12 @@ class _Deconv4s2Function(torch.autograd.Function):
     def forward(ctx, x, weight, bias, bias_grad_is_zero):
         b, h, w, cin = x.shape
         cout = weight.shape[1]
-        L = _lib.lib()
         dev = x.device
         out = torch.empty(b, 2 * h, 2 * w, cout, dtype=torch.float32, device=dev)
-        work = _work(L.eamm_op_deconv4s2_workspace_floats(b, h, w, cin, cout), dev)
+        work = _op.workspace("deconv4s2", dev, b, h, w, cin, cout)
         wt = weight.detach().contiguous()
         bs = bias.detach().contiguous() if bias is not None else None
-        with torch.cuda.device(dev):
-            _check(L.eamm_op_deconv4s2(dev.index, ptr(x), b, h, w, cin, ptr(wt), ptr(bs), cout, ptr(out), ptr(work), work.numel(),
-                                       stream_ptr(dev)))
+        _op.call("deconv4s2", dev, x, b, h, w, cin, wt, bs, cout, out, work=work)
         ctx.save_for_backward(x, weight)
         ctx.has_bias = bias is not None
         ctx.bias_grad_is_zero = bool(bias_grad_is_zero)
@@ -122,28 +95,24 @@ class _Deconv4s2Function(torch.autograd.Function):
         x, weight = ctx.saved_tensors
         b, h, w, cin = x.shape
         cout = weight.shape[1]
-        L = _lib.lib()
         dev = x.device
         grad_out = grad_out.contiguous()
         gx = gw = gb = None
         want_b = ctx.has_bias and ctx.needs_input_grad[2]
-        with torch.cuda.device(dev):
-            if ctx.needs_input_grad[0]:
-                gx = torch.empty_like(x)
-                work = _work(L.eamm_op_deconv4s2_dgrad_workspace_floats(b, h, w, cin, cout), dev)
-                wt = weight.detach().contiguous()
-                _check(L.eamm_op_deconv4s2_dgrad(dev.index, ptr(grad_out), b, h, w, cin, ptr(wt), cout, ptr(gx), ptr(work), work.numel(),
-                                                 stream_ptr(dev)))
-            if ctx.needs_input_grad[1] or want_b:
-                gw = torch.empty_like(weight, memory_format=torch.contiguous_format)
-                if want_b:   # in front of a batch-statistics BatchNorm the bias gradient is exactly zero: no reduction
-                    gb = torch.zeros(cout, dtype=torch.float32, device=dev) if ctx.bias_grad_is_zero else torch.empty(cout, dtype=torch.float32, device=dev)
-                work = _work(L.eamm_op_deconv4s2_wgrad_workspace_floats(b, h, w, cin, cout), dev)
-                _check(L.eamm_op_deconv4s2_wgrad(dev.index, ptr(x), ptr(grad_out), b, h, w, cin, cout, ptr(gw),
-                                                 ptr(gb) if (want_b and not ctx.bias_grad_is_zero) else None, ptr(work), work.numel(),
-                                                 stream_ptr(dev)))
-                if not ctx.needs_input_grad[1]:
-                    gw = None
+        if ctx.needs_input_grad[0]:
+            gx = torch.empty_like(x)
+            work = _op.workspace("deconv4s2_dgrad", dev, b, h, w, cin, cout)
+            wt = weight.detach().contiguous()
+            _op.call("deconv4s2_dgrad", dev, grad_out, b, h, w, cin, wt, cout, gx, work=work)
+        if ctx.needs_input_grad[1] or want_b:
+            gw = torch.empty_like(weight, memory_format=torch.contiguous_format)
+            if want_b:   # in front of a batch-statistics BatchNorm the bias gradient is exactly zero: no reduction
+                gb = torch.zeros(cout, dtype=torch.float32, device=dev) if ctx.bias_grad_is_zero else torch.empty(cout, dtype=torch.float32, device=dev)
+            work = _op.workspace("deconv4s2_wgrad", dev, b, h, w, cin, cout)
+            _op.call("deconv4s2_wgrad", dev, x, grad_out, b, h, w, cin, cout, gw, gb if (want_b and not ctx.bias_grad_is_zero) else None,
+                     work=work)
+            if not ctx.needs_input_grad[1]:
+                gw = None
         return gx, gw, gb, None
 
 
@@ -154,8 +123,7 @@ class _MaxPool3Function(torch.autograd.Function):
     def forward(ctx, x, sy, sx):
         b, h, w, c = x.shape
         out = torch.empty(b, (h - 3) // sy + 1, (w - 3) // sx + 1, c, dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            _check(_lib.lib().eamm_op_audio_maxpool(x.device.index, ptr(x), b, h, w, c, sy, sx, ptr(out), stream_ptr(x.device)))
+        _op.call("audio_maxpool", x.device, x, b, h, w, c, sy, sx, out)
         ctx.save_for_backward(x)
         ctx.strides = (sy, sx)
         return out
@@ -167,9 +135,7 @@ class _MaxPool3Function(torch.autograd.Function):
         sy, sx = ctx.strides
         grad_out = grad_out.contiguous()
         gx = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            _check(_lib.lib().eamm_op_audio_maxpool_backward(x.device.index, ptr(x), ptr(grad_out), b, h, w, c, sy, sx, ptr(gx),
-                                                             stream_ptr(x.device)))
+        _op.call("audio_maxpool_backward", x.device, x, grad_out, b, h, w, c, sy, sx, gx)
         return gx, None, None
 
 
@@ -189,7 +155,7 @@ def lstm_layer(xproj: torch.Tensor, w_hh: torch.Tensor) -> torch.Tensor:
         raise ValueError(f"lstm_layer: w_hh must be [{4 * HIDDEN},{HIDDEN}], got {tuple(getattr(w_hh, 'shape', ()))}")
     if n * t * 4 * HIDDEN >= 2 ** 31:
         raise ValueError("lstm_layer: fewer than 2^31 gate values")
-    _need_gpu(xproj, "lstm_layer")
+    _op.need_gpu(xproj, "audio_ops", "lstm_layer")
     if w_hh.device != xproj.device or w_hh.dtype != torch.float32:
         raise RuntimeError("lstm_layer: w_hh must be float32 on the input's device")
     return _LstmLayerFunction.apply(xproj.contiguous(), w_hh)
@@ -215,10 +181,10 @@ def conv_transpose4s2_nhwc(x: torch.Tensor, weight: torch.Tensor, bias: Optional
         raise ValueError(f"conv_transpose4s2_nhwc: empty input {tuple(x.shape)}")
     if bias is not None and tuple(bias.shape) != (cout,):
         raise ValueError(f"conv_transpose4s2_nhwc: bias must be [{cout}], got {tuple(bias.shape)}")
-    cin_p, cout_p = _round_up(cin, _G), _round_up(cout, _G)
+    cin_p, cout_p = round_up(cin, CHANNEL_GRANULE), round_up(cout, CHANNEL_GRANULE)
     if max(b * h * w * cin_p, 4 * b * h * w * cout_p) * 4 >= 2 ** 32 - 16:
         raise ValueError(f"conv_transpose4s2_nhwc: input {tuple(x.shape)} / output beyond the kernels' 32-bit byte offsets")
-    _need_gpu(x, "conv_transpose4s2_nhwc")
+    _op.need_gpu(x, "audio_ops", "conv_transpose4s2_nhwc")
     if weight.device != x.device or (bias is not None and bias.device != x.device):
         raise RuntimeError("conv_transpose4s2_nhwc: weight, bias and input are on different devices")
     if cin_p != cin:
@@ -247,5 +213,5 @@ def maxpool3_nhwc(x: torch.Tensor, sy: int, sx: int) -> torch.Tensor:
         raise ValueError(f"maxpool3_nhwc: channels a multiple of 4, got C = {c}")
     if x.numel() >= 2 ** 31:
         raise ValueError("maxpool3_nhwc: fewer than 2^31 elements")
-    _need_gpu(x, "maxpool3_nhwc")
+    _op.need_gpu(x, "audio_ops", "maxpool3_nhwc")
     return _MaxPool3Function.apply(x.contiguous(), int(sy), int(sx))

@@ -18,16 +18,17 @@ CPU fallback.
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import Optional
 
 import torch
 
-from . import _lib
-from ._handle import ptr as _ptr, stream_ptr as _stream   # (under the names this module and the tests that bind raw entries use)
+from . import _lib, _op
+from ._handle import ptr as _ptr, stream_ptr as _stream   # noqa: F401  (importable from here under these names, as before)
+from ._op import CHANNEL_GRANULE
 
-_CONV_BK = 32   # channel granule of the implicit-GEMM loaders (conv_common.h CONV_BK)
 _NO_OFFSET = C.c_size_t(-1).value
-_SAVE_TRANSFORM = __import__("os").environ.get("EAMM_SAVE_TRANSFORM", "1") != "0"
+_SAVE_TRANSFORM = os.environ.get("EAMM_SAVE_TRANSFORM", "1") != "0"
 
 
 # The weight gradient of a convolution and its data gradient are independent given (x, dY).  EAMM_WGRAD_STREAM=1 runs the weight
@@ -40,7 +41,6 @@ _SIDE_STREAMS = {}
 
 
 def _wgrad_stream(dev: torch.device):
-    import os
     if os.environ.get("EAMM_WGRAD_STREAM", "0") != "1" or torch.cuda.is_current_stream_capturing():
         return None
     key = torch.cuda.current_stream(dev)      # (a Stream hashes and compares by device and handle)
@@ -48,13 +48,6 @@ def _wgrad_stream(dev: torch.device):
     if st is None:
         st = _SIDE_STREAMS[key] = torch.cuda.Stream(device=dev)
     return st
-
-
-def _need_gpu(t: torch.Tensor, what: str):
-    if t.device.type != "cuda":
-        raise RuntimeError(f"eamm_amd.autograd_ops.{what} runs only on a ROCm GPU (there is no CPU fallback)")
-    if t.dtype != torch.float32:
-        raise RuntimeError(f"{what}: float32 tensors only, got {t.dtype}")
 
 
 class _WarpFunction(torch.autograd.Function):
@@ -65,9 +58,7 @@ class _WarpFunction(torch.autograd.Function):
         n, h, w = deformation.shape[:3]
         ns, c = feat.shape[0], feat.shape[3]
         out = torch.empty(n, h, w, c, dtype=torch.float32, device=feat.device)
-        with torch.cuda.device(feat.device):
-            _lib.check(_lib.lib().eamm_op_warp(feat.device.index, _ptr(feat), _ptr(deformation), _ptr(occlusion), n, ns, h, w, c, h, w,
-                                               _ptr(out), 0, None, _stream(feat.device)), None)
+        _op.call("warp", feat.device, feat, deformation, occlusion, n, ns, h, w, c, h, w, out, 0, None)
         ctx.save_for_backward(feat, deformation, occlusion)
         return out
 
@@ -83,10 +74,7 @@ class _WarpFunction(torch.autograd.Function):
         go = torch.empty_like(occlusion) if (occlusion is not None and need[2]) else None
         if gf is None and gd is None and go is None:
             return None, None, None
-        with torch.cuda.device(feat.device):
-            _lib.check(_lib.lib().eamm_op_warp_backward(feat.device.index, _ptr(feat), _ptr(deformation), _ptr(occlusion),
-                                                        _ptr(grad_out), n, ns, h, w, c, _ptr(gf), _ptr(gd), _ptr(go),
-                                                        _stream(feat.device)), None)
+        _op.call("warp_backward", feat.device, feat, deformation, occlusion, grad_out, n, ns, h, w, c, gf, gd, go)
         return gf, gd, go
 
 
@@ -96,7 +84,7 @@ def warp(features: torch.Tensor, deformation: torch.Tensor, occlusion: Optional[
     features NCHW [n,C,h,w] or [1,C,h,w] (one source for all frames); deformation [n,h,w,2]; occlusion [n,1,h,w] or None;
     flow and occlusion at the features' resolution (the reference's bilinear resize of a coarser flow stays a torch op in
     front of this one).  Returns NCHW [n,C,h,w]."""
-    _need_gpu(features, "warp")
+    _op.need_gpu(features, "autograd_ops", "warp")
     n, h, w, two = deformation.shape
     if two != 2 or features.shape[2:] != (h, w) or features.shape[0] not in (1, n) or features.shape[1] % 8:
         raise ValueError(f"warp: features {tuple(features.shape)} / deformation {tuple(deformation.shape)} mismatch "
@@ -121,17 +109,14 @@ class _Conv2dSameFunction(torch.autograd.Function):
         b, h, w, cin = x.shape
         cout = weight.shape[1] if transposed else weight.shape[0]
         kh, kw = weight.shape[2:]
-        L = _lib.lib()
         out = torch.empty(b, h, w, cout, dtype=torch.float32, device=x.device)
-        nwork = L.eamm_op_conv_dev_workspace_floats(b, h, w, cin, cout, kh, kw)
+        nwork = _lib.lib().eamm_op_conv_dev_workspace_floats(b, h, w, cin, cout, kh, kw)
         if nwork == 0:
             raise ValueError(f"conv2d_same: unsupported convolution {tuple(x.shape)} x {tuple(weight.shape)}")
         work = torch.empty(nwork, dtype=torch.float32, device=x.device)
         wt = weight.detach().contiguous()
         bt = bias.detach().contiguous() if bias is not None else None
-        with torch.cuda.device(x.device):
-            _lib.check(L.eamm_op_conv_dev(x.device.index, _ptr(x), b, h, w, cin, _ptr(wt), _ptr(bt), cout, kh, kw, int(transposed),
-                                          _ptr(out), _ptr(work), nwork, _stream(x.device)), None)
+        _op.call("conv_dev", x.device, x, b, h, w, cin, wt, bt, cout, kh, kw, int(transposed), out, work=work)
         return (out, work) if keep_work else out
 
     @staticmethod
@@ -160,28 +145,23 @@ class _Conv2dSameFunction(torch.autograd.Function):
         cout, _, kh, kw = weight.shape
         gx = gw = gb = side = None
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-            L = _lib.lib()
             gw = torch.empty_like(weight, memory_format=torch.contiguous_format)
             # a bias that feeds a batch-statistics BatchNorm directly has a gradient of exactly zero (the mean is subtracted
             # again): the caller says so and the sum over the pixels is not computed (autograd's own value there is rounding noise)
             zero_gb = ctx.has_bias and ctx.bias_grad_is_zero
             gb = torch.empty(cout, dtype=torch.float32, device=x.device) if (ctx.has_bias and not zero_gb) else None
-            nwork = L.eamm_op_conv_wgrad_workspace_floats(b, h, w, cin, cout, kh, kw)
-            work = torch.empty(max(1, nwork), dtype=torch.float32, device=x.device)
+            work = _op.workspace("conv_wgrad", x.device, b, h, w, cin, cout, kh, kw)
             if zero_gb:
                 gb0 = torch.zeros(cout, dtype=torch.float32, device=x.device)
             side = _wgrad_stream(x.device) if ctx.needs_input_grad[0] else None
             cur = torch.cuda.current_stream(x.device)
             if side is not None:
                 side.wait_stream(cur)            # x, dY and the buffers above are ready in the current stream's order
-            with torch.cuda.device(x.device):
-                if saved_work is not None:
-                    v = C.c_void_p(saved_work.data_ptr() + 4 * ctx.v_offset)
-                    _lib.check(L.eamm_op_conv_wgrad_saved(x.device.index, v, _ptr(grad_out), b, h, w, cin, cout, _ptr(gw), _ptr(gb),
-                                                          _ptr(work), nwork, _stream(stream=side or cur)), None)
-                else:
-                    _lib.check(L.eamm_op_conv_wgrad(x.device.index, _ptr(x), _ptr(grad_out), b, h, w, cin, cout, kh, kw, _ptr(gw), _ptr(gb),
-                                                    _ptr(work), nwork, _stream(stream=side or cur)), None)
+            if saved_work is not None:
+                v = C.c_void_p(saved_work.data_ptr() + 4 * ctx.v_offset)
+                _op.call("conv_wgrad_saved", x.device, v, grad_out, b, h, w, cin, cout, gw, gb, work=work, stream=side)
+            else:
+                _op.call("conv_wgrad", x.device, x, grad_out, b, h, w, cin, cout, kh, kw, gw, gb, work=work, stream=side)
             if zero_gb:
                 gb = gb0
         if ctx.needs_input_grad[0]:
@@ -202,14 +182,10 @@ class _FirstConv7Function(torch.autograd.Function):
         ctx.bias_grad_is_zero = bool(bias_grad_is_zero)
         b, h, w, _ = x4.shape
         n = weight.shape[0]
-        L = _lib.lib()
         out = torch.empty(b, h, w, n, dtype=torch.float32, device=x4.device)
-        nwork = L.eamm_op_conv7_thin_workspace_floats(b, h, w, n)
-        work = torch.empty(nwork, dtype=torch.float32, device=x4.device)
+        work = _op.workspace("conv7_thin", x4.device, b, h, w, n)
         wt, bt = weight.detach().contiguous(), bias.detach().contiguous()
-        with torch.cuda.device(x4.device):
-            _lib.check(L.eamm_op_conv7_thin(x4.device.index, _ptr(x4), _ptr(wt), _ptr(bt), b, h, w, n, 0, _ptr(out), _ptr(work), nwork,
-                                            _stream(x4.device)), None)
+        _op.call("conv7_thin", x4.device, x4, wt, bt, b, h, w, n, 0, out, work=work)
         ctx.save_for_backward(x4, weight)
         return out
 
@@ -221,17 +197,13 @@ class _FirstConv7Function(torch.autograd.Function):
         n = weight.shape[0]
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:   # the source image rarely needs a gradient: the general kernels on the padded filter
-            wp = torch.nn.functional.pad(weight.detach(), (0, 0, 0, 0, 0, _CONV_BK - 3))              # [N,32,7,7]
+            wp = torch.nn.functional.pad(weight.detach(), (0, 0, 0, 0, 0, CHANNEL_GRANULE - 3))   # [N,32,7,7]
             gx = _Conv2dSameFunction._conv(grad_out, wp, None, transposed=True)[..., :4].contiguous()
             gx[..., 3] = 0
         if ctx.needs_input_grad[1]:
-            L = _lib.lib()
             gw = torch.empty_like(weight, memory_format=torch.contiguous_format)
-            nwork = L.eamm_op_conv7_thin_workspace_floats(b, h, w, n)
-            work = torch.empty(nwork, dtype=torch.float32, device=x4.device)
-            with torch.cuda.device(x4.device):
-                _lib.check(L.eamm_op_conv7_thin_wgrad(x4.device.index, _ptr(x4), _ptr(grad_out), b, h, w, n, 1, _ptr(gw), _ptr(work), nwork,
-                                                      _stream(x4.device)), None)
+            work = _op.workspace("conv7_thin", x4.device, b, h, w, n)
+            _op.call("conv7_thin_wgrad", x4.device, x4, grad_out, b, h, w, n, 1, gw, work=work)
         if ctx.needs_input_grad[2]:
             gb = torch.zeros_like(weight[:, 0, 0, 0]) if ctx.bias_grad_is_zero else grad_out.sum(dim=(0, 1, 2))
         return gx, gw, gb, None
@@ -245,14 +217,10 @@ class _FinalConvSigmoidFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias):
         b, h, w, n = x.shape
-        L = _lib.lib()
         y = torch.empty(b, 3, h, w, dtype=torch.float32, device=x.device)
-        nwork = 7 * n * 32
-        work = torch.empty(nwork, dtype=torch.float32, device=x.device)
+        work = torch.empty(7 * n * 32, dtype=torch.float32, device=x.device)
         wt, bt = weight.detach().contiguous(), bias.detach().contiguous()
-        with torch.cuda.device(x.device):
-            _lib.check(L.eamm_op_final_conv_sigmoid(x.device.index, _ptr(x), _ptr(wt), _ptr(bt), b, h, w, n, _ptr(y), _ptr(work), nwork,
-                                                    _stream(x.device)), None)
+        _op.call("final_conv_sigmoid", x.device, x, wt, bt, b, h, w, n, y, work=work)
         ctx.save_for_backward(x, weight, y)
         return y
 
@@ -262,21 +230,16 @@ class _FinalConvSigmoidFunction(torch.autograd.Function):
         b, h, w, n = x.shape
         g = grad_y * y * (1.0 - y)                                                          # through the sigmoid, NCHW [B,3,H,W]
         g4 = torch.nn.functional.pad(g.permute(0, 2, 3, 1), (0, 1)).contiguous()             # NHWC, four floats per pixel
-        L = _lib.lib()
-        nwork = L.eamm_op_conv7_thin_workspace_floats(b, h, w, n)
-        work = torch.empty(nwork, dtype=torch.float32, device=x.device)
+        work = _op.workspace("conv7_thin", x.device, b, h, w, n)
         gx = gw = gb = None
-        with torch.cuda.device(x.device):
-            if ctx.needs_input_grad[0]:
-                gx = torch.empty_like(x)
-                wt = weight.detach().contiguous()
-                _lib.check(L.eamm_op_conv7_thin(x.device.index, _ptr(g4), _ptr(wt), None, b, h, w, n, 1, _ptr(gx), _ptr(work), nwork,
-                                                _stream(x.device)), None)
-            if ctx.needs_input_grad[1]:
-                gw = torch.empty_like(weight, memory_format=torch.contiguous_format)
-                work2 = torch.empty(nwork, dtype=torch.float32, device=x.device)
-                _lib.check(L.eamm_op_conv7_thin_wgrad(x.device.index, _ptr(g4), _ptr(x), b, h, w, n, 0, _ptr(gw), _ptr(work2), nwork,
-                                                      _stream(x.device)), None)
+        if ctx.needs_input_grad[0]:
+            gx = torch.empty_like(x)
+            wt = weight.detach().contiguous()
+            _op.call("conv7_thin", x.device, g4, wt, None, b, h, w, n, 1, gx, work=work)
+        if ctx.needs_input_grad[1]:
+            gw = torch.empty_like(weight, memory_format=torch.contiguous_format)
+            work2 = torch.empty_like(work)
+            _op.call("conv7_thin_wgrad", x.device, g4, x, b, h, w, n, 0, gw, work=work2)
         if ctx.needs_input_grad[2]:
             gb = g.sum(dim=(0, 2, 3))
         return gx, gw, gb
@@ -284,7 +247,7 @@ class _FinalConvSigmoidFunction(torch.autograd.Function):
 
 def first_conv7(x4: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, bias_grad_is_zero: bool = False) -> torch.Tensor:
     """7x7 "same" convolution of a three-channel image (NHWC [B,H,W,4], fourth channel zero) to N = 32 | 64 channels."""
-    _need_gpu(x4, "first_conv7")
+    _op.need_gpu(x4, "autograd_ops", "first_conv7")
     if x4.shape[3] != 4 or tuple(weight.shape[1:]) != (3, 7, 7) or weight.shape[0] not in (32, 64) or bias is None:
         raise ValueError(f"first_conv7: input {tuple(x4.shape)} / weight {tuple(weight.shape)} unsupported")
     return _FirstConv7Function.apply(x4.contiguous(), weight, bias, bias_grad_is_zero)
@@ -292,7 +255,7 @@ def first_conv7(x4: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, bias
 
 def final_conv7_sigmoid(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
     """sigmoid(7x7 "same" convolution of NHWC [B,H,W,N], N = 32 | 64, to three channels + bias) -> NCHW [B,3,H,W]."""
-    _need_gpu(x, "final_conv7_sigmoid")
+    _op.need_gpu(x, "autograd_ops", "final_conv7_sigmoid")
     if tuple(weight.shape) != (3, x.shape[3], 7, 7) or x.shape[3] not in (32, 64) or bias is None:
         raise ValueError(f"final_conv7_sigmoid: input {tuple(x.shape)} / weight {tuple(weight.shape)} unsupported")
     return _FinalConvSigmoidFunction.apply(x.contiguous(), weight, bias)
@@ -303,11 +266,11 @@ def conv2d_same_nhwc(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch
     """``conv2d_same`` on the kernels' own layout: x NHWC [B,H,W,Cin] -> NHWC [B,H,W,Cout] (no layout copies).
     ``bias_grad_is_zero``: the output feeds a batch-statistics BatchNorm directly, so the bias gradient is exactly zero and is
     returned as zeros without being computed."""
-    _need_gpu(x, "conv2d_same_nhwc")
+    _op.need_gpu(x, "autograd_ops", "conv2d_same_nhwc")
     cout, cin, kh, kw = weight.shape
-    if (kh, kw) not in ((3, 3), (7, 7)) or x.shape[3] != cin or cin % _CONV_BK or cout % _CONV_BK:
+    if (kh, kw) not in ((3, 3), (7, 7)) or x.shape[3] != cin or cin % CHANNEL_GRANULE or cout % CHANNEL_GRANULE:
         raise ValueError(f"conv2d_same_nhwc: weight {tuple(weight.shape)} / input {tuple(x.shape)} unsupported "
-                         f"(3x3 or 7x7, channels multiples of {_CONV_BK})")
+                         f"(3x3 or 7x7, channels multiples of {CHANNEL_GRANULE})")
     if weight.device != x.device or (bias is not None and bias.device != x.device):
         raise RuntimeError("conv2d_same_nhwc: parameters and input are on different devices")
     return _Conv2dSameFunction.apply(x.contiguous(), weight, bias, bias_grad_is_zero)
@@ -315,7 +278,7 @@ def conv2d_same_nhwc(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch
 
 def warp_nhwc(features: torch.Tensor, deformation: torch.Tensor, occlusion: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``warp`` on NHWC features [n|1,h,w,C] (C a multiple of 8), flow [n,h,w,2], occlusion [n,h,w] or None -> NHWC [n,h,w,C]."""
-    _need_gpu(features, "warp_nhwc")
+    _op.need_gpu(features, "autograd_ops", "warp_nhwc")
     n, h, w, two = deformation.shape
     if two != 2 or features.shape[1:3] != (h, w) or features.shape[0] not in (1, n) or features.shape[3] % 8:
         raise ValueError(f"warp_nhwc: features {tuple(features.shape)} / deformation {tuple(deformation.shape)} mismatch")
@@ -328,11 +291,11 @@ def conv2d_same(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tens
     """``F.conv2d(x, weight, bias, padding=k // 2)`` for the path's square 3x3 / 7x7 filters (reference modules/util.py:858-938),
     differentiable in x, weight and bias.  x NCHW [B,Cin,H,W], weight [Cout,Cin,k,k] on the GPU; Cin and Cout multiples of 32
     (the granule of the forward kernels, which also compute the data gradient).  Returns NCHW."""
-    _need_gpu(x, "conv2d_same")
+    _op.need_gpu(x, "autograd_ops", "conv2d_same")
     cout, cin, kh, kw = weight.shape
-    if (kh, kw) not in ((3, 3), (7, 7)) or x.shape[1] != cin or cin % _CONV_BK or cout % _CONV_BK:
+    if (kh, kw) not in ((3, 3), (7, 7)) or x.shape[1] != cin or cin % CHANNEL_GRANULE or cout % CHANNEL_GRANULE:
         raise ValueError(f"conv2d_same: weight {tuple(weight.shape)} / input {tuple(x.shape)} unsupported "
-                         f"(3x3 or 7x7, channels multiples of {_CONV_BK})")
+                         f"(3x3 or 7x7, channels multiples of {CHANNEL_GRANULE})")
     if weight.device != x.device or (bias is not None and bias.device != x.device):
         raise RuntimeError("conv2d_same: parameters and input are on different devices")
     out = _Conv2dSameFunction.apply(x.permute(0, 2, 3, 1).contiguous(), weight, bias, False)

@@ -2,7 +2,7 @@
 // padding of odd widths, BatchNorm folding and weight repacking, the workspace, and the frame-invariant half of
 // OcclusionAwareGenerator.forward (reference modules/generator.py:59-97):
 //   eamm_encode_source  -- first 7x7 block, down blocks, anti-alias down-sampling (+ export / import of what it caches)
-// The per-frame half, eamm_forward_frames, and its launch plan are in eamm_forward.hip; the eamm_op_* entries in eamm_op_api.hip.
+// The per-frame half, eamm_forward_frames, and its launch plan are in eamm_forward.hip; the eamm_op_* entries in the four eamm_op_*.hip.
 #include "eamm_ctx.h"
 
 namespace {

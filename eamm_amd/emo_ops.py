@@ -19,25 +19,8 @@ from typing import Sequence, Tuple
 
 import torch
 
-from . import _lib
-from ._handle import ptr, stream_ptr
-
-_G = 32   # channel granule of the convolution kernels
-
-
-def _need_gpu(t: torch.Tensor, what: str):
-    if t.device.type != "cuda":
-        raise RuntimeError(f"eamm_amd.emo_ops.{what} runs only on a ROCm GPU (there is no CPU fallback)")
-    if t.dtype != torch.float32:
-        raise RuntimeError(f"{what}: float32 tensors only, got {t.dtype}")
-
-
-def _check(code):
-    _lib.check(code, None)
-
-
-def _work(n: int, dev) -> torch.Tensor:
-    return torch.empty(max(1, n), dtype=torch.float32, device=dev)
+from . import _lib, _op
+from ._op import CHANNEL_GRANULE
 
 
 class _ConvS2Function(torch.autograd.Function):
@@ -47,13 +30,11 @@ class _ConvS2Function(torch.autograd.Function):
     def forward(ctx, x, weight):
         b, h, w, cin = x.shape
         cout, _, k, _ = weight.shape
-        L = _lib.lib()
         dev = x.device
         out = torch.empty(b, h // 2, w // 2, cout, dtype=torch.float32, device=dev)
-        work = _work(L.eamm_op_conv_s2_workspace_floats(b, h, w, cin, cout, k), dev)
+        work = _op.workspace("conv_s2", dev, b, h, w, cin, cout, k)
         wt = weight.detach().contiguous()
-        with torch.cuda.device(dev):
-            _check(L.eamm_op_conv_s2(dev.index, ptr(x), b, h, w, cin, ptr(wt), cout, k, ptr(out), ptr(work), work.numel(), stream_ptr(dev)))
+        _op.call("conv_s2", dev, x, b, h, w, cin, wt, cout, k, out, work=work)
         ctx.save_for_backward(x, weight)
         return out
 
@@ -62,22 +43,18 @@ class _ConvS2Function(torch.autograd.Function):
         x, weight = ctx.saved_tensors
         b, h, w, cin = x.shape
         cout, _, k, _ = weight.shape
-        L = _lib.lib()
         dev = x.device
         grad_out = grad_out.contiguous()
         gx = gw = None
-        with torch.cuda.device(dev):
-            if ctx.needs_input_grad[0]:
-                gx = torch.empty_like(x)
-                work = _work(L.eamm_op_conv_s2_dgrad_workspace_floats(b, h, w, cin, cout, k), dev)
-                wt = weight.detach().contiguous()
-                _check(L.eamm_op_conv_s2_dgrad(dev.index, ptr(grad_out), b, h, w, cin, ptr(wt), cout, k, ptr(gx), ptr(work), work.numel(),
-                                               stream_ptr(dev)))
-            if ctx.needs_input_grad[1]:
-                gw = torch.empty_like(weight, memory_format=torch.contiguous_format)
-                work = _work(L.eamm_op_conv_s2_wgrad_workspace_floats(b, h, w, cin, cout, k), dev)
-                _check(L.eamm_op_conv_s2_wgrad(dev.index, ptr(x), ptr(grad_out), b, h, w, cin, cout, k, ptr(gw), ptr(work), work.numel(),
-                                               stream_ptr(dev)))
+        if ctx.needs_input_grad[0]:
+            gx = torch.empty_like(x)
+            work = _op.workspace("conv_s2_dgrad", dev, b, h, w, cin, cout, k)
+            wt = weight.detach().contiguous()
+            _op.call("conv_s2_dgrad", dev, grad_out, b, h, w, cin, wt, cout, k, gx, work=work)
+        if ctx.needs_input_grad[1]:
+            gw = torch.empty_like(weight, memory_format=torch.contiguous_format)
+            work = _op.workspace("conv_s2_wgrad", dev, b, h, w, cin, cout, k)
+            _op.call("conv_s2_wgrad", dev, x, grad_out, b, h, w, cin, cout, k, gw, work=work)
         return gx, gw
 
 
@@ -88,8 +65,7 @@ class _MaxPoolFunction(torch.autograd.Function):
     def forward(ctx, x):
         b, h, w, c = x.shape
         out = torch.empty(b, h // 2, w // 2, c, dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            _check(_lib.lib().eamm_op_emo_maxpool(x.device.index, ptr(x), b, h, w, c, ptr(out), stream_ptr(x.device)))
+        _op.call("emo_maxpool", x.device, x, b, h, w, c, out)
         ctx.save_for_backward(x)
         return out
 
@@ -99,8 +75,7 @@ class _MaxPoolFunction(torch.autograd.Function):
         b, h, w, c = x.shape
         grad_out = grad_out.contiguous()
         gx = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            _check(_lib.lib().eamm_op_emo_maxpool_backward(x.device.index, ptr(x), ptr(grad_out), b, h, w, c, ptr(gx), stream_ptr(x.device)))
+        _op.call("emo_maxpool_backward", x.device, x, grad_out, b, h, w, c, gx)
         return gx
 
 
@@ -113,8 +88,7 @@ class _EmoFinalFunction(torch.autograd.Function):
         dev = a.device
         value = torch.empty(b, 4, 2, dtype=torch.float32, device=dev)
         jac = torch.empty(b, 4, 2, 2, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _check(_lib.lib().eamm_op_emo_final(dev.index, ptr(a), ptr(w98), b, ptr(value), ptr(jac), stream_ptr(dev)))
+        _op.call("emo_final", dev, a, w98, b, value, jac)
         ctx.save_for_backward(a, w98)
         ctx.set_materialize_grads(False)      # an output the loss never reads has no gradient: its term is skipped
         return value, jac
@@ -126,14 +100,11 @@ class _EmoFinalFunction(torch.autograd.Function):
             return None, None
         b = a.shape[0]
         dev = a.device
-        L = _lib.lib()
         g_value = None if g_value is None else g_value.contiguous()
         g_jac = None if g_jac is None else g_jac.contiguous()
         ga, gw = torch.empty_like(a), torch.empty_like(w98)
-        work = _work(L.eamm_op_emo_final_workspace_floats(b), dev)
-        with torch.cuda.device(dev):
-            _check(L.eamm_op_emo_final_backward(dev.index, ptr(a), ptr(w98), ptr(g_value), ptr(g_jac), b, ptr(ga), ptr(gw), ptr(work),
-                                                work.numel(), stream_ptr(dev)))
+        work = _op.workspace("emo_final", dev, b)
+        _op.call("emo_final_backward", dev, a, w98, g_value, g_jac, b, ga, gw, work=work)
         return (ga if ctx.needs_input_grad[0] else None), (gw if ctx.needs_input_grad[1] else None)
 
 
@@ -149,9 +120,9 @@ def conv2d_s2_nhwc(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
         raise ValueError(f"conv2d_s2_nhwc: 1x1 or 3x3 filters only, got {kh}x{kw}")
     if b < 1 or h < 2 or w < 2 or h % 2 or w % 2:
         raise ValueError(f"conv2d_s2_nhwc: even map sides only (odd sizes are out of scope), got {h} x {w}")
-    if c != cin or cin % _G or cout % _G:
-        raise ValueError(f"conv2d_s2_nhwc: weight {tuple(weight.shape)} / input {tuple(x.shape)} unsupported (channels multiples of {_G})")
-    _need_gpu(x, "conv2d_s2_nhwc")
+    if c != cin or cin % CHANNEL_GRANULE or cout % CHANNEL_GRANULE:
+        raise ValueError(f"conv2d_s2_nhwc: weight {tuple(weight.shape)} / input {tuple(x.shape)} unsupported (channels multiples of {CHANNEL_GRANULE})")
+    _op.need_gpu(x, "emo_ops", "conv2d_s2_nhwc")
     if weight.device != x.device:
         raise RuntimeError("conv2d_s2_nhwc: weight and input are on different devices")
     if _lib.lib().eamm_op_conv_s2_workspace_floats(b, h, w, cin, cout, kh) == 0:
@@ -168,7 +139,7 @@ def maxpool3s2_nhwc(x: torch.Tensor) -> torch.Tensor:
         raise ValueError(f"maxpool3s2_nhwc: even map sides only, got {h} x {w}")
     if x.numel() >= 2 ** 31:
         raise ValueError("maxpool3s2_nhwc: fewer than 2^31 elements")
-    _need_gpu(x, "maxpool3s2_nhwc")
+    _op.need_gpu(x, "emo_ops", "maxpool3s2_nhwc")
     return _MaxPoolFunction.apply(x.contiguous())
 
 
@@ -185,7 +156,7 @@ def emo_final(a: torch.Tensor, w98: torch.Tensor) -> Tuple[torch.Tensor, torch.T
         raise ValueError(f"emo_final: input [B,64], got {tuple(a.shape)}")
     if w98.dim() != 1 or w98.numel() != 98:
         raise ValueError(f"emo_final: 98 weights (final_weights), got {tuple(w98.shape)}")
-    _need_gpu(a, "emo_final")
+    _op.need_gpu(a, "emo_ops", "emo_final")
     if w98.device != a.device or w98.dtype != torch.float32:
         raise RuntimeError("emo_final: weights must be float32 on the input's device")
     return _EmoFinalFunction.apply(a.contiguous(), w98.contiguous())

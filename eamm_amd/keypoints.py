@@ -105,8 +105,7 @@ def one_euro_smooth(seq: torch.Tensor, mincutoff: float = 1.0, beta: float = 0.0
     frames; a 2048-frame clip takes ~0.15 ms, no host round trip) -- the clip pipeline's path.  A CPU tensor is filtered on
     the host in float32 in the reference's operation order (numpy; the reference itself filters on the host)."""
     if seq.is_cuda:
-        from . import _lib
-        from ._handle import ptr, stream_ptr
+        from . import _op
         x = seq.detach().to(torch.float32).contiguous()
         T = x.shape[0]
         out = torch.empty_like(x)
@@ -115,10 +114,8 @@ def one_euro_smooth(seq: torch.Tensor, mincutoff: float = 1.0, beta: float = 0.0
             if state is not None and (state.device != x.device or state.dtype != torch.float32 or state.numel() != 3 * E
                                       or not state.is_contiguous()):
                 raise RuntimeError(f"one_euro_smooth: state must be a contiguous float32 [3,{E}] tensor on {x.device}")
-            with torch.cuda.device(x.device):
-                _lib.check(_lib.lib().eamm_op_one_euro(x.device.index, ptr(x), T, E, float(mincutoff), float(beta), float(dcutoff),
-                                                       float(freq), float(scale), ptr(out), ptr(state), int(bool(resume)),
-                                                       stream_ptr(x.device)), None)
+            _op.call("one_euro", x.device, x, T, E, float(mincutoff), float(beta), float(dcutoff), float(freq), float(scale), out, state,
+                     int(bool(resume)))
         return out
     if state is not None or resume:
         raise RuntimeError("one_euro_smooth: the resumable form is the device path's (a CPU tensor is filtered whole)")

@@ -13,17 +13,7 @@ from typing import Dict
 
 import torch
 
-from . import _lib
-from ._handle import ptr, stream_ptr
-from .autograd_ops import _need_gpu
-
-
-def _check(code):
-    _lib.check(code, None)
-
-
-def _workspace(b, k, dev):
-    return torch.empty(max(1, _lib.lib().eamm_op_kp_head_workspace_floats(b, k)), dtype=torch.float32, device=dev)
+from . import _op
 
 
 class _KpHeadFunction(torch.autograd.Function):
@@ -38,10 +28,8 @@ class _KpHeadFunction(torch.autograd.Function):
         jac = new(b, k, 2, 2) if njm > 0 else None
         heat = new(b, k, h - 6 + 2 * pad, w - 6 + 2 * pad) if want_heatmap else None
         stats = new(b, k, 2)
-        ws = _workspace(b, k, dev)
-        with torch.cuda.device(dev):
-            _check(_lib.lib().eamm_op_kp_head(dev.index, ptr(logits), b, k, njm, h, w, cs, pad, float(temperature), ptr(value), ptr(jac),
-                                              ptr(heat), ptr(stats), ptr(ws), ws.numel(), stream_ptr(dev)))
+        ws = _op.workspace("kp_head", dev, b, k)
+        _op.call("kp_head", dev, logits, b, k, njm, h, w, cs, pad, float(temperature), value, jac, heat, stats, work=ws)
         ctx.save_for_backward(logits, stats, value, jac)
         ctx.cfg = (k, njm, pad, float(temperature))
         ctx.set_materialize_grads(False)      # an output the loss never reads has no gradient: its term is skipped, not a zero tensor
@@ -58,11 +46,9 @@ class _KpHeadFunction(torch.autograd.Function):
         cont = lambda t: None if t is None else t.contiguous()
         g_value, g_jac, g_heat = cont(g_value), cont(g_jac), cont(g_heat)
         grad = torch.empty_like(logits)
-        ws = _workspace(b, k, dev)
-        with torch.cuda.device(dev):
-            _check(_lib.lib().eamm_op_kp_head_backward(dev.index, ptr(logits), ptr(stats), ptr(value), ptr(jac), ptr(g_value), ptr(g_jac),
-                                                       ptr(g_heat), b, k, njm, h, w, cs, pad, temperature, ptr(grad), ptr(ws), ws.numel(),
-                                                       stream_ptr(dev)))
+        ws = _op.workspace("kp_head", dev, b, k)
+        _op.call("kp_head_backward", dev, logits, stats, value, jac, g_value, g_jac, g_heat, b, k, njm, h, w, cs, pad, temperature, grad,
+                 work=ws)
         return grad, None, None, None, None, None
 
 
@@ -83,7 +69,7 @@ def kp_head(logits_nhwc: torch.Tensor, K: int, njm: int, pad: int, temperature: 
         raise ValueError(f"kp_head: a {h} x {w} map with padding {pad} (0..3) leaves no window of at least 1 x 1")
     if not temperature > 0:
         raise ValueError(f"kp_head: temperature must be positive, got {temperature}")
-    _need_gpu(logits_nhwc, "kp_head")
+    _op.need_gpu(logits_nhwc, "autograd_ops", "kp_head")   # (the module name this message has always carried)
     value, jac, heat = _KpHeadFunction.apply(logits_nhwc.contiguous(), K, njm, pad, float(temperature), bool(want_heatmap))
     out = {"value": value}
     if heat is not None:

@@ -14,13 +14,9 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import _lib
-from ._handle import ptr, stream_ptr
-from .autograd_ops import _need_gpu
+from . import _op
 
-
-def _check(code):
-    _lib.check(code, None)
+_MODULE = "autograd_ops"   # (the module name these operators' "runs only on a ROCm GPU" message has always carried)
 
 
 class _AntiAliasDownFunction(torch.autograd.Function):
@@ -30,9 +26,7 @@ class _AntiAliasDownFunction(torch.autograd.Function):
     def forward(ctx, source, weight, inv_scale):
         b, _, hh, ww = source.shape
         small = torch.empty(b, hh // inv_scale, ww // inv_scale, 4, dtype=torch.float32, device=source.device)
-        with torch.cuda.device(source.device):
-            _check(_lib.lib().eamm_op_antialias_down(source.device.index, ptr(source), ptr(weight), b, hh, ww, inv_scale, ptr(small),
-                                                     stream_ptr(source.device)))
+        _op.call("antialias_down", source.device, source, weight, b, hh, ww, inv_scale, small)
         ctx.save_for_backward(weight)
         ctx.shape, ctx.inv_scale = (b, hh, ww), inv_scale
         return small
@@ -45,16 +39,14 @@ class _AntiAliasDownFunction(torch.autograd.Function):
         b, hh, ww = ctx.shape
         grad_small = grad_small.contiguous()
         grad = torch.empty(b, 3, hh, ww, dtype=torch.float32, device=grad_small.device)
-        with torch.cuda.device(grad.device):
-            _check(_lib.lib().eamm_op_antialias_down_backward(grad.device.index, ptr(grad_small), ptr(weight), b, hh, ww, ctx.inv_scale,
-                                                              ptr(grad), stream_ptr(grad.device)))
+        _op.call("antialias_down_backward", grad.device, grad_small, weight, b, hh, ww, ctx.inv_scale, grad)
         return grad, None, None
 
 
 def antialias_down(source: torch.Tensor, weight: Optional[torch.Tensor], scale_factor: float) -> torch.Tensor:
     """AntiAliasInterpolation2d (reference modules/util.py:1005-1052) on an RGB batch -> NHWC [B,h,w,4]; ``scale_factor`` 0.25 (the
     13x13 Gaussian of every shipped configuration) or 1 (util.py:1047-1048 returns the input)."""
-    _need_gpu(source, "antialias_down")
+    _op.need_gpu(source, _MODULE, "antialias_down")
     inv = int(round(1.0 / scale_factor))
     if source.dim() != 4 or source.shape[1] != 3 or inv not in (1, 4) or source.shape[2] % inv or source.shape[3] % inv:
         raise ValueError(f"antialias_down: RGB NCHW input with sides multiples of 1/scale_factor, scale_factor 0.25 or 1; got "
@@ -75,9 +67,7 @@ class _KpRecordsFunction(torch.autograd.Function):
         n, k = kd_val.shape[:2]
         rec = torch.empty(n, k, 8, dtype=torch.float32, device=kd_val.device)
         flag = torch.zeros(1, dtype=torch.int32, device=kd_val.device)
-        with torch.cuda.device(kd_val.device):
-            _check(_lib.lib().eamm_op_kp_records(kd_val.device.index, ptr(kd_val), ptr(kd_jac), ptr(ks_val), ptr(ks_jac), n, k,
-                                                 ptr(rec), ptr(flag), stream_ptr(kd_val.device)))
+        _op.call("kp_records", kd_val.device, kd_val, kd_jac, ks_val, ks_jac, n, k, rec, flag)
         # torch.inverse raises (and synchronises) on a singular matrix too -- but a host read is illegal while the stream is being
         # captured into a graph: there the flag stays on the device and backward() (or the replay's caller) reads it
         ctx.flag = None
@@ -105,26 +95,20 @@ class _KpRecordsFunction(torch.autograd.Function):
         g_ksj = new(n, k, 2, 2) if (need[3] and ks_jac is not None) else None
         if g_kdv is None and g_kdj is None and g_ksv is None and g_ksj is None:
             return None, None, None, None
-        with torch.cuda.device(dev):
-            _check(_lib.lib().eamm_op_kp_records_backward(dev.index, ptr(kd_jac), ptr(ks_jac), ptr(grad_rec), n, k, ptr(g_kdv),
-                                                          ptr(g_ksv), ptr(g_kdj), ptr(g_ksj), stream_ptr(dev)))
+        _op.call("kp_records_backward", dev, kd_jac, ks_jac, grad_rec, n, k, g_kdv, g_ksv, g_kdj, g_ksj)
         return g_kdv, g_kdj, g_ksv, g_ksj
 
 
 def kp_records(kp_driving: dict, kp_source: dict) -> torch.Tensor:
     """dense_motion.py:47-67: the per key point affine map T_k(z) = J_k (z - kp_driving_k) + kp_source_k as records [n,K,8]."""
     kd_val, ks_val = kp_driving["value"], kp_source["value"]
-    _need_gpu(kd_val, "kp_records")
+    _op.need_gpu(kd_val, _MODULE, "kp_records")
     kd_jac = kp_driving.get("jacobian") if "jacobian" in kp_driving else None
     ks_jac = kp_source.get("jacobian") if kd_jac is not None else None
     if kd_val.shape != ks_val.shape or kd_val.dim() != 3 or kd_val.shape[2] != 2:
         raise ValueError(f"kp_records: key-point values must both be [n,K,2], got {tuple(kd_val.shape)} / {tuple(ks_val.shape)}")
     cont = lambda t: None if t is None else t.contiguous()
     return _KpRecordsFunction.apply(cont(kd_val), cont(kd_jac), cont(ks_val), cont(ks_jac))
-
-
-def _workspace(n, k, h, w, dev):
-    return torch.empty(max(1, _lib.lib().eamm_op_motion_workspace_floats(n, k, h, w)), dtype=torch.float32, device=dev)
 
 
 class _MotionFrontFunction(torch.autograd.Function):
@@ -137,9 +121,7 @@ class _MotionFrontFunction(torch.autograd.Function):
         dev = rec.device
         hg = torch.empty(n, h, w, cpad, dtype=torch.float32, device=dev)
         sd = torch.empty(n, k + 1, 3, h, w, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _check(_lib.lib().eamm_op_motion_front(dev.index, ptr(rec), ptr(small), n, k, h, w, float(variance), cpad, ptr(hg), ptr(sd),
-                                                   stream_ptr(dev)))
+        _op.call("motion_front", dev, rec, small, n, k, h, w, float(variance), cpad, hg, sd)
         ctx.save_for_backward(rec, small)
         ctx.variance, ctx.cpad = float(variance), cpad
         return hg, sd
@@ -156,18 +138,15 @@ class _MotionFrontFunction(torch.autograd.Function):
         grad_sd = None if grad_sd is None else grad_sd.contiguous()
         g_rec = torch.empty_like(rec)
         g_small = torch.empty_like(small) if ctx.needs_input_grad[1] else None
-        ws = _workspace(n, k, h, w, dev)
-        with torch.cuda.device(dev):
-            _check(_lib.lib().eamm_op_motion_front_backward(dev.index, ptr(rec), ptr(small), n, k, h, w, ctx.variance, ctx.cpad,
-                                                            ptr(grad_hg), ptr(grad_sd), ptr(g_small), ptr(g_rec), ptr(ws), ws.numel(),
-                                                            stream_ptr(dev)))
+        ws = _op.workspace("motion", dev, n, k, h, w)
+        _op.call("motion_front_backward", dev, rec, small, n, k, h, w, ctx.variance, ctx.cpad, grad_hg, grad_sd, g_small, g_rec, work=ws)
         return (g_rec if ctx.needs_input_grad[0] else None), g_small, None, None
 
 
 def motion_front(records: torch.Tensor, small: torch.Tensor, kp_variance: float, cpad: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """dense_motion.py:32-45, 47-79, 93-94: heat-maps, sparse motions and the K+1 warps of the down-sampled source, laid out as the
     hourglass input (channel 4k = heat-map k, 4k+1..3 = RGB warped by motion k; zero padded to ``cpad``) + ``sparse_deformed``."""
-    _need_gpu(records, "motion_front")
+    _op.need_gpu(records, _MODULE, "motion_front")
     n, k = records.shape[:2]
     if tuple(small.shape[:1]) != (n,) or small.dim() != 4 or small.shape[3] != 4 or cpad < 4 * (k + 1) or cpad % 4:
         raise ValueError(f"motion_front: records {tuple(records.shape)} / small {tuple(small.shape)} / cpad {cpad} mismatch")
@@ -187,11 +166,9 @@ class _MotionHeadFunction(torch.autograd.Function):
         mask = torch.empty(n, k + 1, h, w, dtype=torch.float32, device=dev)
         defo = torch.empty(n, h, w, 2, dtype=torch.float32, device=dev)
         occ = torch.empty(n, h, w, dtype=torch.float32, device=dev) if (lo is not None or stacked) else None
-        lo_ptr = C.c_void_p(lm.data_ptr() + 4 * (k + 1)) if stacked else ptr(lo)
+        lo_ptr = C.c_void_p(lm.data_ptr() + 4 * (k + 1)) if stacked else lo
         ldo = ld if stacked else (0 if lo is None else lo.shape[3])
-        with torch.cuda.device(dev):
-            _check(_lib.lib().eamm_op_motion_head(dev.index, ptr(lm), ld, lo_ptr, ldo, ptr(rec), n, k, h, w,
-                                                  ptr(mask), ptr(defo), ptr(occ), stream_ptr(dev)))
+        _op.call("motion_head", dev, lm, ld, lo_ptr, ldo, rec, n, k, h, w, mask, defo, occ)
         ctx.save_for_backward(mask, occ, rec)
         ctx.ld, ctx.ldo, ctx.stacked = ld, ldo, bool(stacked)
         return mask, defo, occ
@@ -206,13 +183,11 @@ class _MotionHeadFunction(torch.autograd.Function):
         g_mask, g_defo, g_occ = cont(g_mask), cont(g_defo), cont(g_occ)
         g_lm = torch.empty(n, h, w, ctx.ld, dtype=torch.float32, device=dev)
         g_lo = torch.empty(n, h, w, ctx.ldo, dtype=torch.float32, device=dev) if (occ is not None and not ctx.stacked) else None
-        g_lo_ptr = C.c_void_p(g_lm.data_ptr() + 4 * (k + 1)) if ctx.stacked else ptr(g_lo)
+        g_lo_ptr = C.c_void_p(g_lm.data_ptr() + 4 * (k + 1)) if ctx.stacked else g_lo
         g_rec = torch.empty_like(rec)
-        ws = _workspace(n, k, h, w, dev)
-        with torch.cuda.device(dev):
-            _check(_lib.lib().eamm_op_motion_head_backward(dev.index, ptr(mask), ptr(occ), ptr(rec), n, k, h, w, ptr(g_mask), ptr(g_defo),
-                                                           ptr(g_occ), ptr(g_lm), ctx.ld, g_lo_ptr, ctx.ldo, ptr(g_rec), ptr(ws),
-                                                           ws.numel(), stream_ptr(dev)))
+        ws = _op.workspace("motion", dev, n, k, h, w)
+        _op.call("motion_head_backward", dev, mask, occ, rec, n, k, h, w, g_mask, g_defo, g_occ, g_lm, ctx.ld, g_lo_ptr, ctx.ldo, g_rec,
+                 work=ws)
         return g_lm, g_lo, (g_rec if ctx.needs_input_grad[2] else None), None
 
 
@@ -220,7 +195,7 @@ def motion_head(mask_logits: torch.Tensor, occlusion_logits: Optional[torch.Tens
     """dense_motion.py:98-111 on the two 7x7 convolutions' NHWC outputs (channels 0..K of ``mask_logits``, channel 0 of
     ``occlusion_logits``): mask [n,K+1,h,w], deformation [n,h,w,2], occlusion [n,h,w] or None.  ``stacked``: ONE convolution with
     the two filters stacked produced both -- the occlusion logit is channel K + 1 of ``mask_logits``, ``occlusion_logits`` is None."""
-    _need_gpu(mask_logits, "motion_head")
+    _op.need_gpu(mask_logits, _MODULE, "motion_head")
     n, k = records.shape[:2]
     if mask_logits.dim() != 4 or mask_logits.shape[0] != n or mask_logits.shape[3] < k + 1 + int(stacked):
         raise ValueError(f"motion_head: mask logits {tuple(mask_logits.shape)} do not hold {k + 1} motions of {n} frames")

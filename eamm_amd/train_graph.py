@@ -33,18 +33,12 @@ import torch
 import torch.nn.functional as F
 
 from . import autograd_ops
+from ._op import CHANNEL_GRANULE, round_up
 from .sync_batchnorm import SynchronizedBatchNorm2d, _BatchNormNHWCFunction
-
-_G = 32   # channel granule of the convolution kernels
-
-
-def _round_up(n: int, m: int) -> int:
-    return (n + m - 1) // m * m
-
 
 def _pad_last(x: torch.Tensor, mult: int) -> torch.Tensor:
     c = x.shape[-1]
-    return x if c % mult == 0 else F.pad(x, (0, _round_up(c, mult) - c))
+    return x if c % mult == 0 else F.pad(x, (0, round_up(c, mult) - c))
 
 
 def conv(x: torch.Tensor, mod: torch.nn.Conv2d, feeds_norm: bool = False, keep_padded: bool = False) -> torch.Tensor:
@@ -58,9 +52,9 @@ def conv(x: torch.Tensor, mod: torch.nn.Conv2d, feeds_norm: bool = False, keep_p
 def conv_wb(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], feeds_norm: bool = False, keep_padded: bool = False) -> torch.Tensor:
     """``conv`` on a filter / bias pair that is not a module's (the flow head's two stacked convolutions)."""
     cout, cin = w.shape[:2]
-    cin_p, cout_p = _round_up(cin, _G), _round_up(cout, _G)
+    cin_p, cout_p = round_up(cin, CHANNEL_GRANULE), round_up(cout, CHANNEL_GRANULE)
     if cin_p != cin:
-        x = _pad_last(x, _G)
+        x = _pad_last(x, CHANNEL_GRANULE)
         w = F.pad(w, (0, 0, 0, 0, 0, cin_p - cin))
     if cout_p != cout:
         w = F.pad(w, (0, 0, 0, 0, 0, 0, 0, cout_p - cout))
@@ -239,8 +233,8 @@ def _dense_motion(g: _Graph, source_image, kp_driving, kp_source):
         small = motion_ops.antialias_down(source_image, dm.down.weight if dm.scale_factor != 1 else None, dm.scale_factor)
         rec = motion_ops.kp_records(kp_driving, kp_source)
         # hourglass input [B,h,w,64]: 4 (K+1) real channels + zeros up to the kernels' granule -- the convolutions take it as it is
-        hg_in, sparse = motion_ops.motion_front(rec, small, dm.kp_variance, _round_up(4 * (dm.num_kp + 1), _G))
-        if dm.hourglass.decoder.up_blocks[-1].conv.weight.shape[0] % _G:   # the last concatenation would not end on the granule
+        hg_in, sparse = motion_ops.motion_front(rec, small, dm.kp_variance, round_up(4 * (dm.num_kp + 1), CHANNEL_GRANULE))
+        if dm.hourglass.decoder.up_blocks[-1].conv.weight.shape[0] % CHANNEL_GRANULE:   # the last concatenation would not end on the granule
             hg_in = hg_in[..., :4 * (dm.num_kp + 1)]
         feat = g.hourglass(hg_in, dm.hourglass)
         if dm.occlusion is not None and dm.mask.bias is not None and dm.occlusion.bias is not None:

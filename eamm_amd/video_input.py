@@ -46,7 +46,6 @@ from typing import Optional
 import numpy as np
 import torch
 
-from ._handle import ptr, stream_ptr
 from .config import emotion_augmentation_config
 
 OUT = 256
@@ -475,34 +474,28 @@ def _upload_u8(frames, dev) -> torch.Tensor:
 
 
 def _resize_device(x: torch.Tensor) -> torch.Tensor:
-    from . import _lib
+    from . import _op
     n, H, W, Ch = (int(s) for s in x.shape)
     if (H, W) == (OUT, OUT):
         return x[..., :3].contiguous()
     wy, wx = gaussian_taps(H), gaussian_taps(W)
     ty, tx = (C.c_double * len(wy))(*wy), (C.c_double * len(wx))(*wx)
     out = torch.empty((n, OUT, OUT, 3), dtype=torch.uint8, device=x.device)
-    L = _lib.lib()
-    with torch.cuda.device(x.device):
-        for a in range(0, n, MAX_LAUNCH):
-            b = min(n, a + MAX_LAUNCH)
-            _lib.check(L.eamm_op_resize_aa(x.device.index, ptr(x[a:b]), b - a, H, W, Ch, ty, len(wy) // 2, tx, len(wx) // 2,
-                                           ptr(out[a:b]), stream_ptr(x.device)), None)
+    for a in range(0, n, MAX_LAUNCH):
+        b = min(n, a + MAX_LAUNCH)
+        _op.call("resize_aa", x.device, x[a:b], b - a, H, W, Ch, ty, len(wy) // 2, tx, len(wx) // 2, out[a:b])
     return out
 
 
 def _warp_device(x: torch.Tensor, maps: np.ndarray, mode: int) -> torch.Tensor:
-    from . import _lib
+    from . import _op
     n, H, W, Ch = (int(s) for s in x.shape)
     m = torch.from_numpy(np.ascontiguousarray(maps.reshape(n, 6), dtype=np.float64)).to(x.device)
     shape = (n, OUT, OUT, 3) if mode == 0 else (n, 3, OUT, OUT)
     out = torch.empty(shape, dtype=torch.float32, device=x.device)
-    L = _lib.lib()
-    with torch.cuda.device(x.device):
-        for a in range(0, n, MAX_LAUNCH):
-            b = min(n, a + MAX_LAUNCH)
-            _lib.check(L.eamm_op_similarity_warp(x.device.index, ptr(x[a:b]), b - a, H, W, Ch, ptr(m[a:b]), mode, ptr(out[a:b]),
-                                                 stream_ptr(x.device)), None)
+    for a in range(0, n, MAX_LAUNCH):
+        b = min(n, a + MAX_LAUNCH)
+        _op.call("similarity_warp", x.device, x[a:b], b - a, H, W, Ch, m[a:b], mode, out[a:b])
     return out
 
 
@@ -614,7 +607,7 @@ class EmotionVideo:
     def _frames(self, t0: int, t1: int) -> torch.Tensor:
         if self.device.type != "cuda":
             return torch.from_numpy(augment_reference(self.aligned.numpy(), self.draw, self._raw_params, t0, t1))
-        from . import _lib
+        from . import _op
         dev = self.device
         out = torch.empty((t1 - t0, 3, OUT, OUT), dtype=torch.float32, device=dev)
         if t1 == t0:
@@ -625,11 +618,8 @@ class EmotionVideo:
             if t is not None:
                 t.record_stream(stream)
         x0, y0, w, h = self.params["mouth"]
-        L = _lib.lib()
-        with torch.cuda.device(dev):
-            for a in range(t0, t1, MAX_LAUNCH):
-                b = min(t1, a + MAX_LAUNCH)
-                _lib.check(L.eamm_op_emotion_augment(dev.index, ptr(self.aligned), self.n_frames, a, b - a, int(self.draw["flip"]),
-                                                     self._rot, ptr(self._hinv), ptr(self._noise), self.draw.get("noise_seed", 0),
-                                                     x0, y0, w, h, ptr(out[a - t0:b - t0]), stream_ptr(stream=stream)), None)
+        for a in range(t0, t1, MAX_LAUNCH):
+            b = min(t1, a + MAX_LAUNCH)
+            _op.call("emotion_augment", dev, self.aligned, self.n_frames, a, b - a, int(self.draw["flip"]), self._rot, self._hinv,
+                     self._noise, self.draw.get("noise_seed", 0), x0, y0, w, h, out[a - t0:b - t0], stream=stream)
         return out

@@ -10,7 +10,6 @@ lie beyond the bar, none beyond 20 bars.  A tensor whose reference gradient is b
 bias in front of batch statistics) is scaled by that largest one.  The reference's own fp32 run differs from its float64 run by at
 most 5.3e-5 relative on any gradient tensor, a hundredth of FP32_MIN_REL.
 """
-import ctypes as C
 import functools
 import json
 import os
@@ -21,7 +20,8 @@ import torch
 import torch.nn.functional as F
 
 from conftest import GOLDEN
-from eamm_amd import EmotionDetector, KPDetector_a, _lib, emo_ops, tiny_kp_config
+from eamm_amd import EmotionDetector, KPDetector_a, _lib, _op, emo_ops, tiny_kp_config
+from eamm_amd._handle import ptr as p, stream_ptr as stream   # (for the calls below that read an entry's return code themselves)
 from eamm_amd.weights import (emotion_state_dict_spec, kp_state_dict_spec, synthetic_keypoints, synthetic_source,
                               synthetic_state_dict)
 
@@ -29,14 +29,6 @@ DEV = "cuda:0"
 FP32_MIN_REL = 5e-3       # tests/test_train_backward.py
 TIGHT_MIN_REL = 2e-5
 UNUSED = ("fc.", "fc_n.", "final_4.", "final_10.")
-
-
-def p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def close(got, want, want32, what, floor=TIGHT_MIN_REL):
@@ -113,8 +105,8 @@ def test_conv_s2_gradients_write_everything_and_repeat_bit_for_bit(k, shape):
     for _ in range(3):
         dx, dw = torch.full_like(xd, float("nan")), torch.full_like(wd, float("nan"))
         wsd, wsw = torch.full((nd,), float("nan"), device=DEV), torch.full((nw,), float("nan"), device=DEV)
-        _lib.check(L.eamm_op_conv_s2_dgrad(0, p(gd), b, h, w, cin, p(wd), cout, k, p(dx), p(wsd), nd, stream()))
-        _lib.check(L.eamm_op_conv_s2_wgrad(0, p(xd), p(gd), b, h, w, cin, cout, k, p(dw), p(wsw), nw, stream()))
+        _op.call("conv_s2_dgrad", gd.device, gd, b, h, w, cin, wd, cout, k, dx, work=wsd)
+        _op.call("conv_s2_wgrad", gd.device, xd, gd, b, h, w, cin, cout, k, dw, work=wsw)
         runs.append((dx.cpu(), dw.cpu()))
     dx, dw = runs[0]
     assert bool(torch.isfinite(dx).all()) and bool(torch.isfinite(dw).all())
@@ -160,10 +152,9 @@ def test_maxpool_backward_takes_atens_first_maximum(shape, plateau):
     assert bool(((got != 0) == (want != 0)).all()), "gradient positions differ from ATen's"
     close(got, want, nhwc(ref[torch.float32][1]), f"maxpool {shape} plateau={plateau}")
     # the C entry on a poisoned buffer: every element written
-    L = _lib.lib()
     b, h, w, c = shape
     dx = torch.full_like(xg, float("nan")).detach()
-    _lib.check(L.eamm_op_emo_maxpool_backward(0, p(xg.detach()), p(nhwc(gy).to(DEV)), b, h, w, c, p(dx), stream()))
+    _op.call("emo_maxpool_backward", dx.device, xg.detach(), nhwc(gy).to(DEV), b, h, w, c, dx)
     assert torch.equal(dx.cpu(), got)
 
 

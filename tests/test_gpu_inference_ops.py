@@ -9,17 +9,13 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from eamm_amd import _lib
+from eamm_amd import _op
 from eamm_amd.weights import antialias_kernel, synthetic_keypoints
 from test_gpu_motion_ops import _close, _reference_front
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 NAN = float("nan")
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def _nan(*shape):
@@ -29,8 +25,7 @@ def _nan(*shape):
 def _run(name, *args):
     """One entry on device 0 and the current stream, then a wait.  Tensors are passed as such (never as a bare data_ptr() of a
     temporary): they stay referenced until the launch has finished."""
-    raw = [a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args]
-    _lib.check(getattr(_lib.lib(), name)(0, *raw, _stream()), None)
+    _op.call(name[len("eamm_op_"):], torch.device(DEV), *args)
     torch.cuda.synchronize()
 
 

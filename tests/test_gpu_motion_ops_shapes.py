@@ -314,7 +314,7 @@ def _nan(*shape):
 def _front_backward_raw(rec, small, cpad, g_hg, g_sd, want_small, short=0):
     """eamm_op_motion_front_backward as motion_ops calls it, on NaN-filled outputs and workspace -> (code, d records, d small)."""
     from eamm_amd import _lib
-    from eamm_amd.autograd_ops import _ptr, _stream
+    from eamm_amd._handle import ptr as _ptr, stream_ptr as _stream
     n, k = rec.shape[:2]
     h, w = small.shape[1:3]
     dev = rec.device
@@ -330,7 +330,7 @@ def _front_backward_raw(rec, small, cpad, g_hg, g_sd, want_small, short=0):
 def _head_backward_raw(mask, occ, rec, g_m, g_d, g_o, ld, ldo, short=0):
     """eamm_op_motion_head_backward likewise -> (code, d mask logits [n,h,w,ld], d occlusion logits [n,h,w,ldo], d records)."""
     from eamm_amd import _lib
-    from eamm_amd.autograd_ops import _ptr, _stream
+    from eamm_amd._handle import ptr as _ptr, stream_ptr as _stream
     n, k1, h, w = mask.shape
     k = k1 - 1
     dev = mask.device
