@@ -264,8 +264,10 @@ int pack_conv(CtxBase* c, const HostConv& f, const int* map, int C0_packed, int 
     return upload_bias(c, &L->bias, f.b, (size_t)L->ntiles * L->BN);
 }
 
-// -> PatchLayer: the spatial-patch kernel of the UpBlock2d convolution (3x3), polyphase or collapsed-phase form
-int pack_patch(CtxBase* c, const HostConv& f, const int* map, int C0_packed, int C1_packed, bool poly, PatchLayer* P) {
+// -> PatchLayer: the spatial-patch kernel of the UpBlock2d convolution (3x3), polyphase or collapsed-phase form;
+// split_planes: also the three-plane bf16 image of the polyphase form (a layer that only runs split over workgroups needs none)
+int pack_patch(CtxBase* c, const HostConv& f, const int* map, int C0_packed, int C1_packed, bool poly, PatchLayer* P,
+               bool split_planes = false) {
     const int cin_packed = C0_packed + C1_packed;
     P->C0 = C0_packed;
     P->C1 = C1_packed;
@@ -276,6 +278,11 @@ int pack_patch(CtxBase* c, const HostConv& f, const int* map, int C0_packed, int
     else
         patch_pack_host(f.w.data(), f.Cout, f.Cin, map, cin_packed, packed.data());
     if (int rc = upload(c, poly ? &P->w_poly : &P->w, packed)) return rc;
+    if (poly && split_planes) {   // the whole-tile launches of such a layer run the split-bf16 form (conv_mfma_patch_poly.hip)
+        std::vector<float> planes(patch_poly_split_packed_elems(cin_packed, f.Cout));
+        patch_poly_pack_split_host(f.w.data(), f.Cout, f.Cin, map, cin_packed, reinterpret_cast<uint16_t*>(planes.data()));
+        if (int rc = upload(c, &P->w_poly3, planes)) return rc;
+    }
     return upload_bias(c, &P->bias, f.b, (size_t)((f.Cout + 63) / 64) * 64);
 }
 
@@ -323,9 +330,10 @@ int build_layer(CtxBase* c, const std::vector<FoldSpec>& parts, int ks, int C0_r
 }
 
 // A 3x3 layer (MODE_PLAIN, or MODE_PHASE: the layer consumes the low-resolution input of an UpBlock2d and evaluates
-// "nearest x2 + 3x3" as four 2x2 phase filters) packed for every kernel that may run it (pick(), launch_up())
+// "nearest x2 + 3x3" as four 2x2 phase filters) packed for every kernel that may run it (pick(), launch_up());
+// patch_split_planes: pack_patch's split_planes
 int build_set(CtxBase* c, const std::vector<FoldSpec>& parts, int C0_real, int C0_packed, int C1_real, int C1_packed,
-              LayerSet* S, LayerMode mode) {
+              LayerSet* S, LayerMode mode, bool patch_split_planes = false) {
     HostConv f;
     int rc = fold_conv(c, parts, 3, C0_real + C1_real, &f);
     if (rc) return rc;
@@ -354,7 +362,7 @@ int build_set(CtxBase* c, const std::vector<FoldSpec>& parts, int C0_real, int C
         }
     }
     if (mode == MODE_PHASE && parts.size() == 1 && !parts[0].norm.empty() && (Cout & 3) == 0 && c->patch_min_blocks >= 0) {
-        if ((rc = pack_patch(c, f, map.data(), C0_packed, C1_packed, c->patch_poly != 0, &S->patch))) return rc;
+        if ((rc = pack_patch(c, f, map.data(), C0_packed, C1_packed, c->patch_poly != 0, &S->patch, patch_split_planes))) return rc;
         S->has_patch = true;
     }
     return 0;

@@ -24,10 +24,23 @@
 //     (patch_poly_splits), raw phase sums go to a slab per split and patch_poly_reduce_kernel adds them in a fixed order
 //     with bias and activation.
 // fp32 throughout; only the summation order differs from the reference (measured at the prediction: DESIGN.md 5.2d).
+//
+// The products come in two forms (template parameter FORM of conv_patch_poly_kernel, as SPLIT of wino4_gemm_kernel):
+//   FORM 0: v_mfma_f32_32x32x2_f32 on the fp32 operands (everything above).
+//   FORM 1: (whole-tile launches of a layer that has the three-plane weight image) every fp32 operand is the EXACT sum of three
+//           bf16 values taken by truncation, a = a1 + a2 + a3, and a*b is the six products a1b3, a3b1, a2b1, a1b1, a2b2, a1b2 on
+//           v_mfma_f32_32x32x16_bf16 with fp32 accumulation into the same nine accumulators (the dropped terms are <= 2^-24
+//           relative): 108 MFMAs of 32 cycles per chunk and wave instead of 144 of 64.  The activations stay fp32 in HBM and LDS
+//           (same patch DMA, same swizzle); the row transform stays fp32 VALU and each transformed fragment -- the lane's 8 K
+//           values of the 32x32x16 operand are two of the 16-byte slots above, K steps 2S and 2S+1 -- is split in registers
+//           (wino4_split3).  The weights are split once on the host (patch_poly_pack_split_host), lane-linear 1 KiB images per
+//           (point, plane).  LDS ring: the patch keeps its two 32-channel stages (2 x 41 KiB), the weight planes come in 16-channel
+//           half-chunks (27 KiB) on a ring of two: 136 KiB, one barrier per half-chunk (54 MFMAs per wave).
 #include "conv_common.h"
 
 #include <algorithm>
 #include <cstdlib>
+#include <cstring>
 
 namespace eamm {
 
@@ -60,7 +73,8 @@ struct PatchPolyArgs {
     unsigned in0_bytes, in1_bytes, w_bytes;
     int B, H, W;           // low-resolution input size; output is [B,2H,2W,Cout]
     int tiles_x, tiles_y, ntiles;
-    const float* w;        // packed [ntile][cchunk][point 3i+j][32][32], swizzled
+    const float* w;        // packed [ntile][cchunk][point 3i+j][32][32], swizzled; FORM 1: the three-plane bf16 image of
+                           // patch_poly_pack_split_host, [ntile][16-channel half-chunk][point][plane][64 lanes][8]
     const float* bias;     // [>= ntiles*32]
     int Cout, act;
     float* out;
@@ -69,6 +83,8 @@ struct PatchPolyArgs {
     size_t slab;           // floats per slab
 };
 
+// FORM: the product form (file header): 0 fp32 MFMA, 1 six bf16 MFMAs on the three-way split operands.
+template <int FORM>
 __global__ __launch_bounds__(ZWAVES * 64) void conv_patch_poly_kernel(const PatchPolyArgs p) {
     constexpr int BK = CONV_BK;
     constexpr int A_STAGE = ZPAD * BK;            // floats (41 KiB)
@@ -77,7 +93,12 @@ __global__ __launch_bounds__(ZWAVES * 64) void conv_patch_poly_kernel(const Patc
     constexpr int A_INSTR = (A_PIECES + ZWAVES - 1) / ZWAVES;    // per wave: 6
     constexpr int B_INSTR = (B_PIECES + ZWAVES - 1) / ZWAVES;    //           5
     static_assert(A_INSTR + B_INSTR <= 12, "one DMA piece per sub-step");
-    extern __shared__ __attribute__((aligned(16))) float smem[];  // [2][A_STAGE] [2][B_STAGE]
+    // FORM 1: the planes of a 16-channel half-chunk, 9 points x 3 planes x 1 KiB (27 KiB), 27 pieces: 4 per wave; and half of a
+    // chunk's patch pieces per half-chunk
+    constexpr int B3_STAGE = 9 * 3 * 256;         // floats
+    constexpr int B3_PIECES = 9 * 3, B3_INSTR = (B3_PIECES + ZWAVES - 1) / ZWAVES, A_HALF = A_INSTR / 2;
+    static_assert(A_INSTR % 2 == 0 && B3_INSTR + A_HALF <= 9, "one DMA piece per point of a half-chunk");
+    extern __shared__ __attribute__((aligned(16))) float smem[];  // [2][A_STAGE] [2][B_STAGE]; FORM 1: [2][A_STAGE] [2][B3_STAGE]
     float* const As = smem;
     float* const Bs = smem + 2 * A_STAGE;
 
@@ -136,6 +157,16 @@ __global__ __launch_bounds__(ZWAVES * 64) void conv_patch_poly_kernel(const Patc
         if (wave + ZWAVES * j < B_PIECES) {
             const unsigned so = (unsigned)((ntile * cchunks + cc) * B_STAGE + (wave + ZWAVES * j) * (8 * BK)) * 4u;
             float* dst = Bs + st * B_STAGE + (wave + ZWAVES * j) * (8 * BK);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (lds_ptr_t)dst, 16, w_lane, so, 0, 0);
+        }
+    };
+
+    // FORM 1: piece id = wave + 8 j of the 27 KiB of half-chunk hc (= 2 cc + S), lane-linear
+    auto dma_plane_piece = [&](auto jc, int hc, int wst) {
+        constexpr int j = decltype(jc)::value;
+        if (wave + ZWAVES * j < B3_PIECES) {
+            const unsigned so = (unsigned)((ntile * 2 * cchunks + hc) * B3_STAGE + (wave + ZWAVES * j) * 256) * 4u;
+            float* dst = Bs + wst * B3_STAGE + (wave + ZWAVES * j) * 256;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (lds_ptr_t)dst, 16, w_lane, so, 0, 0);
         }
     };
@@ -222,12 +253,87 @@ __global__ __launch_bounds__(ZWAVES * 64) void conv_patch_poly_kernel(const Patc
         __syncthreads();
     };
 
+    // FORM 1, half-chunk S of chunk cc: K step of 16 channels = the fp32 form's steps 2 S and 2 S + 1.  Per point the fp32 row and
+    // column transform on both slots, the split into three bf16x8 planes, three ds_read_b128 of weight planes and six MFMAs; one DMA
+    // piece behind the MFMAs of points 0 .. 6: the planes of the next half-chunk first, then half of the next chunk's patch.
+    auto half_chunk = [&](int cc, auto Sc) {
+        constexpr int S = decltype(Sc)::value;
+        const int st = (cc - c_begin) & 1;
+        const float* a_stage = As + st * A_STAGE;
+        const float* b_stage = Bs + S * B3_STAGE + lane * 4;
+        const bool more = cc + 1 < c_end;
+        // point pt = 3 i + j needs column col(j) = 1, 0, 2 of row i's neighbourhood row (centre, above, below) and, off the centre
+        // row, the centre pixel of that column again (re-read from LDS: it is cheaper than 24 registers held over the half-chunk)
+        f32x4 xr[2], cr[2], r1[2];   // the row's pixel and the centre row's, both slots; r1: column 1 of row i after the row transform
+        u32x4 ap[3], ub[3];          // the point's three activation planes and three weight planes
+        auto load_raw = [&](auto ptc) {
+            constexpr int pt = decltype(ptc)::value, i = pt / 3, j = pt % 3;
+            constexpr int col = j == 0 ? 1 : j == 1 ? 0 : 2, row = i == 0 ? 1 : i == 1 ? 0 : 2;
+            static_for<2>([&](auto hc) {
+                constexpr int h2 = decltype(hc)::value;
+                xr[h2] = *reinterpret_cast<const f32x4*>(a_stage + (ta[3 * row + col] ^ (8 * (2 * S + h2))));
+                if constexpr (i > 0) cr[h2] = *reinterpret_cast<const f32x4*>(a_stage + (ta[3 + col] ^ (8 * (2 * S + h2))));
+            });
+        };
+        auto load_planes = [&](auto ptc) {
+            constexpr int pt = decltype(ptc)::value;
+            static_for<3>([&](auto plc) {
+                constexpr int pl = decltype(plc)::value;
+                ub[pl] = *reinterpret_cast<const u32x4*>(b_stage + (pt * 3 + pl) * 256);
+            });
+        };
+        auto split_point = [&](auto ptc) {
+            constexpr int pt = decltype(ptc)::value, i = pt / 3, j = pt % 3;
+            f32x4 r[2];
+            static_for<2>([&](auto hc) {
+                constexpr int h2 = decltype(hc)::value;
+                if constexpr (i == 0) r[h2] = xr[h2]; else r[h2] = pk_sub4(xr[h2], cr[h2]);
+                if constexpr (j == 0) r1[h2] = r[h2]; else r[h2] = pk_sub4(r[h2], r1[h2]);
+            });
+            wino4_split3(r[0], r[1], ap);
+        };
+        // Per point: its weight planes are read under its own split, the next point's pixels under its MFMAs.
+        load_raw(std::integral_constant<int, 0>{});
+        static_for<9>([&](auto ptc) {
+            constexpr int pt = decltype(ptc)::value;
+            load_planes(ptc);
+            __builtin_amdgcn_sched_barrier(0);
+            split_point(ptc);
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (pt + 1 < 9) load_raw(std::integral_constant<int, pt + 1>{});
+            __builtin_amdgcn_sched_barrier(0);
+            static_for<6>([&](auto tc) {   // a1b3 | a3b1 a2b1 a1b1 | a2b2 a1b2
+                constexpr int t = decltype(tc)::value;
+                constexpr int pa = t == 0 ? 0 : t == 1 ? 2 : t == 2 ? 1 : t == 3 ? 0 : t == 4 ? 1 : 0;
+                constexpr int pb = t == 0 ? 2 : t <= 3 ? 0 : 1;
+                acc[pt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, ap[pa]),
+                                                                  __builtin_bit_cast(bf16x8_t, ub[pb]), acc[pt], 0, 0, 0);
+            });
+            if constexpr (pt < B3_INSTR) {
+                if (S == 0 || more) dma_plane_piece(std::integral_constant<int, pt>{}, 2 * cc + S + 1, S ^ 1);
+            } else if constexpr (pt - B3_INSTR < A_HALF) {
+                if (more) dma_patch_piece(std::integral_constant<int, A_HALF * S + pt - B3_INSTR>{}, cc + 1, st ^ 1);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        });
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+    };
+
     // ---- main loop over channel chunks
     static_for<A_INSTR>([&](auto jc) { dma_patch_piece(jc, c_begin, 0); });
-    static_for<B_INSTR>([&](auto jc) { dma_weight_piece(jc, c_begin, 0); });
+    if constexpr (FORM == 1) static_for<B3_INSTR>([&](auto jc) { dma_plane_piece(jc, 2 * c_begin, 0); });
+    else static_for<B_INSTR>([&](auto jc) { dma_weight_piece(jc, c_begin, 0); });
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    for (int cc = c_begin; cc < c_end; ++cc) chunk(cc);
+    if constexpr (FORM == 1) {
+        for (int cc = c_begin; cc < c_end; ++cc) {
+            half_chunk(cc, std::integral_constant<int, 0>{});
+            half_chunk(cc, std::integral_constant<int, 1>{});
+        }
+    } else {
+        for (int cc = c_begin; cc < c_end; ++cc) chunk(cc);
+    }
 
     // ---- epilogue: form each phase (3 adds per output), stage its 256 x 32 tile through LDS, store 16-byte pieces
     constexpr int LDO = ZBN + 4, C4 = ZBN / 4, NTHR = ZWAVES * 64, PER = ZT * ZT * C4 / NTHR;
@@ -304,32 +410,68 @@ size_t patch_poly_packed_elems(int Cin_packed, int Cout) {
     return (size_t)((Cout + ZBN - 1) / ZBN) * (Cin_packed / CONV_BK) * 9 * ZBN * CONV_BK;
 }
 
-// w: 3x3 weights [Cout][Cin][3][3] (BatchNorm folded) -> U = G w G^T, G = [1 1 1; 1 0 0; 0 0 1], laid out
-// [ntile][cchunk][point 3i+j][32][32], LDS swizzle applied.
-void patch_poly_pack_host(const float* w, int Cout, int Cin, const int* cin_map, int cin_packed, float* dst) {
+namespace {
+// w: 3x3 weights [Cout][Cin][3][3] (BatchNorm folded) -> U = G w G^T, G = [1 1 1; 1 0 0; 0 0 1], computed in double;
+// calls put(o, packed input channel, point 3i+j, (float)u) for every U element of a mapped channel
+template <typename F>
+void patch_poly_for_each_u(const float* w, int Cout, int Cin, const int* cin_map, int cin_packed, F&& put) {
     static const double G[3][3] = {{1, 1, 1}, {1, 0, 0}, {0, 0, 1}};
-    const int BK = CONV_BK, cch = cin_packed / BK;
-    const size_t total = patch_poly_packed_elems(cin_packed, Cout);
-    for (size_t i = 0; i < total; ++i) dst[i] = 0.f;
     for (int o = 0; o < Cout; ++o) {
-        const int nt = o / ZBN, nl = o % ZBN;
         for (int cp = 0; cp < cin_packed; ++cp) {
             const int c = cin_map ? cin_map[cp] : cp;
             if (c < 0 || c >= Cin) continue;
             const float* s = w + ((size_t)o * Cin + c) * 9;
-            const int cc = cp / BK, kl = cp % BK;
-            const int kk = ((((kl >> 2) ^ ((nl >> 1) & 7)) << 2) | (kl & 3));
             for (int pt = 0; pt < 9; ++pt) {
                 const int i = pt / 3, j = pt % 3;
                 double u = 0.0;
                 for (int a = 0; a < 3; ++a)
                     for (int b2 = 0; b2 < 3; ++b2) u += G[i][a] * G[j][b2] * (double)s[a * 3 + b2];
-                const size_t tile = ((size_t)nt * cch + cc) * 9 + pt;
-                dst[(tile * ZBN + nl) * BK + kk] = (float)u;
+                put(o, cp, pt, (float)u);
             }
         }
     }
 }
+}  // namespace
+
+// U laid out [ntile][cchunk][point 3i+j][32][32], LDS swizzle applied.
+void patch_poly_pack_host(const float* w, int Cout, int Cin, const int* cin_map, int cin_packed, float* dst) {
+    const int BK = CONV_BK, cch = cin_packed / BK;
+    const size_t total = patch_poly_packed_elems(cin_packed, Cout);
+    for (size_t i = 0; i < total; ++i) dst[i] = 0.f;
+    patch_poly_for_each_u(w, Cout, Cin, cin_map, cin_packed, [&](int o, int cp, int pt, float u) {
+        const int nt = o / ZBN, nl = o % ZBN;
+        const int cc = cp / BK, kl = cp % BK;
+        const int kk = ((((kl >> 2) ^ ((nl >> 1) & 7)) << 2) | (kl & 3));
+        const size_t tile = ((size_t)nt * cch + cc) * 9 + pt;
+        dst[(tile * ZBN + nl) * BK + kk] = u;
+    });
+}
+
+// The same U as three bf16 planes for FORM 1 of conv_patch_poly_kernel: the fp32-ROUNDED value of patch_poly_pack_host is split by
+// truncation, u1 = top 16 bits of u, u2 = top 16 bits of u - u1, u3 = u - u1 - u2 (both differences exact), so u1 + u2 + u3 is
+// that float exactly.  Image [ntile][16-channel half-chunk][point][3 planes][64 lanes][8]: a (point, plane) of a half-chunk is the
+// 1 KiB a wave reads with ONE ds_read_b128 per lane, lane-linear (conflict-free).  Lane = 32 h + (output channel % 32) holds the
+// half-chunk's channels 4 h + e (e < 4) and 8 + 4 h + (e - 4) (e >= 4): the lane's two 16-byte slots of the fp32 patch pixel.
+void patch_poly_pack_split_host(const float* w, int Cout, int Cin, const int* cin_map, int cin_packed, uint16_t* dst) {
+    const int hch = cin_packed / 16;
+    const size_t total = 3 * patch_poly_packed_elems(cin_packed, Cout);
+    for (size_t i = 0; i < total; ++i) dst[i] = 0;
+    auto bits = [](float f) { uint32_t b; memcpy(&b, &f, 4); return b; };
+    auto top = [](uint32_t b) { b &= 0xFFFF0000u; float f; memcpy(&f, &b, 4); return f; };
+    patch_poly_for_each_u(w, Cout, Cin, cin_map, cin_packed, [&](int o, int cp, int pt, float u) {
+        const int nt = o / ZBN, nl = o % ZBN;
+        const int hc = cp / 16, kl = cp % 16;
+        const int lane = ((kl >> 2) & 1) * 32 + nl, e = (kl >> 3) * 4 + (kl & 3);
+        const float r = u - top(bits(u)), r2 = r - top(bits(r));
+        uint16_t* blk = dst + ((((size_t)nt * hch + hc) * 9 + pt) * 3) * 512 + lane * 8 + e;
+        blk[0] = (uint16_t)(bits(u) >> 16);
+        blk[512] = (uint16_t)(bits(r) >> 16);
+        blk[1024] = (uint16_t)(bits(r2) >> 16);
+    });
+}
+
+// floats of device memory the three-plane image takes (six bytes per U element)
+size_t patch_poly_split_packed_elems(int Cin_packed, int Cout) { return patch_poly_packed_elems(Cin_packed, Cout) * 3 / 2; }
 
 hipError_t patch_poly_launch(const PatchLayer& L, const float* in0, const float* in1, int B, int H, int W, int act,
                               float* out, hipStream_t stream, int splits, float* partial, size_t partial_cap) {
@@ -342,7 +484,10 @@ hipError_t patch_poly_launch(const PatchLayer& L, const float* in0, const float*
     a.C0 = L.C0;
     a.C1 = L.C1;
     const size_t px = (size_t)B * H * W;
-    const size_t b0 = px * L.C0 * 4, b1 = px * L.C1 * 4, bw = patch_poly_packed_elems(L.C0 + L.C1, L.Cout) * 4;
+    // the split-bf16 product form: the whole-tile launches of a layer that has the three-plane image (the decoder's up blocks)
+    const bool split = splits == 1 && L.w_poly3 != nullptr;
+    const size_t b0 = px * L.C0 * 4, b1 = px * L.C1 * 4,
+                 bw = (split ? patch_poly_split_packed_elems(L.C0 + L.C1, L.Cout) : patch_poly_packed_elems(L.C0 + L.C1, L.Cout)) * 4;
     if (b0 >= 0xFFFFFFF0ull || b1 >= 0xFFFFFFF0ull || bw >= 0xFFFFFFF0ull) return hipErrorInvalidValue;
     a.in0_bytes = (unsigned)b0;
     a.in1_bytes = (unsigned)b1;
@@ -353,7 +498,7 @@ hipError_t patch_poly_launch(const PatchLayer& L, const float* in0, const float*
     a.tiles_x = (W + ZT - 1) / ZT;
     a.tiles_y = (H + ZT - 1) / ZT;
     a.ntiles = (L.Cout + ZBN - 1) / ZBN;
-    a.w = L.w_poly;
+    a.w = split ? L.w_poly3 : L.w_poly;
     a.bias = L.bias;
     a.Cout = L.Cout;
     a.act = act;
@@ -361,15 +506,18 @@ hipError_t patch_poly_launch(const PatchLayer& L, const float* in0, const float*
     a.splits = splits;
     a.partial = partial;
     a.slab = slab;
-    constexpr size_t lds_loop = sizeof(float) * 2 * (ZPAD * CONV_BK + 9 * ZBN * CONV_BK);
+    constexpr size_t lds_loop0 = sizeof(float) * 2 * (ZPAD * CONV_BK + 9 * ZBN * CONV_BK);   // 154 KiB
+    constexpr size_t lds_loop1 = sizeof(float) * 2 * (ZPAD * CONV_BK + 9 * 3 * 256);          // 136 KiB
     constexpr size_t lds_epi = sizeof(float) * (ZT * ZT) * (ZBN + 4);
-    constexpr size_t lds = lds_loop > lds_epi ? lds_loop : lds_epi;
-    static_assert(lds <= 160 * 1024, "LDS budget");
-    static lds_once_mask configured{0};
-    if (hipError_t e = ensure_dynamic_lds(conv_patch_poly_kernel, lds, &configured); e != hipSuccess) return e;
+    static_assert(lds_loop0 <= 160 * 1024 && lds_loop0 >= lds_loop1 && lds_loop1 >= lds_epi, "LDS budget");
+    const size_t lds = split ? lds_loop1 : lds_loop0;
+    static lds_once_mask configured[2] = {{0}, {0}};
+    const auto kern = split ? conv_patch_poly_kernel<1> : conv_patch_poly_kernel<0>;
+    if (hipError_t e = ensure_dynamic_lds(kern, lds, &configured[split]); e != hipSuccess) return e;
     const int blocks = a.tiles_x * a.tiles_y * B * a.ntiles * splits;
+    // the fp32-equivalent multiply-adds, whatever the product form
     note_mfma_flops(2.0 * a.tiles_x * a.tiles_y * B * (ZT * ZT) * 9.0 * (a.ntiles * ZBN) * (L.C0 + L.C1));
-    hipLaunchKernelGGL(conv_patch_poly_kernel, dim3(blocks), dim3(ZWAVES * 64), lds, stream, a);
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(ZWAVES * 64), lds, stream, a);
     if (splits > 1) {
         const size_t total4 = slab / 4;
         const int rb = (int)std::min<size_t>((total4 + 255) / 256, 4096);

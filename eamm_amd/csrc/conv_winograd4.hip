@@ -193,31 +193,6 @@ __constant__ float WINO4_AT[4][8] = {{1.f, 1.f, 1.f, 1.f, 1.f, 0.f, 0.f, 0.f},
                                      {0.f, 1.f, 1.f, 4.f, 4.f, 0.f, 0.f, 0.f},
                                      {0.f, 1.f, -1.f, 8.f, -8.f, 1.f, 0.f, 0.f}};
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-
-// bf16 pair {hi16(lo), hi16(hi)}: one v_perm_b32
-__device__ __forceinline__ unsigned wino4_hi_pair(unsigned lo, unsigned hi) { return __builtin_amdgcn_perm(hi, lo, 0x07060302u); }
-
-// Eight fp32 values -> three planes of eight bf16, by truncation: a1 = top 16 bits of a, r = a - a1 (exact), a2 = top 16 bits
-// of r, a3 = r - a2 (exact, at most 8 significant bits: its low half is zero).  a1 + a2 + a3 == a; inf / NaN give NaN residuals.
-__device__ __forceinline__ void wino4_split3(const f32x4_t& x0, const f32x4_t& x1, u32x4 (&pl)[3]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {   // a pair at a time: few temporaries
-        unsigned b1[2], b2[2], b3[2];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const float x = i < 2 ? x0[2 * i + h] : x1[2 * i - 4 + h];
-            b1[h] = __float_as_uint(x);
-            const float r = x - __uint_as_float(b1[h] & 0xFFFF0000u);
-            b2[h] = __float_as_uint(r);
-            b3[h] = __float_as_uint(r - __uint_as_float(b2[h] & 0xFFFF0000u));
-        }
-        pl[0][i] = wino4_hi_pair(b1[0], b1[1]);
-        pl[1][i] = wino4_hi_pair(b2[0], b2[1]);
-        pl[2][i] = wino4_hi_pair(b3[0], b3[1]);
-    }
-}
-
 // A wave owns 16 Winograd tiles x NT*16 output channels; WM x WN waves per block.  SUB: 32-channel chunks per
 // barrier interval; NST: LDS ring depth in intervals; PE: one DMA piece every PE MFMAs from the start of an interval.
 // SPLIT: the product form (file header): 0 fp32 MFMA, 1 six bf16 MFMAs on the three-way split operands.

@@ -449,7 +449,7 @@ int eamm_finalize_weights(eamm_ctx* c) {
     for (int i = 0; i < c->nd; ++i) {
         const std::string p = "up_blocks." + std::to_string(i);
         const int ci = i == 0 ? c->Cb : c->up_c[i - 1];
-        if ((rc = build_set(c, {{p + ".conv", nm(p + ".norm")}}, ci, ci, 0, 0, &c->up[i], MODE_PHASE))) return rc;
+        if ((rc = build_set(c, {{p + ".conv", nm(p + ".norm")}}, ci, ci, 0, 0, &c->up[i], MODE_PHASE, true))) return rc;
     }
     if (c->Cimg > 3) {   // more than three outputs: the plain 7x7 kernel (N padded to its 32-column tile), sigmoid and the NCHW
         // store in its epilogue -- correct for any channel count, ten times the minimal work: RGBA is not the shipped case

@@ -64,17 +64,18 @@ int op_conv_col7(OpBuffers* t, const ConvOp& a) {
     return EAMM_OK;
 }
 
-// spatial-patch kernels of the up-convolution: 3000 collapsed-phase form, 3003 polyphase minimal-filtering form (splitk > 1:
-// its channel reduction over that many workgroups)
+// spatial-patch kernels of the up-convolution: 3000 collapsed-phase form, 3003 polyphase minimal-filtering form as the engine
+// runs a decoder up block (splitk > 1: its channel reduction over that many workgroups, fp32 products; else the split-bf16
+// products), 3004 the polyphase form with fp32 products forced
 int op_conv_patch(OpBuffers* t, const ConvOp& a) {
-    const bool pp = a.tile_n == 3003;
+    const bool pp = a.tile_n == 3003 || a.tile_n == 3004;
     const int psplit = a.splitk > 1 ? a.splitk : 1;
     if (a.kh != 3 || a.kw != 3 || !a.up || a.pool || a.resid || (a.Cout & 3) || (psplit > 1 && (!pp || ((a.C0 + a.C1) / 32) % psplit)))
         return fail(t, EAMM_ERR_ARG, "eamm_op_conv: unsupported patch-kernel configuration");
     PatchLayer P;
     float* ppart = nullptr;
     const size_t ppart_elems = psplit > 1 ? (size_t)psplit * a.B * 4 * a.Hin * a.Win * a.Cout : 0;
-    int rc = pack_patch(t, op_weights(a, a.C0 + a.C1), nullptr, a.C0, a.C1, pp, &P);
+    int rc = pack_patch(t, op_weights(a, a.C0 + a.C1), nullptr, a.C0, a.C1, pp, &P, a.tile_n == 3003);
     if (rc || (psplit > 1 && (rc = dev_alloc(t, &ppart, ppart_elems)))) return rc;
     auto patch = [&]() {
         return pp ? patch_poly_launch(P, a.in0, a.in1, a.B, a.Hin, a.Win, a.act, a.out, a.s, psplit, ppart, ppart_elems)
@@ -149,7 +150,7 @@ int op_conv_run(OpBuffers* t, const ConvOp& a) {
     int rc;
     if (a.tile_n == 4002) rc = op_conv_final(t, a);
     else if (a.tile_n == 4000 || a.tile_n == 4001) rc = op_conv_col7(t, a);
-    else if (a.tile_n == 3000 || a.tile_n == 3003) rc = op_conv_patch(t, a);
+    else if (a.tile_n == 3000 || a.tile_n == 3003 || a.tile_n == 3004) rc = op_conv_patch(t, a);
     else if (a.tile_n >= 2000 && a.tile_n < 2200) rc = op_conv_wino(t, a);
     else rc = op_conv_gemm(t, a);
     if (rc) return rc;

@@ -104,11 +104,16 @@ struct PatchLayer {
     int C0 = 0, C1 = 0, Cout = 0;
     float* w = nullptr;     // device, packed [ntile][cchunk][phase][tap][64][32]
     float* w_poly = nullptr;  // device, polyphase minimal-filtering form [ntile 32][cchunk][point 9][32][32] (conv_mfma_patch_poly.hip)
+    float* w_poly3 = nullptr; // device, layers whose whole-tile launches run the split-bf16 product form: the same U as three bf16
+                              // planes (patch_poly_pack_split_host); nullptr: fp32 form only
     float* bias = nullptr;  // device, [ntiles*64]
 };
 size_t patch_packed_elems(int Cin_packed, int Cout);
 size_t patch_poly_packed_elems(int Cin_packed, int Cout);
 void patch_poly_pack_host(const float* w_oihw_3x3, int Cout, int Cin, const int* cin_map, int cin_packed, float* dst);
+// U as three bf16 planes whose sum is patch_poly_pack_host's float exactly; patch_poly_split_packed_elems: its size in FLOATS (x 1.5)
+size_t patch_poly_split_packed_elems(int Cin_packed, int Cout);
+void patch_poly_pack_split_host(const float* w_oihw_3x3, int Cout, int Cin, const int* cin_map, int cin_packed, uint16_t* dst);
 // splits > 1: the channel reduction split over that many workgroups per tile, raw sums into partial[splits][B,2H,2W,Cout]
 // (partial_cap floats), finished by patch_poly_reduce_kernel; patch_poly_splits picks the split for a launch
 hipError_t patch_poly_launch(const PatchLayer& L, const float* in0, const float* in1, int B, int H, int W, int act,

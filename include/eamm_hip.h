@@ -485,8 +485,11 @@ int eamm_profile_read(eamm_ctx* ctx, double* stage_ms, int nstage, int64_t* call
  *   2100 + variant   Winograd F(4x4,3x3) (as 2000, Hin and Win multiples of 4); variant 0 | 3 | 6: the GEMM's software pipeline
  *   2150 + groups    F(4x4,3x3) with the transform-point rows split over 2, 3 or 6 workgroups + output-transform
  *                    kernel (pool allowed without resid)
- *   3000 / 3003      spatial-patch kernel of the up-convolution (up = 1): collapsed-phase / polyphase form (3003 only:
- *                    splitk > 1 splits the channel reduction)
+ *   3000 / 3003      spatial-patch kernel of the up-convolution (up = 1): collapsed-phase / polyphase form.  3003 is the
+ *                    polyphase form as the engine runs a decoder up block: whole-tile launches form every product as six
+ *                    bf16 MFMAs on exact three-way bf16 splits of the fp32 operands (fp32-exact to 2^-24 relative);
+ *                    splitk > 1 splits the channel reduction over workgroups and keeps the fp32 MFMA
+ *   3004             the polyphase form with fp32-MFMA products forced (splitk as 3003)
  *   4000 / 4001      column-patch kernel of a row-split 7x1 convolution (weights [Cout][C][7][1], no bias applied, act 0):
  *                    4000 the final layer (Cout 32, C0 32 or 64, no in1), 4001 the flow head (Cout 96, two inputs)
  *   4002             the generator's final layer whole (7x7, Cout 3, act 2: out is NCHW [B,3,H,W])
