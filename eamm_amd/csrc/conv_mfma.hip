@@ -474,6 +474,9 @@ hipError_t conv_launch(const ConvLayer& L, const ConvIO& io, hipStream_t stream,
     a.split_n = io.split_n;
     if (io.split_n > 0 && (io.out2 == nullptr || io.resid != nullptr || io.pool || io.nchw || L.Cout > io.split_n + 4 || L.Cout <= io.split_n))
         return hipErrorInvalidValue;
+    // the pooled epilogue (conv_epilogue, splitk_reduce_kernel) writes 0.25 * sum act(acc + bias) and nothing else: no caller combines
+    // it with these, and a call that did would get its answer without them
+    if (io.pool && (io.resid != nullptr || io.nchw || io.out2 != nullptr || io.split_n > 0)) return hipErrorInvalidValue;
     a.linear = ((a.H | a.W) & 1) ? 1 : 0;                   // odd side: raster order (2x2 quads need even sides)
     if (a.linear && io.pool) return hipErrorInvalidValue;   // AvgPool2d(2) windows are the quads
     if (pl.splits > 1 && io.partial == nullptr) return hipErrorInvalidValue;

@@ -1,5 +1,5 @@
 // The generator handle and what its C-ABI translation units share: eamm_api.hip (handle, weights, workspace, source encoding),
-// eamm_forward.hip (launch plan, per-frame pass, profiling), eamm_op_api.hip (operator entries), eamm_train_api.hip.
+// eamm_forward.hip (launch plan, per-frame pass, profiling), eamm_op_*.hip (operator entries, over op_common.h), eamm_train_api.hip.
 #pragma once
 #include "../../include/eamm_hip.h"
 #include "api_common.h"

@@ -473,7 +473,8 @@ int eamm_profile_read(eamm_ctx* ctx, double* stage_ms, int nstage, int64_t* call
  * the path on caller-provided device buffers so it can be compared with the oracle in isolation.
  */
 
-/* KHxKW (3x3, 7x7 or 7x1) convolution on NHWC activations as an fp32-MFMA implicit GEMM.
+/* KHxKW (3x3, 7x7 or 7x1; 1x1 on tile codes 0 / 32 / 64 / 128 with up = 0, see eamm_op_conv_ex) convolution on NHWC activations as an
+ * fp32-MFMA implicit GEMM.
  * in0/in1: [B,Hin,Win,C0|C1] (in1 optional: channel concatenation), weight: OIHW host pointer
  * [Cout,C0+C1,kh,kw], bias host [Cout]; up = 1 (3x3 only) computes conv3x3(nearest_x2(input)) in its
  * collapsed four-phase 2x2 form; act: 0 none, 1 relu, 2 sigmoid; pool = 1 applies avgpool2x2 after the
@@ -500,6 +501,35 @@ int eamm_op_conv(int device, const float* in0, int C0, const float* in1, int C1,
                  const float* weight_host, const float* bias_host, int Cout, int kh, int kw,
                  int act, int pool, const float* resid, int splitk, int tile_n, float* out, int iters,
                  float* avg_ms, void* stream);
+
+/* eamm_op_conv with the operands that only the engine sets (eamm_op_conv is this call with all seven zero; tests/test_gpu_conv_modes.py):
+ *   pre_scale, pre_shift   device [C0], both or neither: the Winograd input transform applies the ResBlock pre-activation
+ *                          relu(x * pre_scale + pre_shift) first; the halo stays zero padding of the ACTIVATED tensor.  Tile codes
+ *                          2000 and 21xx only.
+ *   out2, scale2, shift2   second output relu(out * scale2 + shift2), NHWC like out (the next block's pre-activation); scale2,
+ *                          shift2 device [Cout], both with out2.
+ *   nchw                   1: out is written [B,Cout,H,W].
+ *   split_n                > 0: channels n < split_n go to out as NHWC with a split_n-float pixel stride, channels split_n <= n <
+ *                          Cout to out2 as one float4 per pixel (floats past Cout - split_n are not written); needs out2 (scale2,
+ *                          shift2 unused), no resid / pool / nchw, split_n < Cout <= split_n + 4.
+ *   The last five: the implicit GEMM only (tile codes 0, 32, 64, 128, 1001..1005).
+ * kh = kw = 1 (a dense layer on a 1x1 map, or a pointwise convolution) is accepted on the register-staged kernel (tile codes 0, 32,
+ * 64, 128) with up = 0.  pool combines with none of resid, nchw, out2, split_n.  pre_scale, pre_shift, out2, scale2 and shift2 are
+ * 16-byte aligned (the kernels access them four floats at a time).  Every rule above is checked before any device work: EAMM_ERR_ARG,
+ * message in eamm_last_error(NULL). */
+int eamm_op_conv_ex(int device, const float* in0, int C0, const float* in1, int C1, int B, int Hin, int Win, int up,
+                    const float* weight_host, const float* bias_host, int Cout, int kh, int kw,
+                    int act, int pool, const float* resid, int splitk, int tile_n, float* out, int iters,
+                    float* avg_ms, const float* pre_scale, const float* pre_shift, float* out2, const float* scale2,
+                    const float* shift2, int nchw, int split_n, void* stream);
+
+/* The Winograd input transform of the 3x3 / pad 1 convolution on its own, as the engine launches it: x NHWC [B,H,W,C] ->
+ * V[(tile + 2)^2][B * H/tile * W/tile][C] = B^T d B of every (tile + 2)^2 patch d (stride tile, one pixel of zero padding), tile = 2
+ * (F(2x2,3x3)) or 4 (F(4x4,3x3)); with scale / shift (device [C], both or neither) d is taken from relu(x * scale + shift), the
+ * padding staying zero.  H, W multiples of tile, C of 4, pointers 16-byte aligned, fewer than 2^31 output elements; EAMM_ERR_ARG
+ * before any launch otherwise.  Stream-ordered, no sync. */
+int eamm_op_wino_transform(int device, const float* x, const float* scale, const float* shift, int B, int H, int W, int C, int tile,
+                           float* V, void* stream);
 
 /* Temporal smoothing of a clip's key points: the reference's filter1.OneEuroFilter (filter1.py:13-47)
  * applied as `process(x * scale) / scale` frame after frame (demo.py:241-250; key points: mincutoff 0.05, beta 8, dcutoff 1,
@@ -562,6 +592,11 @@ int eamm_op_emotion_augment(int device, const float* aligned, int64_t n_src, int
  * launches with HIP events on `stream` (bench.py's isolated roofline_warp figure). */
 int eamm_op_warp(int device, const float* feat, const float* deformation, const float* occlusion, int n, int ns, int hf,
                  int wf, int C, int h, int w, float* out, int iters, float* avg_ms, void* stream);
+/* eamm_op_warp (which is this call with the three NULL) with the kernel's second output out2 = relu(out * scale2 + shift2), NHWC like
+ * out: the first ResBlock's pre-activation in the direct bottleneck form.  scale2, shift2: device [C]; all three or none. */
+int eamm_op_warp_ex(int device, const float* feat, const float* deformation, const float* occlusion, int n, int ns, int hf,
+                    int wf, int C, int h, int w, float* out, int iters, float* avg_ms, float* out2, const float* scale2,
+                    const float* shift2, void* stream);
 
 /*
  * Backward kernels of the path's two operator kinds, op level.  The reference gets these from
