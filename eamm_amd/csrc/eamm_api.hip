@@ -37,13 +37,6 @@ void expected_keys(const eamm_ctx* c, std::vector<std::string>* keys) {
 
 double conv_flops(int ks, int cin, int cout, double pixels) { return 2.0 * ks * ks * (double)cin * cout * pixels; }
 
-// The F(4x4) kernels address V ([36][tiles][Cin]) and Z ([24][tiles][Cout]) through 32-bit buffer descriptors
-// (wino4_gemm_launch refuses from 0xFFFFF000 bytes): a call with more tiles than this takes the direct kernels.
-bool wino4_fits(size_t tiles, int cin, int cout) {
-    return 36.0 * tiles * cin * 4.0 < 4294963200.0 && 24.0 * tiles * cout * 4.0 < 4294963200.0;
-}
-
-
 // ---- widths that are not multiples of 32 (reference modules/generator.py:14-48 accepts any): the state_dict is padded into
 // the equivalent network whose widths are the next multiples of 32 -- extra output channels get zero filters and a zero bias,
 // their BatchNorm is the identity (weight 1, bias 0, mean 0, variance 1), extra input channels get zero filter columns -- so
@@ -247,7 +240,11 @@ int eamm_create(const eamm_config* cfg, int device, eamm_ctx** out) {
     // chain count both derive from this value
     c->pass_chains = c->pass_chains < 0 ? 1 : std::min(c->pass_chains, 4);
     c->bneck_chains = std::max(1, std::min(c->bneck_chains, 16));
-    c->warp_joint = env_int("EAMM_WARP_JOINT", c->warp_joint);
+    if (getenv("EAMM_WARP_JOINT") && atoi(getenv("EAMM_WARP_JOINT")) != 0) {   // (a benchmark record labelled from it would be wrong)
+        delete c;
+        return fail(nullptr, EAMM_ERR_ARG, "EAMM_WARP_JOINT was removed: one feature-warp launch for all chains' frames measured "
+                    "-0.8 %% frames/s (DESIGN.md section 12, profiles/r04_experiments.txt section 3); unset it");
+    }
     c->wino4_variant = env_int("EAMM_WINO4_VARIANT", c->wino4_variant);
     c->wino4_variant_pinned = getenv("EAMM_WINO4_VARIANT") != nullptr;   // an explicit choice holds for every call size
     {   // read ONCE here, not per call (a device query in every forward_view of the per-frame path)
@@ -283,9 +280,6 @@ int eamm_create(const eamm_config* cfg, int device, eamm_ctx** out) {
     c->first7 = env_int("EAMM_FIRST7", c->first7);
     c->enc_wino_min_mflop = env_int("EAMM_ENC_WINO_MIN_MFLOP", c->enc_wino_min_mflop);
     c->enc_wino_min_tiles = env_int("EAMM_ENC_WINO_MIN_TILES", c->enc_wino_min_tiles);
-    c->dma_cfg_n256 = env_int("EAMM_DMA_CFG_N256", c->dma_cfg_n256);
-    c->dma_cfg_n128 = env_int("EAMM_DMA_CFG_N128", c->dma_cfg_n128);
-    c->dma_cfg_n64 = env_int("EAMM_DMA_CFG_N64", c->dma_cfg_n64);
     *out = c;
     return EAMM_OK;
 }
@@ -294,10 +288,9 @@ void eamm_destroy(eamm_ctx* c) {
     if (!c) return;
     DeviceGuard guard(c->device);
     free_owned(c);
-    for (auto& e : c->prof_events) (void)hipEventDestroy(e);
-    for (auto& e : c->prof_chain_ev) (void)hipEventDestroy(e);
+    for (auto& e : c->prof.events) (void)hipEventDestroy(e);
+    for (auto& e : c->prof.chain_ev) (void)hipEventDestroy(e);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    if (c->ev_warp) (void)hipEventDestroy(c->ev_warp);
     for (auto& e : c->ev_join) (void)hipEventDestroy(e);
     for (auto& st : c->own_streams) (void)hipStreamDestroy(st);   // (drains the stream's work first; the pool's streams stay)
     delete c;
@@ -601,7 +594,6 @@ int eamm_finalize_weights(eamm_ctx* c) {
     c->private_streams = env_int("EAMM_PRIVATE_STREAMS", 0);
     if (max_chains > 1) {
         HIP_TRY(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-        HIP_TRY(c, hipEventCreateWithFlags(&c->ev_warp, hipEventDisableTiming));
         for (int k = 1; k < max_chains; ++k) {
             hipStream_t st = chain_stream(c->device, k - 1);
             hipEvent_t ev = nullptr;
@@ -654,14 +646,9 @@ int eamm_encode_source(eamm_ctx* c, const float* source, int ns, void* stream_) 
         ConvIO d = conv_io(c->enc_tmp[i], ns, c->H >> i, c->W >> i, ACT_RELU, (i == c->nd - 1) ? c->feat : c->enc_tmp[i + 1], c->partial,
                            c->partial_elems);
         d.pool = 1;
-        const int tiles = ns * (d.Hin / 4) * (d.Win / 4);
-        if (i < (int)c->w4down.size() && c->w4down[i].Cout && c->wino_v && c->wino_z && tiles >= c->enc_wino_min_tiles &&
-            wino4_fits((size_t)tiles, c->w4down[i].Cin, c->w4down[i].Cout) &&
-            288e-6 * tiles * c->w4down[i].Cin * c->w4down[i].Cout >= (double)c->enc_wino_min_mflop) {
-            const WinoLayer& L = c->w4down[i];   // as the hourglass encoder levels (forward_view): pooled, so a point-row split of at least 2
-            const int g = wino4_row_split(c, tiles, L.ntiles, true);
-            HIP_TRY(c, wino4_transform_launch(d.in0, nullptr, nullptr, ns, d.Hin, d.Win, L.Cin, c->wino_v, s));
-            HIP_TRY(c, wino4_gemm_launch(L, c->wino_v, ns, d.Hin, d.Win, ACT_RELU, nullptr, d.out, s, 0, g, c->wino_z, 1));
+        // F(4x4) form as the hourglass encoder levels, by the source side's rule (eamm_ctx.h: Wino4Pooled)
+        if (i < (int)c->w4down.size() && wino4_pooled_pays(c, c->w4down[i], ns * (d.Hin / 4) * (d.Win / 4), Wino4Pooled::SOURCE)) {
+            if (int rc = launch_wino4_pooled(c, c->w4down[i], d.in0, ns, d.Hin, d.Win, d.out, c->wino_v, c->wino_z, s)) return rc;
             continue;
         }
         HIP_TRY(c, conv_launch(pick(c, c->down[i], (size_t)ns * d.Hin * d.Win), d, s));

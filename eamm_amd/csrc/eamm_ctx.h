@@ -1,5 +1,7 @@
 // The generator handle and what its C-ABI translation units share: eamm_api.hip (handle, weights, workspace, source encoding),
-// eamm_forward.hip (launch plan, per-frame pass, profiling), eamm_op_*.hip (operator entries, over op_common.h), eamm_train_api.hip.
+// eamm_forward.hip (launch plan, the per-frame pass as one function per stage, profiling), eamm_op_*.hip (operator entries, over
+// op_common.h), eamm_train_api.hip.  Around the handle: PassProfile (the stage profile), FrameView (the slice of the workspace one
+// launch sequence works on) and what eamm_forward.hip defines for the other translation units.
 #pragma once
 #include "../../include/eamm_hip.h"
 #include "api_common.h"
@@ -7,6 +9,46 @@
 #include <functional>
 
 using namespace eamm;
+
+// Optional stage timing of eamm_forward_frames with HIP events on the caller's stream (bench.py roofline leg) and the executed
+// matrix-core flops of every call: eamm_forward_frames brackets a call with begin_call / end_call, forward_view marks the stage
+// boundaries, eamm_profile_read folds the finished event sets into the totals (all in eamm_forward.hip).
+struct PassProfile {
+    static constexpr int NSTAGE = 22;      // front, hg_enc, hg_dec, head, warp, bneck_transform, bneck_conv, up, final + bneck_gemm_kernel
+                                           // + bneck_union_ms (wall time during which ANY chain is in its bottleneck stage), bneck_windows_ms (sum of
+                                           // the chains' bottleneck windows), exec_gflop / bneck_exec_gflop (executed MFMA GFLOP of the recorded
+                                           // calls, all chains: whole pass / bottleneck GEMMs) + 14..21 executed MFMA GFLOP of each of the eight
+                                           // recorded stage intervals (front, hg_enc, hg_dec, head, warp, bottleneck, up, final), all chains
+    static constexpr int MAXCHAIN = 4;     // chains whose bottleneck window is recorded per call
+    static constexpr int NMARK = 8;        // stage boundaries recorded per call (bottleneck is split from sub-events)
+    static constexpr int NSUB = 64;        // per-launch events inside the bottleneck (4 per res-block + 1)
+    static constexpr int PROF_CALLS = 256; // event sets kept before the host must read them
+    struct Call {                          // one recorded call
+        int n = 0, nchain = 0, sub = 0;    // frames; whole-pass chains recorded; sub-events used (0: direct form)
+        bool complete = false;             // every mark recorded (false: the call failed midway and its set is skipped)
+        double flops = 0, flops_bneck = 0, stage_flops[NMARK] = {0};   // executed MFMA flops, all chains: pass / bottleneck / per interval
+    };
+    bool on = false;
+    std::vector<hipEvent_t> events;        // PROF_CALLS * (NMARK+1 + NSUB): stage marks of the main stream's sequence, then sub-events
+    std::vector<hipEvent_t> chain_ev;      // PROF_CALLS * MAXCHAIN * 2: start / end of each whole-pass chain's bottleneck stage
+    std::vector<Call> calls;               // PROF_CALLS records, sized once by eamm_profile_enable: the first `used` await a read
+    int used = 0;
+    hipEvent_t *ev = nullptr, *cev = nullptr;   // the event sets of the call being enqueued (null: it is not recorded)
+    Call cur;                              // ... and its record (flops are counted whether or not it is recorded)
+    double ms[NSTAGE] = {0};
+    long ncalls = 0, nframes = 0;
+
+    void begin_call(int n, int chains);
+    void account(int interval);            // flops launched since the last mark belong to the stage interval that ends here
+    hipError_t mark(int i, hipStream_t s, int chain) {       // stage boundary i of chain `chain`'s sequence (events: chain 0 only)
+        if (i > 0) account(i - 1);
+        return ev && chain == 0 ? hipEventRecord(ev[i], s) : hipSuccess;
+    }
+    // one more per-launch event inside chain 0's bottleneck; edge 0 / 1: chain `chain` enters / leaves its bottleneck
+    hipError_t sub(hipStream_t s) { return ev && cur.sub < NSUB ? hipEventRecord(ev[NMARK + 1 + cur.sub++], s) : hipSuccess; }
+    hipError_t window(int chain, int edge, hipStream_t s) { return cev && chain < MAXCHAIN ? hipEventRecord(cev[2 * chain + edge], s) : hipSuccess; }
+    hipError_t end_call(hipStream_t s);                      // the last stage ends where the call ends (after the join)
+};
 
 struct eamm_ctx : eamm::CtxBase {
     eamm_config cfg{};
@@ -63,13 +105,10 @@ struct eamm_ctx : eamm::CtxBase {
     int private_streams = 0;               // EAMM_PRIVATE_STREAMS=1: always the private set
     int last_streams = 0;                  // which set the last call used: 0 pool, 1 private (pool taken), 2 private (capture)
     hipEvent_t ev_fork = nullptr;
-    hipEvent_t ev_warp = nullptr;          // recorded by the first chain behind the joint warp launch (EAMM_WARP_JOINT)
     int epi_v = 0;                         // EAMM_WINO4_EPI_V=1: timing experiment (wrong results): see conv_winograd4.hip DBG 30
     float* epi_scratch = nullptr;
-    int warp_joint = 0;                    // one feature-warp launch for all chains' frames
     std::vector<hipEvent_t> ev_join;
-    int cur_pass_chains = 1;               // whole-pass chains of the call being enqueued
-    int cur_call_frames = 0;               // ... and its frames (all chains)
+    int cur_call_frames = 0;               // frames of the call being enqueued (all chains)
     int wino_tile = 4;                     // preferred output tile (EAMM_WINO_TILE): 4 -> F(4x4) where it applies, 2 -> F(2x2)
     int wino4_variant = 6;                 // wino4_gemm_kernel pipeline variant, 0 | 3 | 6 (3: one DMA piece per 8 MFMAs; 2.062 -> 2.047 ms per step vs
                                            // one per 4; 6 = 3 with the V stream loaded non-temporally where every GEMM workgroup of the call has a CU
@@ -112,30 +151,7 @@ struct eamm_ctx : eamm::CtxBase {
 
     double flops_frame = 0, flops_encode = 0;
 
-    // optional stage timing with HIP events on the caller's stream (bench.py roofline leg)
-    static constexpr int NSTAGE = 22;      // front, hg_enc, hg_dec, head, warp, bneck_transform, bneck_conv, up, final + bneck_gemm_kernel
-                                           // + bneck_union_ms (wall time during which ANY chain is in its bottleneck stage), bneck_windows_ms (sum of
-                                           // the chains' bottleneck windows), exec_gflop / bneck_exec_gflop (executed MFMA GFLOP of the recorded
-                                           // calls, all chains: whole pass / bottleneck GEMMs) + 14..21 executed MFMA GFLOP of each of the eight
-                                           // recorded stage intervals (front, hg_enc, hg_dec, head, warp, bottleneck, up, final), all chains
-    static constexpr int MAXCHAIN = 4;     // chains whose bottleneck window is recorded per call
-    static constexpr int NMARK = 8;        // stage boundaries recorded per call (bottleneck is split from sub-events)
-    static constexpr int NSUB = 64;        // per-launch events inside the bottleneck (4 per res-block + 1)
-    static constexpr int PROF_CALLS = 256; // event sets kept before the host must read them
-    bool profiling = false;
-    std::vector<hipEvent_t> prof_events;   // PROF_CALLS * (NMARK+1 + NSUB)
-    std::vector<hipEvent_t> prof_chain_ev; // PROF_CALLS * MAXCHAIN * 2: start / end of each whole-pass chain's bottleneck stage
-    std::vector<int> prof_nchain;          // chains recorded by each call
-    std::vector<double> prof_flops, prof_flops_bneck;   // executed MFMA flops of each recorded call
-    double call_flops = 0, call_flops_bneck = 0;         // ... of the call being enqueued
-    double call_stage_flops[8] = {0};                    // ... per stage interval (all chains)
-    std::vector<double> prof_stage_flops;                // PROF_CALLS * NMARK
-    std::vector<int> prof_sub;             // sub-events used by each recorded call (0: direct form)
-    std::vector<int> prof_marks;           // stage marks each recorded call completed (NMARK + 1 unless it failed midway)
-    int prof_used = 0;
-    double prof_ms[NSTAGE] = {0};
-    long prof_calls = 0, prof_frames = 0;
-    std::vector<int> prof_n;
+    PassProfile prof;
 
     // ---- training-mode forward (eamm_train_api.hip; SURVEY.md 8f row N4, second slice) ---------------------------------
     bool train_mode = false;               // eamm_set_training before finalisation: convolutions packed WITHOUT BatchNorm folded in
@@ -183,6 +199,42 @@ inline ConvIO conv_io(const float* in0, int B, int Hin, int Win, int act, float*
     return io;
 }
 
+// The F(4x4) kernels address V ([36][tiles][Cin]) and Z ([24][tiles][Cout]) through 32-bit buffer descriptors
+// (wino4_gemm_launch refuses from 0xFFFFF000 bytes): a call with more tiles than this takes the direct kernels.
+inline bool wino4_fits(size_t tiles, int cin, int cout) {
+    return 36.0 * tiles * cin * 4.0 < 4294963200.0 && 24.0 * tiles * cout * 4.0 < 4294963200.0;
+}
+
+// The slice of the per-frame workspace one launch sequence works on: frames [f0, f0 + n) of a call (every per-frame
+// buffer is frame-major, so a slice is a pointer offset) with its own split-K slab and Winograd buffers.
+struct FrameView {
+    int n = 0, ns = 1;
+    const float *kd_val = nullptr, *kd_jac = nullptr, *ks_val = nullptr, *ks_jac = nullptr;
+    const float *feat = nullptr, *src_small = nullptr, *src_full = nullptr;
+    float *kp_rec = nullptr, *hg_in = nullptr, *logits = nullptr, *deformation = nullptr, *occlusion = nullptr;
+    float *xa = nullptr, *xb = nullptr, *act = nullptr, *tmp = nullptr, *final_part = nullptr;
+    std::vector<float*> e_buf, u_buf, up_buf;
+    float* partial = nullptr;
+    size_t partial_elems = 0;
+    float *wino_v = nullptr, *wino_z = nullptr;
+    eamm_outputs out{};
+};
+
+// ---- defined in eamm_forward.hip for the other translation units ---------------------------------------------------------
 // Side stream k of `device` from the pool every handle of the process shares (created on first use, never destroyed; null on
-// failure).  One definition, in eamm_forward.hip beside StreamLease, which leases the pool per call.
+// failure); StreamLease leases the pool per call.
 hipStream_t chain_stream(int device, int k);
+// The view of frames [f0, f0 + n) of a call whose sources number ns_call (1, or one per frame), on split-K slab `slab`
+FrameView make_view(const eamm_ctx* c, int f0, int n, int ns_call, int slab, const float* kd_val, const float* kd_jac,
+                    const float* ks_val, const float* ks_jac, const eamm_outputs* o);
+// The stages of the per-frame pass without a BatchNorm site inside: eamm_train_begin runs these same launch sequences between
+// its own convolution / BatchNorm sites.  Each enqueues on s and returns an EAMM_* code.
+int stage_motion_front(eamm_ctx* c, const FrameView& v, hipStream_t s);        // kp_prepare + motion_front
+int stage_flow_head(eamm_ctx* c, const FrameView& v, hipStream_t s);           // 7x7 head conv + softmax / flow / sigmoid
+int stage_warp(eamm_ctx* c, const FrameView& v, hipStream_t s, bool pre_act);  // features (+ r0's pre-activation) and 'deformed'
+int stage_final(eamm_ctx* c, const FrameView& v, hipStream_t s);               // final 7x7 + sigmoid (+ uint8 frames)
+// A pooled DownBlock2d level in F(4x4,3x3) form: whether it pays, by the caller's own rule, and its launches
+enum class Wino4Pooled { HOURGLASS, SOURCE };
+bool wino4_pooled_pays(const eamm_ctx* c, const WinoLayer& L, int tiles, Wino4Pooled caller);
+int launch_wino4_pooled(eamm_ctx* c, const WinoLayer& L, const float* in, int n, int Hin, int Win, float* out, float* vbuf,
+                        float* zbuf, hipStream_t s);

@@ -2,8 +2,9 @@
 // include/eamm_hip.h:
 //   eamm_forward_frames -- per frame batch: key-point records, motion front end, hourglass, flow head,
 //                          feature warp, bottleneck, up blocks, final 7x7 + sigmoid
-// with the rules that pick each stage's launch form for a call of n frames (ONE function per rule: the launch sequence and
-// eamm_describe_plan both call it), the chains' stream pool, and the stage profile, whose layout is forward_view's.
+// In this order: the chains' stream pool and make_view; the rules that pick each stage's launch form for a call of n frames (ONE
+// function per rule: the launch sequence and eamm_describe_plan both call it); ONE function per stage (eamm_ctx.h declares those
+// that eamm_train_begin and eamm_encode_source share); forward_view, the sequence of stage marks and stage calls; PassProfile.
 #include "eamm_ctx.h"
 #include <mutex>
 
@@ -28,6 +29,52 @@ hipStream_t chain_stream(int device, int k) {   // (declared in eamm_ctx.h: eamm
     std::lock_guard<std::mutex> lock(g_pool_mu);
     if (!g_pool[device][k] && hipStreamCreateWithFlags(&g_pool[device][k], hipStreamNonBlocking) != hipSuccess) g_pool[device][k] = nullptr;
     return g_pool[device][k];
+}
+
+FrameView make_view(const eamm_ctx* c, int f0, int n, int ns_call, int slab, const float* kd_val, const float* kd_jac,
+                    const float* ks_val, const float* ks_jac, const eamm_outputs* o) {   // (FrameView: eamm_ctx.h)
+    FrameView v;
+    const size_t F = (size_t)f0, K = c->K;
+    const size_t HW = (size_t)c->H * c->W, hw = (size_t)c->h * c->w, hwf = (size_t)c->hf * c->wf;
+    const size_t sf = ns_call > 1 ? F : 0;   // per-frame sources (the module's batch contract) move with the frames
+    v.n = n;
+    v.ns = ns_call > 1 ? n : 1;
+    v.kd_val = kd_val + F * K * 2;
+    v.kd_jac = kd_jac ? kd_jac + F * K * 4 : nullptr;
+    v.ks_val = ks_val + sf * K * 2;
+    v.ks_jac = ks_jac ? ks_jac + sf * K * 4 : nullptr;
+    v.feat = c->feat + sf * hwf * c->Cb;
+    v.src_small = c->src_small + sf * hw * 4;
+    v.src_full = c->src_full + sf * c->Cpl * HW;
+    v.kp_rec = c->kp_rec + F * K * KP_STRIDE;
+    v.hg_in = c->hg_in ? c->hg_in + F * hw * c->Cp0 : nullptr;            // (no motion network: these four do not exist)
+    for (int i = 0; i < c->nb; ++i) {
+        v.e_buf.push_back(c->e_buf[i] + F * (hw >> (2 * (i + 1))) * c->enc_c[i]);
+        v.u_buf.push_back(c->u_buf[i] + F * (hw >> (2 * (c->nb - 1 - i))) * c->dec_c[i]);
+    }
+    v.logits = c->logits ? c->logits + F * hw * (c->head_nc ? 128 : 32) : nullptr;
+    v.deformation = c->deformation ? c->deformation + F * hw * 2 : nullptr;
+    v.occlusion = c->occlusion ? c->occlusion + F * hw : nullptr;
+    v.xa = c->xa + F * hwf * c->Cb;
+    v.xb = c->xb + F * hwf * c->Cb;
+    v.act = c->act + F * hwf * c->Cb;
+    v.tmp = c->tmp + F * hwf * c->Cb;
+    for (int i = 0; i < c->nd; ++i) v.up_buf.push_back(c->up_buf[i] + F * (hwf << (2 * (i + 1))) * c->up_c[i]);
+    v.final_part = c->final_part + F * HW * 32;
+    v.partial = c->partial + (size_t)slab * c->partial_elems;
+    v.partial_elems = c->partial_elems;
+    v.wino_v = c->wino_v ? c->wino_v + 4 * F * hwf * c->Cb : nullptr;                  // sized 4 x activations per frame
+    v.wino_z = c->wino_z ? c->wino_z + 24 * (F * hwf / 16) * c->Cb : nullptr;
+    v.out = *o;
+    const size_t CO = c->Cimg > 3 ? c->Cimg : 3;   // channels of the tensors the pass writes (staging tensors for one or two)
+    if (o->prediction) v.out.prediction = o->prediction + F * CO * HW;
+    if (o->mask) v.out.mask = o->mask + F * (K + 1) * hw;
+    if (o->sparse_deformed) v.out.sparse_deformed = o->sparse_deformed + F * (K + 1) * CO * hw;
+    if (o->occlusion_map) v.out.occlusion_map = o->occlusion_map + F * hw;
+    if (o->deformed) v.out.deformed = o->deformed + F * CO * HW;
+    if (o->deformation) v.out.deformation = o->deformation + F * hw * 2;
+    if (o->frames_u8) v.out.frames_u8 = o->frames_u8 + F * HW * 3;
+    return v;
 }
 
 namespace {
@@ -100,67 +147,6 @@ int bottleneck_chains(const eamm_ctx* c, int n) {
     return chains;
 }
 
-// The slice of the per-frame workspace one launch sequence works on: frames [f0, f0 + n) of a call (every per-frame
-// buffer is frame-major, so a slice is a pointer offset) with its own split-K slab and Winograd buffers.
-struct FrameView {
-    int n = 0, ns = 1;
-    const float *kd_val = nullptr, *kd_jac = nullptr, *ks_val = nullptr, *ks_jac = nullptr;
-    const float *feat = nullptr, *src_small = nullptr, *src_full = nullptr;
-    float *kp_rec = nullptr, *hg_in = nullptr, *logits = nullptr, *deformation = nullptr, *occlusion = nullptr;
-    float *xa = nullptr, *xb = nullptr, *act = nullptr, *tmp = nullptr, *final_part = nullptr;
-    std::vector<float*> e_buf, u_buf, up_buf;
-    float* partial = nullptr;
-    size_t partial_elems = 0;
-    float *wino_v = nullptr, *wino_z = nullptr;
-    eamm_outputs out{};
-};
-
-FrameView make_view(const eamm_ctx* c, int f0, int n, int ns_call, int slab, const float* kd_val, const float* kd_jac,
-                           const float* ks_val, const float* ks_jac, const eamm_outputs* o) {
-    FrameView v;
-    const size_t F = (size_t)f0, K = c->K;
-    const size_t HW = (size_t)c->H * c->W, hw = (size_t)c->h * c->w, hwf = (size_t)c->hf * c->wf;
-    const size_t sf = ns_call > 1 ? F : 0;   // per-frame sources (the module's batch contract) move with the frames
-    v.n = n;
-    v.ns = ns_call > 1 ? n : 1;
-    v.kd_val = kd_val + F * K * 2;
-    v.kd_jac = kd_jac ? kd_jac + F * K * 4 : nullptr;
-    v.ks_val = ks_val + sf * K * 2;
-    v.ks_jac = ks_jac ? ks_jac + sf * K * 4 : nullptr;
-    v.feat = c->feat + sf * hwf * c->Cb;
-    v.src_small = c->src_small + sf * hw * 4;
-    v.src_full = c->src_full + sf * c->Cpl * HW;
-    v.kp_rec = c->kp_rec + F * K * KP_STRIDE;
-    v.hg_in = c->hg_in ? c->hg_in + F * hw * c->Cp0 : nullptr;            // (no motion network: these four do not exist)
-    for (int i = 0; i < c->nb; ++i) {
-        v.e_buf.push_back(c->e_buf[i] + F * (hw >> (2 * (i + 1))) * c->enc_c[i]);
-        v.u_buf.push_back(c->u_buf[i] + F * (hw >> (2 * (c->nb - 1 - i))) * c->dec_c[i]);
-    }
-    v.logits = c->logits ? c->logits + F * hw * (c->head_nc ? 128 : 32) : nullptr;
-    v.deformation = c->deformation ? c->deformation + F * hw * 2 : nullptr;
-    v.occlusion = c->occlusion ? c->occlusion + F * hw : nullptr;
-    v.xa = c->xa + F * hwf * c->Cb;
-    v.xb = c->xb + F * hwf * c->Cb;
-    v.act = c->act + F * hwf * c->Cb;
-    v.tmp = c->tmp + F * hwf * c->Cb;
-    for (int i = 0; i < c->nd; ++i) v.up_buf.push_back(c->up_buf[i] + F * (hwf << (2 * (i + 1))) * c->up_c[i]);
-    v.final_part = c->final_part + F * HW * 32;
-    v.partial = c->partial + (size_t)slab * c->partial_elems;
-    v.partial_elems = c->partial_elems;
-    v.wino_v = c->wino_v ? c->wino_v + 4 * F * hwf * c->Cb : nullptr;                  // sized 4 x activations per frame
-    v.wino_z = c->wino_z ? c->wino_z + 24 * (F * hwf / 16) * c->Cb : nullptr;
-    v.out = *o;
-    const size_t CO = c->Cimg > 3 ? c->Cimg : 3;   // channels of the tensors the pass writes (staging tensors for one or two)
-    if (o->prediction) v.out.prediction = o->prediction + F * CO * HW;
-    if (o->mask) v.out.mask = o->mask + F * (K + 1) * hw;
-    if (o->sparse_deformed) v.out.sparse_deformed = o->sparse_deformed + F * (K + 1) * CO * hw;
-    if (o->occlusion_map) v.out.occlusion_map = o->occlusion_map + F * hw;
-    if (o->deformed) v.out.deformed = o->deformed + F * CO * HW;
-    if (o->deformation) v.out.deformation = o->deformation + F * hw * 2;
-    if (o->frames_u8) v.out.frames_u8 = o->frames_u8 + F * HW * 3;
-    return v;
-}
-
 // Chains over the WHOLE per-frame pass: the frames of a call are independent, so a call of n frames can run as K launch
 // sequences of n/K frames on K streams.  The sequences drift apart (the host enqueues them one after the other), and the
 // chip then runs one chain's HBM- or latency-bound kernels (input transforms, warps, the small-grid deep hourglass levels
@@ -189,16 +175,10 @@ int pass_chains(const eamm_ctx* c, int n) {
     return fits(2) ? 2 : 1;
 }
 
-// Whether hourglass encoder level i runs in F(4x4,3x3) form (input transform, point-row-split GEMM, pooled output transform)
-// in a launch sequence of n frames: the level was packed (eamm_finalize_weights), has enough 4x4 tiles -- four times as many
-// where its transformed weights exceed ~100 MB (the 4x4-map level: 151 MB) -- and enough direct-form MFLOP (2 * 9 * 16 pixels
-// per tile); smaller levels are launch-bound and one launch beats three
+// Whether hourglass encoder level i runs in F(4x4,3x3) form in a launch sequence of n frames (wino4_pooled_pays below)
 bool enc_level_wino4(const eamm_ctx* c, int i, int n) {
-    if (i >= (int)c->w4enc.size() || !c->w4enc[i].Cout) return false;
-    const WinoLayer& L = c->w4enc[i];
-    const int tiles = n * ((c->h >> i) / 4) * ((c->w >> i) / 4);
-    const bool heavy = 144.0 * L.Cin * L.Cout > 100e6;
-    return tiles >= c->enc_wino_min_tiles * (heavy ? 4 : 1) && 288e-6 * tiles * L.Cin * L.Cout >= (double)c->enc_wino_min_mflop;
+    if (i >= (int)c->w4enc.size()) return false;
+    return wino4_pooled_pays(c, c->w4enc[i], n * ((c->h >> i) / 4) * ((c->w >> i) / 4), Wino4Pooled::HOURGLASS);
 }
 
 // Whether the final layer of a launch sequence of n frames takes the fused column-patch form (gather of the seven horizontal
@@ -209,211 +189,198 @@ bool final_is_fused(const eamm_ctx* c, int n) {
     return c->final_w_swz && c->final_conv.BN == 32 && c->final_fused && n * ((c->H + 15) / 16) >= c->final_fused_min_rows;
 }
 
-// One launch sequence over the frames of `v` on stream s.  `chained`: another sequence runs beside this one.
-// phase: the whole pass, or its two halves around the feature warp (PH_PRE: key points ... flow head; PH_POST: warp ... final
-// layer).  With `joint` (first chain's PH_POST) the warps run ONCE for all the call's frames -- the view `joint` -- and the
-// other chains' PH_POST skip them and start behind c->ev_warp.
-enum { PH_ALL = 0, PH_PRE = 1, PH_POST = 2 };
-int forward_view(eamm_ctx* c, const FrameView& v, hipStream_t s, hipEvent_t* ev, bool chained, hipEvent_t* cev = nullptr,
-                 int phase = PH_ALL, const FrameView* joint = nullptr) {
-    const int n = v.n, ns = v.ns;
-    const int h = c->h, w = c->w, hf = c->hf, wf = c->wf, K = c->K;
-    const bool occ = c->cfg.estimate_occlusion_map != 0;
-    // a convolution of this view's n frames at Hin x Win, on the view's split-K slab
-    auto conv_for = [&](const float* in0, int Hin, int Win, int act, float* out) {
-        return conv_io(in0, n, Hin, Win, act, out, v.partial, v.partial_elems);
-    };
-    // executed matrix-core flops launched since the last mark belong to the stage interval that ends here
-    auto account = [&](int interval) {
-        const double f = take_mfma_flops();
-        c->call_flops += f;
-        c->call_stage_flops[interval] += f;
-        if (interval == 5) c->call_flops_bneck += f;
-    };
-#define STAGE_MARK(i)                                  \
-    do {                                               \
-        if ((i) > 0) account((i) - 1);                 \
-        if (ev) {                                      \
-            HIP_TRY(c, hipEventRecord(ev[i], s));      \
-            c->prof_marks.back() = (i) + 1;            \
-        }                                              \
-    } while (0)
-    const int nr = c->cfg.num_bottleneck_blocks;
-    const int form = bottleneck_form(c, n);
-    const bool wino = form != 0;
-    if (c->nb == 0) {   // no motion network (generator.py:64 is false): the encoder features enter the bottleneck as they are
-        STAGE_MARK(0); STAGE_MARK(1); STAGE_MARK(2); STAGE_MARK(3); STAGE_MARK(4);
-        HIP_TRY(c, broadcast_features_launch(v.feat, n, ns, hf, wf, c->Cb, v.xa, wino ? nullptr : v.act, c->pre_s[0], c->pre_t[0], s));
-        STAGE_MARK(5);
-    } else {
-    if (phase != PH_POST) {
-    STAGE_MARK(0);
+// a convolution of the view's n frames at Hin x Win, on the view's split-K slab
+ConvIO conv_for(const FrameView& v, const float* in0, int Hin, int Win, int act, float* out) {
+    return conv_io(in0, v.n, Hin, Win, act, out, v.partial, v.partial_elems);
+}
+
+}  // namespace
+
+// ---- the stages: each enqueues one stage of the pass for the frames of `v` on stream s ----------------------------------
+// Whether a pooled DownBlock2d level runs in F(4x4,3x3) form (input transform, point-row-split GEMM, pooled output transform)
+// for a launch of `tiles` 4x4 tiles: the level was packed (eamm_finalize_weights), has enough tiles and enough direct-form
+// MFLOP (2 * 9 * 16 pixels per tile); smaller levels are launch-bound and one launch beats three.  The two callers' rules
+// differ and stay apart on purpose (unifying them would change which kernel runs for widths beyond the shipped ones): HOURGLASS
+// asks four times the tiles where the transformed weights exceed ~100 MB (the 4x4-map level: 151 MB); SOURCE borrows
+// workspaces sized for the frames, so they must exist and the tiles must fit their 32-bit descriptors (wino4_fits).
+bool wino4_pooled_pays(const eamm_ctx* c, const WinoLayer& L, int tiles, Wino4Pooled caller) {
+    if (!L.Cout) return false;
+    const int min_tiles = c->enc_wino_min_tiles * (caller == Wino4Pooled::HOURGLASS && 144.0 * L.Cin * L.Cout > 100e6 ? 4 : 1);
+    if (caller == Wino4Pooled::SOURCE && !(c->wino_v && c->wino_z && wino4_fits((size_t)tiles, L.Cin, L.Cout))) return false;
+    return tiles >= min_tiles && 288e-6 * tiles * L.Cin * L.Cout >= (double)c->enc_wino_min_mflop;
+}
+
+int launch_wino4_pooled(eamm_ctx* c, const WinoLayer& L, const float* in, int n, int Hin, int Win, float* out, float* vbuf,
+                        float* zbuf, hipStream_t s) {
+    // F(4x4,3x3): 4x fewer MACs; the transform-point rows are split over workgroups (>= 2: the pooled epilogue is the
+    // output-transform kernel's)
+    const int g = wino4_row_split(c, n * (Hin / 4) * (Win / 4), L.ntiles, true);
+    HIP_TRY(c, wino4_transform_launch(in, nullptr, nullptr, n, Hin, Win, L.Cin, vbuf, s));
+    // pipeline variant 0 (one DMA piece per 4 MFMAs): within noise of the bottleneck's variant at these sizes, and a
+    // different instantiation -- per-kernel averages in traces / PMC passes stay those of the bottleneck launches alone
+    HIP_TRY(c, wino4_gemm_launch(L, vbuf, n, Hin, Win, ACT_RELU, nullptr, out, s, 0, g, zbuf, 1));
+    return EAMM_OK;
+}
+
+int stage_motion_front(eamm_ctx* c, const FrameView& v, hipStream_t s) {
     // key-point records; 'jacobian' missing from kp_driving => identity (dense_motion.py:55)
-    HIP_TRY(c, kp_prepare_launch(v.kd_val, v.kd_jac, v.ks_val, v.kd_jac ? v.ks_jac : nullptr, n, ns, K, v.kp_rec, c->bad_flag, s));
+    HIP_TRY(c, kp_prepare_launch(v.kd_val, v.kd_jac, v.ks_val, v.kd_jac ? v.ks_jac : nullptr, v.n, v.ns, c->K, v.kp_rec, c->bad_flag, s));
     // heat-maps + sparse motions + K+1 warped sources -> hourglass input     dense_motion.py:88-94
-    HIP_TRY(c, motion_front_launch(v.kp_rec, v.src_small, n, ns, K, h, w, c->cfg.kp_variance, c->Cp0, v.hg_in,
-                                   v.out.sparse_deformed, s, c->G, c->Cimg > 3 ? c->Cimg : 3, (size_t)c->cfg.max_sources * h * w * 4));
-    STAGE_MARK(1);
-    // hourglass encoder                                                       util.py:956-960
+    HIP_TRY(c, motion_front_launch(v.kp_rec, v.src_small, v.n, v.ns, c->K, c->h, c->w, c->cfg.kp_variance, c->Cp0, v.hg_in,
+                                   v.out.sparse_deformed, s, c->G, c->Cimg > 3 ? c->Cimg : 3, (size_t)c->cfg.max_sources * c->h * c->w * 4));
+    return EAMM_OK;
+}
+
+static int stage_hg_encoder(eamm_ctx* c, const FrameView& v, hipStream_t s) {   // util.py:956-960
     for (int i = 0; i < c->nb; ++i) {
-        ConvIO io = conv_for(i == 0 ? v.hg_in : v.e_buf[i - 1], h >> i, w >> i, ACT_RELU, v.e_buf[i]);
+        ConvIO io = conv_for(v, i == 0 ? v.hg_in : v.e_buf[i - 1], c->h >> i, c->w >> i, ACT_RELU, v.e_buf[i]);
         io.pool = 1;
-        if (enc_level_wino4(c, i, n)) {
-            // F(4x4,3x3): 4x fewer MACs; the transform-point rows are split over workgroups (>= 2: the pooled epilogue is
-            // the output-transform kernel's)
-            const WinoLayer& L = c->w4enc[i];
-            const int g = wino4_row_split(c, n * (io.Hin / 4) * (io.Win / 4), L.ntiles, true);
-            HIP_TRY(c, wino4_transform_launch(io.in0, nullptr, nullptr, n, io.Hin, io.Win, L.Cin, v.wino_v, s));
-            // pipeline variant 0 (one DMA piece per 4 MFMAs): within noise of the bottleneck's variant at these sizes, and a
-            // different instantiation -- per-kernel averages in traces / PMC passes stay those of the bottleneck launches alone
-            HIP_TRY(c, wino4_gemm_launch(L, v.wino_v, n, io.Hin, io.Win, ACT_RELU, nullptr, io.out, s, 0, g, v.wino_z, 1));
+        if (enc_level_wino4(c, i, v.n)) {
+            if (int rc = launch_wino4_pooled(c, c->w4enc[i], io.in0, v.n, io.Hin, io.Win, io.out, v.wino_v, v.wino_z, s)) return rc;
             continue;
         }
-        HIP_TRY(c, conv_launch(pick(c, c->hg_enc[i], (size_t)n * io.Hin * io.Win), io, s));
+        HIP_TRY(c, conv_launch(pick(c, c->hg_enc[i], (size_t)v.n * io.Hin * io.Win), io, s));
     }
-    STAGE_MARK(2);
-    // hourglass decoder: nearest x2 and the skip concatenation are folded into the operand loader
-    for (int i = 0; i < c->nb; ++i) {
-        ConvIO io = conv_for(i == 0 ? v.e_buf[c->nb - 1] : v.u_buf[i - 1], h >> (c->nb - i), w >> (c->nb - i), ACT_RELU, v.u_buf[i]);
-        io.in1 = i == 0 ? nullptr : v.e_buf[c->nb - 1 - i];
-        if (int urc = launch_up(c, c->hg_dec[i], io, s)) return urc;
+    return EAMM_OK;
+}
+
+// nearest x2 and the skip concatenation are folded into the operand loader
+static int stage_hg_decoder(eamm_ctx* c, const FrameView& v, hipStream_t s) {
+    const int nb = c->nb;
+    for (int i = 0; i < nb; ++i) {
+        ConvIO io = conv_for(v, i == 0 ? v.e_buf[nb - 1] : v.u_buf[i - 1], c->h >> (nb - i), c->w >> (nb - i), ACT_RELU, v.u_buf[i]);
+        io.in1 = i == 0 ? nullptr : v.e_buf[nb - 1 - i];
+        if (int rc = launch_up(c, c->hg_dec[i], io, s)) return rc;
     }
-    STAGE_MARK(3);
-    // mask / occlusion logits, then softmax + flow combine + sigmoid         dense_motion.py:98-111
-    {
-        ConvIO io = conv_for(v.u_buf[c->nb - 1], h, w, ACT_NONE, v.logits);
-        io.in1 = v.hg_in;
-        ConvLayer head = c->head;
-        float* defo = v.deformation;
-        if (c->head_nc) {
-            head.Cout = 128;  // partial products written with a 128-float pixel stride (7*nc used)
-            // the column-patch kernel runs one workgroup per 16x16-pixel tile: below ~half a chip of tiles (4 frames at
-            // 64x64) the split-K im2col kernel is faster (measured: 1 frame 0.122 -> 0.073 ms, 4 frames 0.122 -> 0.094 ms)
-            const int head_tiles = n * ((h + 15) / 16) * ((w + 15) / 16);
-            if (c->head_w_swz && head_tiles >= c->head_col7_min_tiles)
-                HIP_TRY(c, conv_col7s_launch(io.in0, head.C0, io.in1, head.C1, n, h, w, c->head_w_swz, 3, v.logits, 128, s));
-            else
-                HIP_TRY(c, conv_launch(head, io, s));
-            HIP_TRY(c, motion_head_rowsplit_launch(v.logits, 128, c->head_nc, c->head_bias, v.kp_rec, n, K, h, w,
-                                                   occ ? 1 : 0, defo, v.occlusion, v.out.mask, v.out.occlusion_map, s));
-        } else {
-            head.Cout = 32;  // logits are written with a 32-float pixel stride; channels >= K+2 have zero weights
+    return EAMM_OK;
+}
+
+// mask / occlusion logits, then softmax + flow combine + sigmoid         dense_motion.py:98-111
+int stage_flow_head(eamm_ctx* c, const FrameView& v, hipStream_t s) {
+    const int n = v.n, h = c->h, w = c->w, K = c->K;
+    const int occ = c->cfg.estimate_occlusion_map ? 1 : 0;
+    ConvIO io = conv_for(v, v.u_buf[c->nb - 1], h, w, ACT_NONE, v.logits);
+    io.in1 = v.hg_in;
+    ConvLayer head = c->head;
+    if (c->head_nc) {
+        head.Cout = 128;  // partial products written with a 128-float pixel stride (7*nc used)
+        // the column-patch kernel runs one workgroup per 16x16-pixel tile: below ~half a chip of tiles (4 frames at
+        // 64x64) the split-K im2col kernel is faster (measured: 1 frame 0.122 -> 0.073 ms, 4 frames 0.122 -> 0.094 ms)
+        const int head_tiles = n * ((h + 15) / 16) * ((w + 15) / 16);
+        if (c->head_w_swz && head_tiles >= c->head_col7_min_tiles)
+            HIP_TRY(c, conv_col7s_launch(io.in0, head.C0, io.in1, head.C1, n, h, w, c->head_w_swz, 3, v.logits, 128, s));
+        else
             HIP_TRY(c, conv_launch(head, io, s));
-            HIP_TRY(c, motion_head_launch(v.logits, v.kp_rec, n, K, h, w, occ ? 1 : 0, defo, v.occlusion, v.out.mask,
-                                          v.out.occlusion_map, s));
-        }
-        if (v.out.deformation)
-            HIP_TRY(c, hipMemcpyAsync(v.out.deformation, defo, (size_t)n * h * w * 2 * sizeof(float),
-                                      hipMemcpyDeviceToDevice, s));
-    }
-    }   // phase != PH_POST
-    if (phase == PH_PRE) {
-        account(3);
-        return EAMM_OK;
-    }
-    if (phase == PH_POST && joint == nullptr) {
-        HIP_TRY(c, hipStreamWaitEvent(s, c->ev_warp, 0));    // the first chain's launch warped this chain's frames as well
+        HIP_TRY(c, motion_head_rowsplit_launch(v.logits, 128, c->head_nc, c->head_bias, v.kp_rec, n, K, h, w, occ, v.deformation,
+                                               v.occlusion, v.out.mask, v.out.occlusion_map, s));
     } else {
-        if (phase == PH_POST)   // every chain's flow is ready (the caller made this stream wait for the others' PH_PRE)
-            for (size_t k = 0; k < c->ev_join.size(); ++k) HIP_TRY(c, hipStreamWaitEvent(s, c->ev_join[k], 0));
-        STAGE_MARK(4);
-        // feature warp x occlusion (+ r0's pre-activation for the direct form)       generator.py:79-84
-        const FrameView& wv = joint ? *joint : v;
-        HIP_TRY(c, warp_features_launch(wv.feat, wv.deformation, occ ? wv.occlusion : nullptr, wv.n, wv.ns, hf, wf, c->Cb, h, w,
-                                        wv.xa, wino ? nullptr : wv.act, c->pre_s[0], c->pre_t[0], s));
-        if (wv.out.deformed)                                                        // generator.py:86
-            HIP_TRY(c, warp_image_launch(wv.src_full, wv.deformation, wv.n, wv.ns, c->H, c->W, h, w, wv.out.deformed, s, c->Cpl,
-                                         c->Cimg > 3 ? c->Cimg : 3));
-        if (joint) HIP_TRY(c, hipEventRecord(c->ev_warp, s));
-        STAGE_MARK(5);
+        head.Cout = 32;  // logits are written with a 32-float pixel stride; channels >= K+2 have zero weights
+        HIP_TRY(c, conv_launch(head, io, s));
+        HIP_TRY(c, motion_head_launch(v.logits, v.kp_rec, n, K, h, w, occ, v.deformation, v.occlusion, v.out.mask,
+                                      v.out.occlusion_map, s));
     }
-    }
-    // bottleneck                                                               generator.py:89
-    float *x = v.xa, *xn = v.xb;
-    if (cev) HIP_TRY(c, hipEventRecord(cev[0], s));
-    hipEvent_t* sub = (ev && wino && 4 * nr + 1 <= eamm_ctx::NSUB) ? ev + eamm_ctx::NMARK + 1 : nullptr;
-    int nsub = 0;
-#define SUB_MARK()                                               \
-    do {                                                         \
-        if (sub) HIP_TRY(c, hipEventRecord(sub[nsub++], s));     \
-    } while (0)
-    const bool wino4 = form == 4;
-    const int w4g = (wino4 && !chained) ? wino4_groups(c, n) : 1;   // a chained view shares the chip: never split the point rows
-    // (round 5: splitting a whole-pass chain's bottleneck once more -- 2 x 2 sub-chains of 4 frames -- was built and measured
-    //  neutral, 3917 vs 3958 frames/s: the input transform is latency-bound and does not shrink with the frames per launch;
-    //  profiles/r05_experiments.txt section 2, git 9500c6c)
+    if (v.out.deformation)
+        HIP_TRY(c, hipMemcpyAsync(v.out.deformation, v.deformation, (size_t)n * h * w * 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return EAMM_OK;
+}
+
+// feature warp x occlusion (generator.py:79-84) and 'deformed' (generator.py:86).  pre_act: also write r0's pre-activation
+// relu(norm1(.)) for the direct-form bottleneck (the Winograd forms apply it in their input transform; training runs norm1
+// as a BatchNorm site of its own)
+int stage_warp(eamm_ctx* c, const FrameView& v, hipStream_t s, bool pre_act) {
+    const bool occ = c->cfg.estimate_occlusion_map != 0;
+    HIP_TRY(c, warp_features_launch(v.feat, v.deformation, occ ? v.occlusion : nullptr, v.n, v.ns, c->hf, c->wf, c->Cb, c->h, c->w,
+                                    v.xa, pre_act ? v.act : nullptr, c->pre_s[0], c->pre_t[0], s));
+    if (v.out.deformed)
+        HIP_TRY(c, warp_image_launch(v.src_full, v.deformation, v.n, v.ns, c->H, c->W, c->h, c->w, v.out.deformed, s, c->Cpl,
+                                     c->Cimg > 3 ? c->Cimg : 3));
+    return EAMM_OK;
+}
+
+// ---- bottleneck (generator.py:89): three forms, one function each; the blocks ping-pong between xa and xb (stage_up).
+// `timed`: record the profile's per-launch sub-events -- before each of the four launches of a block on s, once after the last.
+
+// F(4x4,3x3), as `chains` groups of frames on as many streams (bottleneck_chains; a view of a whole-pass chain, `chained`, shares
+// the chip already and runs as one).  conv1(relu(norm1(x))): the pre-activation rides on the input transform; norm2 + relu in
+// the GEMM's epilogue; conv2's epilogue adds x.
+// (round 5: splitting a whole-pass chain's bottleneck once more -- 2 x 2 sub-chains of 4 frames -- was built and measured
+//  neutral, 3917 vs 3958 frames/s: the input transform is latency-bound and does not shrink with the frames per launch;
+//  profiles/r05_experiments.txt section 2, git 9500c6c)
+static int bottleneck_wino4(eamm_ctx* c, const FrameView& v, hipStream_t s, bool chained, bool timed) {
+    const int n = v.n, hf = c->hf, wf = c->wf, nr = c->cfg.num_bottleneck_blocks;
     const int chains = chained ? 1 : bottleneck_chains(c, n);
-    const int w4var = wino4_variant_for(c, chained ? c->cur_call_frames : n);
-    auto split_stream = [&](int k) { return c->side_streams[k - 1]; };
-    hipEvent_t split_fork = c->ev_fork;
-    auto split_join = [&](int k) { return c->ev_join[k - 1]; };
+    // one chain may split the point rows over workgroups, through Z (never a chained view; several chains only where the split is 1)
+    const int groups = chained ? 1 : wino4_groups(c, n);
+    // EAMM_WINO4_EPI_V (timing experiment, wrong results, experiments build): only the stage's FIRST transform runs (every GEMM
+    // then reads that V: realistic operand values), and the GEMMs' epilogues write V-sized extra output instead (variant 50)
+    const bool epi = c->epi_v && c->epi_scratch && chains == 1 && groups == 1;
+    float* zbuf = epi ? c->epi_scratch + (size_t)3 * (v.xa - c->xa) : chains > 1 ? nullptr : v.wino_z;
+    const int var = epi ? 50 : wino4_variant_for(c, chained ? c->cur_call_frames : n);
+    const size_t per_frame = (size_t)hf * wf * c->Cb;
+    const int nbase = n / chains, nrem = n % chains;   // the first nrem chains take one more frame
+    float *x = v.xa, *xn = v.xb;
     if (chains > 1) {
-        const size_t per_frame = (size_t)hf * wf * c->Cb;
-        const int nbase = n / chains, nrem = n % chains;   // the first nrem chains take one more frame
-        HIP_TRY(c, hipEventRecord(split_fork, s));
-        for (int k = 1; k < chains; ++k) HIP_TRY(c, hipStreamWaitEvent(split_stream(k), split_fork, 0));
-        for (int i = 0; i < nr; ++i) {
-            for (int k = 0; k < chains; ++k) {
-                hipStream_t sk = k ? split_stream(k) : s;
-                const int nk = nbase + (k < nrem ? 1 : 0);
-                const size_t f0 = (size_t)k * nbase + std::min(k, nrem);
-                float* xk = x + f0 * per_frame;
-                float* xnk = xn + f0 * per_frame;
-                float* tk = v.tmp + f0 * per_frame;
-                float* vk = v.wino_v + 4 * f0 * per_frame;   // 2.25 nk frames used of the 4 nk reserved for this chain
-                // events around the main stream's (chain 0's) kernels only: they time those launches while the other
-                // chains' run beside them
-                if (k == 0) SUB_MARK();
-                HIP_TRY(c, wino4_transform_launch(xk, c->pre_s[i], c->pre_t[i], nk, hf, wf, c->Cb, vk, sk));
-                if (k == 0) SUB_MARK();
-                HIP_TRY(c, wino4_gemm_launch(c->w4res1[i], vk, nk, hf, wf, ACT_RELU, nullptr, tk, sk, w4var, 1, nullptr));
-                if (k == 0) SUB_MARK();
-                HIP_TRY(c, wino4_transform_launch(tk, nullptr, nullptr, nk, hf, wf, c->Cb, vk, sk));
-                if (k == 0) SUB_MARK();
-                HIP_TRY(c, wino4_gemm_launch(c->w4res2[i], vk, nk, hf, wf, ACT_NONE, xk, xnk, sk, w4var, 1, nullptr));
-            }
-            std::swap(x, xn);
-        }
-        SUB_MARK();
-        for (int k = 1; k < chains; ++k) {
-            HIP_TRY(c, hipEventRecord(split_join(k), split_stream(k)));
-            HIP_TRY(c, hipStreamWaitEvent(s, split_join(k), 0));
-        }
+        HIP_TRY(c, hipEventRecord(c->ev_fork, s));
+        for (int k = 1; k < chains; ++k) HIP_TRY(c, hipStreamWaitEvent(c->side_streams[k - 1], c->ev_fork, 0));
     }
-    for (int i = 0; i < nr && wino && chains == 1; ++i) {
-        // conv1(relu(norm1(x))): the pre-activation rides on the input transform; norm2 + relu in the epilogue
-        SUB_MARK();
-        if (wino4) {
-            // EAMM_WINO4_EPI_V (timing experiment, wrong results): only the stage's FIRST transform runs (every GEMM then reads that
-            // V: realistic operand values), and the GEMMs' epilogues write V-sized extra output instead (variant 50)
-            const bool epi = c->epi_v && c->epi_scratch && w4g == 1;
-            float* escr = epi ? c->epi_scratch + (size_t)3 * (v.xa - c->xa) : v.wino_z;
-            const int wvar = epi ? 50 : w4var;
-            if (!epi || i == 0) HIP_TRY(c, wino4_transform_launch(x, c->pre_s[i], c->pre_t[i], n, hf, wf, c->Cb, v.wino_v, s));
-            SUB_MARK();
-            HIP_TRY(c, wino4_gemm_launch(c->w4res1[i], v.wino_v, n, hf, wf, ACT_RELU, nullptr, v.tmp, s, wvar, w4g, escr));
-            SUB_MARK();
-            if (!epi) HIP_TRY(c, wino4_transform_launch(v.tmp, nullptr, nullptr, n, hf, wf, c->Cb, v.wino_v, s));
-            SUB_MARK();
-            HIP_TRY(c, wino4_gemm_launch(c->w4res2[i], v.wino_v, n, hf, wf, ACT_NONE, x, xn, s, wvar, w4g, escr));   // out += x
-        } else {
-            HIP_TRY(c, wino_transform_launch(x, c->pre_s[i], c->pre_t[i], n, hf, wf, c->Cb, v.wino_v, s));
-            SUB_MARK();
-            HIP_TRY(c, wino_gemm_launch(c->wres1[i], v.wino_v, n, hf, wf, ACT_RELU, nullptr, v.tmp, s));
-            SUB_MARK();
-            HIP_TRY(c, wino_transform_launch(v.tmp, nullptr, nullptr, n, hf, wf, c->Cb, v.wino_v, s));
-            SUB_MARK();
-            HIP_TRY(c, wino_gemm_launch(c->wres2[i], v.wino_v, n, hf, wf, ACT_NONE, x, xn, s));   // out += x
+    for (int i = 0; i < nr; ++i) {
+        for (int k = 0; k < chains; ++k) {
+            hipStream_t sk = k ? c->side_streams[k - 1] : s;
+            const int nk = nbase + (k < nrem ? 1 : 0);
+            const size_t f0 = (size_t)k * nbase + std::min(k, nrem);
+            float* xk = x + f0 * per_frame;
+            float* xnk = xn + f0 * per_frame;
+            float* tk = v.tmp + f0 * per_frame;
+            float* vk = v.wino_v + 4 * f0 * per_frame;   // 2.25 nk frames used of the 4 nk reserved for this chain
+            // events around the main stream's (chain 0's) kernels only: they time those launches while the other
+            // chains' run beside them
+            const bool ev = timed && k == 0;
+            if (ev) HIP_TRY(c, c->prof.sub(s));
+            if (!epi || i == 0) HIP_TRY(c, wino4_transform_launch(xk, c->pre_s[i], c->pre_t[i], nk, hf, wf, c->Cb, vk, sk));
+            if (ev) HIP_TRY(c, c->prof.sub(s));
+            HIP_TRY(c, wino4_gemm_launch(c->w4res1[i], vk, nk, hf, wf, ACT_RELU, nullptr, tk, sk, var, groups, zbuf));
+            if (ev) HIP_TRY(c, c->prof.sub(s));
+            if (!epi) HIP_TRY(c, wino4_transform_launch(tk, nullptr, nullptr, nk, hf, wf, c->Cb, vk, sk));
+            if (ev) HIP_TRY(c, c->prof.sub(s));
+            HIP_TRY(c, wino4_gemm_launch(c->w4res2[i], vk, nk, hf, wf, ACT_NONE, xk, xnk, sk, var, groups, zbuf));   // out += x
         }
         std::swap(x, xn);
     }
-    if (chains == 1) SUB_MARK();
-#undef SUB_MARK
-    if (sub) c->prof_sub.back() = nsub;
-    for (int i = 0; i < nr && !wino; ++i) {
-        const ConvIO a = conv_for(v.act, hf, wf, ACT_RELU, v.tmp);  // conv1 -> norm2 (folded) -> relu
+    if (timed) HIP_TRY(c, c->prof.sub(s));
+    for (int k = 1; k < chains; ++k) {
+        HIP_TRY(c, hipEventRecord(c->ev_join[k - 1], c->side_streams[k - 1]));
+        HIP_TRY(c, hipStreamWaitEvent(s, c->ev_join[k - 1], 0));
+    }
+    return EAMM_OK;
+}
+
+// F(2x2,3x3): the same four launches per block, with the F(2x2) kernels
+static int bottleneck_wino2(eamm_ctx* c, const FrameView& v, hipStream_t s, bool timed) {
+    const int n = v.n, hf = c->hf, wf = c->wf, nr = c->cfg.num_bottleneck_blocks;
+    float *x = v.xa, *xn = v.xb;
+    for (int i = 0; i < nr; ++i) {
+        if (timed) HIP_TRY(c, c->prof.sub(s));
+        HIP_TRY(c, wino_transform_launch(x, c->pre_s[i], c->pre_t[i], n, hf, wf, c->Cb, v.wino_v, s));
+        if (timed) HIP_TRY(c, c->prof.sub(s));
+        HIP_TRY(c, wino_gemm_launch(c->wres1[i], v.wino_v, n, hf, wf, ACT_RELU, nullptr, v.tmp, s));
+        if (timed) HIP_TRY(c, c->prof.sub(s));
+        HIP_TRY(c, wino_transform_launch(v.tmp, nullptr, nullptr, n, hf, wf, c->Cb, v.wino_v, s));
+        if (timed) HIP_TRY(c, c->prof.sub(s));
+        HIP_TRY(c, wino_gemm_launch(c->wres2[i], v.wino_v, n, hf, wf, ACT_NONE, x, xn, s));   // out += x
+        std::swap(x, xn);
+    }
+    if (timed) HIP_TRY(c, c->prof.sub(s));
+    return EAMM_OK;
+}
+
+// direct form: the block's input arrives pre-activated in v.act (the warp's, then conv2's, second output)
+static int bottleneck_direct(eamm_ctx* c, const FrameView& v, hipStream_t s) {
+    const int n = v.n, hf = c->hf, wf = c->wf, nr = c->cfg.num_bottleneck_blocks;
+    float *x = v.xa, *xn = v.xb;
+    for (int i = 0; i < nr; ++i) {
+        const ConvIO a = conv_for(v, v.act, hf, wf, ACT_RELU, v.tmp);  // conv1 -> norm2 (folded) -> relu
         HIP_TRY(c, conv_launch(pick(c, c->res1[i], (size_t)n * hf * wf), a, s));
-        ConvIO b = conv_for(v.tmp, hf, wf, ACT_NONE, xn);
+        ConvIO b = conv_for(v, v.tmp, hf, wf, ACT_NONE, xn);
         b.resid = x;       // out += x
         if (i + 1 < nr) {  // next block's relu(norm1(.))
             b.out2 = v.act;
@@ -423,45 +390,112 @@ int forward_view(eamm_ctx* c, const FrameView& v, hipStream_t s, hipEvent_t* ev,
         HIP_TRY(c, conv_launch(pick(c, c->res2[i], (size_t)n * hf * wf), b, s));
         std::swap(x, xn);
     }
-    STAGE_MARK(6);
-    if (cev) HIP_TRY(c, hipEventRecord(cev[1], s));
-    // up blocks                                                                generator.py:90-91
-    const float* cur = x;
-    for (int i = 0; i < c->nd; ++i) {
-        if (int urc = launch_up(c, c->up[i], conv_for(cur, hf << i, wf << i, ACT_RELU, v.up_buf[i]), s)) return urc;
-        cur = v.up_buf[i];
-    }
-    STAGE_MARK(7);
-    // final 7x7 + sigmoid, written NCHW straight into the caller's buffer      generator.py:92-93
-    {
-        ConvIO io = conv_for(cur, c->H, c->W, ACT_NONE, v.final_part);
-        if (c->Cimg > 3) {   // plain 7x7 kernel, sigmoid + NCHW store in the epilogue, straight into the caller's [n,C,H,W]
-            io.act = ACT_SIGMOID;
-            io.nchw = 1;
-            io.out = v.out.prediction;
-            HIP_TRY(c, conv_launch(c->final_conv, io, s));
-            account(7);
-            return EAMM_OK;
-        }
-        ConvLayer fl = c->final_conv;
-        fl.Cout = 32;  // 32-float pixel stride; channels >= 21 have zero weights
-        if (final_is_fused(c, n)) {
-            HIP_TRY(c, conv_col7_fused_launch(cur, fl.C0, n, c->H, c->W, c->final_w_swz, c->final_bias, v.out.prediction, s));
-        } else {
-            if (c->final_w_swz && fl.BN == 32)
-                HIP_TRY(c, conv_col7_launch(cur, fl.C0, n, c->H, c->W, c->final_w_swz, v.final_part, s));
-            else
-                HIP_TRY(c, conv_launch(fl, io, s));
-            HIP_TRY(c, final_shift_sum_launch(v.final_part, c->final_bias, n, c->H, c->W, v.out.prediction, s));
-        }
-    }
-    if (v.out.frames_u8) HIP_TRY(c, to_u8_launch(v.out.prediction, n, c->H, c->W, v.out.frames_u8, s));
-    account(7);
-#undef STAGE_MARK
-    return EAMM_OK;   // (the caller records the last stage mark, after joining the chains)
+    return EAMM_OK;
 }
 
-}  // namespace
+// chain: index of this launch sequence among the call's whole-pass chains (0: the caller's stream, whose launches are timed)
+static int stage_bottleneck(eamm_ctx* c, const FrameView& v, hipStream_t s, int chain, bool chained) {
+    const bool timed = chain == 0 && 4 * c->cfg.num_bottleneck_blocks + 1 <= PassProfile::NSUB;
+    switch (bottleneck_form(c, v.n)) {
+        case 4: return bottleneck_wino4(c, v, s, chained, timed);
+        case 2: return bottleneck_wino2(c, v, s, timed);
+        default: return bottleneck_direct(c, v, s);
+    }
+}
+
+static int stage_up(eamm_ctx* c, const FrameView& v, hipStream_t s) {   // generator.py:90-91
+    const float* x = (c->cfg.num_bottleneck_blocks & 1) ? v.xb : v.xa;   // the bottleneck's blocks ping-pong between the two
+    for (int i = 0; i < c->nd; ++i) {
+        if (int rc = launch_up(c, c->up[i], conv_for(v, x, c->hf << i, c->wf << i, ACT_RELU, v.up_buf[i]), s)) return rc;
+        x = v.up_buf[i];
+    }
+    return EAMM_OK;
+}
+
+// final 7x7 + sigmoid on the last up block's output, written NCHW straight into the caller's buffer      generator.py:92-93
+int stage_final(eamm_ctx* c, const FrameView& v, hipStream_t s) {
+    const float* in = v.up_buf[c->nd - 1];
+    ConvIO io = conv_for(v, in, c->H, c->W, ACT_NONE, v.final_part);
+    if (c->Cimg > 3) {   // plain 7x7 kernel, sigmoid + NCHW store in the epilogue, straight into the caller's [n,C,H,W]
+        io.act = ACT_SIGMOID;
+        io.nchw = 1;
+        io.out = v.out.prediction;
+        HIP_TRY(c, conv_launch(c->final_conv, io, s));
+        return EAMM_OK;
+    }
+    ConvLayer fl = c->final_conv;
+    fl.Cout = 32;  // 32-float pixel stride; channels >= 21 have zero weights
+    if (final_is_fused(c, v.n)) {
+        HIP_TRY(c, conv_col7_fused_launch(in, fl.C0, v.n, c->H, c->W, c->final_w_swz, c->final_bias, v.out.prediction, s));
+    } else {
+        if (c->final_w_swz && fl.BN == 32)
+            HIP_TRY(c, conv_col7_launch(in, fl.C0, v.n, c->H, c->W, c->final_w_swz, v.final_part, s));
+        else
+            HIP_TRY(c, conv_launch(fl, io, s));
+        HIP_TRY(c, final_shift_sum_launch(v.final_part, c->final_bias, v.n, c->H, c->W, v.out.prediction, s));
+    }
+    if (v.out.frames_u8) HIP_TRY(c, to_u8_launch(v.out.prediction, v.n, c->H, c->W, v.out.frames_u8, s));
+    return EAMM_OK;
+}
+
+// One launch sequence over the frames of `v` on stream s.  chain: its index among the call's whole-pass chains; `chained`: other
+// sequences run beside it.  (The caller records the last stage mark, after joining the chains.)
+static int forward_view(eamm_ctx* c, const FrameView& v, hipStream_t s, int chain, bool chained) {
+    PassProfile& p = c->prof;
+    const bool direct = bottleneck_form(c, v.n) == 0;
+    int rc;
+    for (int i = 0; i <= (c->nb ? 0 : 4); ++i) HIP_TRY(c, p.mark(i, s, chain));
+    if (c->nb == 0) {   // no motion network (generator.py:64 is false): the encoder features enter the bottleneck as they are
+        HIP_TRY(c, broadcast_features_launch(v.feat, v.n, v.ns, c->hf, c->wf, c->Cb, v.xa, direct ? v.act : nullptr, c->pre_s[0],
+                                             c->pre_t[0], s));
+    } else {
+        if ((rc = stage_motion_front(c, v, s))) return rc;
+        HIP_TRY(c, p.mark(1, s, chain));
+        if ((rc = stage_hg_encoder(c, v, s))) return rc;
+        HIP_TRY(c, p.mark(2, s, chain));
+        if ((rc = stage_hg_decoder(c, v, s))) return rc;
+        HIP_TRY(c, p.mark(3, s, chain));
+        if ((rc = stage_flow_head(c, v, s))) return rc;
+        HIP_TRY(c, p.mark(4, s, chain));
+        if ((rc = stage_warp(c, v, s, direct))) return rc;
+    }
+    HIP_TRY(c, p.mark(5, s, chain));
+    HIP_TRY(c, p.window(chain, 0, s));
+    if ((rc = stage_bottleneck(c, v, s, chain, chained))) return rc;
+    HIP_TRY(c, p.mark(6, s, chain));
+    HIP_TRY(c, p.window(chain, 1, s));
+    if ((rc = stage_up(c, v, s))) return rc;
+    HIP_TRY(c, p.mark(7, s, chain));
+    if ((rc = stage_final(c, v, s))) return rc;
+    p.account(7);
+    return EAMM_OK;
+}
+
+// ---- PassProfile (eamm_ctx.h) -------------------------------------------------------------------------------------------
+void PassProfile::begin_call(int n, int chains) {
+    (void)take_mfma_flops();
+    cur = Call{};
+    cur.n = n;
+    cur.nchain = std::min(chains, (int)MAXCHAIN);
+    const bool rec = on && used < PROF_CALLS;
+    ev = rec ? events.data() + (size_t)used * (NMARK + 1 + NSUB) : nullptr;
+    cev = rec ? chain_ev.data() + (size_t)used * MAXCHAIN * 2 : nullptr;
+    if (rec) calls[used++] = Call{};   // (incomplete until end_call)
+}
+void PassProfile::account(int interval) {
+    const double f = take_mfma_flops();
+    cur.flops += f;
+    cur.stage_flops[interval] += f;
+    if (interval == 5) cur.flops_bneck += f;
+}
+hipError_t PassProfile::end_call(hipStream_t s) {
+    if (!ev) return hipSuccess;
+    const hipError_t e = hipEventRecord(ev[NMARK], s);
+    cur.complete = e == hipSuccess;
+    calls[used - 1] = cur;
+    ev = cev = nullptr;
+    return e;
+}
 
 // -------------------------------------------------------------------------------------------------
 extern "C" {
@@ -496,45 +530,19 @@ int eamm_forward_frames(eamm_ctx* c, int n, const float* kd_val, const float* kd
 
     StreamLease lease(c, s);
     if (lease.rc) return lease.rc;
-    hipEvent_t* ev = nullptr;  // stage boundaries (of the main stream's sequence), recorded only while profiling
-    hipEvent_t* cev = nullptr; // bottleneck window of every whole-pass chain
     const int chains = pass_chains(c, n);
-    c->cur_pass_chains = chains;
     c->cur_call_frames = n;
-    if (c->profiling && c->prof_used < eamm_ctx::PROF_CALLS) {
-        ev = c->prof_events.data() + (size_t)c->prof_used * (eamm_ctx::NMARK + 1 + eamm_ctx::NSUB);
-        cev = c->prof_chain_ev.data() + (size_t)c->prof_used * eamm_ctx::MAXCHAIN * 2;
-        c->prof_n.push_back(n);
-        c->prof_sub.push_back(0);
-        c->prof_marks.push_back(0);
-        c->prof_nchain.push_back(std::min(chains, (int)eamm_ctx::MAXCHAIN));
-        c->prof_flops.push_back(0.0);
-        c->prof_flops_bneck.push_back(0.0);
-        ++c->prof_used;
-    }
-    (void)take_mfma_flops();
-    c->call_flops = c->call_flops_bneck = 0.0;
-    for (double& f : c->call_stage_flops) f = 0.0;
+    c->prof.begin_call(n, chains);
     if (chains == 1) {
-        if (int rc = forward_view(c, make_view(c, 0, n, ns, 0, kd_val, kd_jac, ks_val, ks_jac, o), s, ev, false, cev)) return rc;
+        if (int rc = forward_view(c, make_view(c, 0, n, ns, 0, kd_val, kd_jac, ks_val, ks_jac, o), s, 0, false)) return rc;
     } else {
         const int nbase = n / chains, nrem = n % chains;   // the first nrem chains take one more frame
         HIP_TRY(c, hipEventRecord(c->ev_fork, s));
         for (int k = 1; k < chains; ++k) HIP_TRY(c, hipStreamWaitEvent(c->side_streams[k - 1], c->ev_fork, 0));
-        // EAMM_WARP_JOINT: the chains meet once, after their flow heads: ONE warp launch over all frames (an HBM-bound kernel
-        // that fills the chip alone; per chain it runs beside the other chain's kernels at half the rate), then they part again
-        const bool joint = c->warp_joint && c->nb > 0 && c->ev_warp != nullptr;
-        for (int pass = 0; pass < (joint ? 2 : 1); ++pass) {
-            for (int k = 0; k < chains; ++k) {
-                const int nk = nbase + (k < nrem ? 1 : 0), f0 = k * nbase + std::min(k, nrem);
-                const FrameView v = make_view(c, f0, nk, ns, k, kd_val, kd_jac, ks_val, ks_jac, o);
-                const FrameView all = make_view(c, 0, n, ns, 0, kd_val, kd_jac, ks_val, ks_jac, o);
-                hipStream_t sk = k ? c->side_streams[k - 1] : s;
-                if (int rc = forward_view(c, v, sk, k ? nullptr : ev, true, (cev && k < eamm_ctx::MAXCHAIN) ? cev + 2 * k : nullptr,
-                                          joint ? (pass == 0 ? PH_PRE : PH_POST) : PH_ALL, (joint && pass == 1 && k == 0) ? &all : nullptr))
-                    return rc;
-                if (joint && pass == 0 && k > 0) HIP_TRY(c, hipEventRecord(c->ev_join[k - 1], sk));
-            }
+        for (int k = 0; k < chains; ++k) {
+            const int nk = nbase + (k < nrem ? 1 : 0), f0 = k * nbase + std::min(k, nrem);
+            const FrameView v = make_view(c, f0, nk, ns, k, kd_val, kd_jac, ks_val, ks_jac, o);
+            if (int rc = forward_view(c, v, k ? c->side_streams[k - 1] : s, k, true)) return rc;
         }
         for (int k = 1; k < chains; ++k) {
             HIP_TRY(c, hipEventRecord(c->ev_join[k - 1], c->side_streams[k - 1]));
@@ -550,14 +558,7 @@ int eamm_forward_frames(eamm_ctx* c, int n, const float* kd_val, const float* kd
             HIP_TRY(c, hipMemcpy2DAsync(user->sparse_deformed, C * hw, c->stage_sparse, 3 * hw, C * hw, (size_t)n * (c->K + 1),
                                         hipMemcpyDeviceToDevice, s));
     }
-    if (ev) {   // the last stage ends where the call ends (after the join)
-        HIP_TRY(c, hipEventRecord(ev[eamm_ctx::NMARK], s));
-        c->prof_marks.back() = eamm_ctx::NMARK + 1;
-        c->prof_flops.back() = c->call_flops;
-        c->prof_flops_bneck.back() = c->call_flops_bneck;
-        for (int i = 0; i < eamm_ctx::NMARK; ++i)
-            c->prof_stage_flops[(size_t)(c->prof_used - 1) * eamm_ctx::NMARK + i] = c->call_stage_flops[i];
-    }
+    HIP_TRY(c, c->prof.end_call(s));
     return EAMM_OK;
 }
 
@@ -565,60 +566,56 @@ int eamm_profile_enable(eamm_ctx* c, int on) {
     if (!c) return EAMM_ERR_ARG;
     DeviceGuard guard(c->device);
     if (guard.status != hipSuccess) return fail(c, EAMM_ERR_HIP, "hipSetDevice(%d) failed", c->device);
-    if (on && c->prof_events.empty()) {
-        c->prof_events.resize((size_t)eamm_ctx::PROF_CALLS * (eamm_ctx::NMARK + 1 + eamm_ctx::NSUB));
-        for (auto& e : c->prof_events) HIP_TRY(c, hipEventCreate(&e));
-        c->prof_chain_ev.resize((size_t)eamm_ctx::PROF_CALLS * eamm_ctx::MAXCHAIN * 2);
-        for (auto& e : c->prof_chain_ev) HIP_TRY(c, hipEventCreate(&e));
-        c->prof_stage_flops.assign((size_t)eamm_ctx::PROF_CALLS * eamm_ctx::NMARK, 0.0);
+    PassProfile& p = c->prof;
+    if (on && p.events.empty()) {
+        p.events.resize((size_t)PassProfile::PROF_CALLS * (PassProfile::NMARK + 1 + PassProfile::NSUB));
+        for (auto& e : p.events) HIP_TRY(c, hipEventCreate(&e));
+        p.chain_ev.resize((size_t)PassProfile::PROF_CALLS * PassProfile::MAXCHAIN * 2);
+        for (auto& e : p.chain_ev) HIP_TRY(c, hipEventCreate(&e));
+        p.calls.resize(PassProfile::PROF_CALLS);
     }
-    c->profiling = on != 0;
+    p.on = on != 0;
     return EAMM_OK;
 }
 
 int eamm_profile_read(eamm_ctx* c, double* stage_ms, int nstage, int64_t* calls, int64_t* frames, int reset) {
-    if (!c || !stage_ms || nstage != eamm_ctx::NSTAGE) return fail(c, EAMM_ERR_ARG, "nstage must be %d", eamm_ctx::NSTAGE);
+    constexpr int NSTAGE = PassProfile::NSTAGE, NMARK = PassProfile::NMARK, NSUB = PassProfile::NSUB, MAXCHAIN = PassProfile::MAXCHAIN;
+    if (!c || !stage_ms || nstage != NSTAGE) return fail(c, EAMM_ERR_ARG, "nstage must be %d", NSTAGE);
     DeviceGuard guard(c->device);
     if (guard.status != hipSuccess) return fail(c, EAMM_ERR_HIP, "hipSetDevice(%d) failed", c->device);
+    PassProfile& p = c->prof;
     // stage index of each of the NMARK recorded intervals; the bottleneck interval (5) is split below
-    static const int stage_of[eamm_ctx::NMARK] = {0, 1, 2, 3, 4, 6, 7, 8};
-    int dropped = 0;
-    for (int k = 0; k < c->prof_used; ++k) {  // fold finished event sets into the totals
-        hipEvent_t* ev = c->prof_events.data() + (size_t)k * (eamm_ctx::NMARK + 1 + eamm_ctx::NSUB);
+    static const int stage_of[NMARK] = {0, 1, 2, 3, 4, 6, 7, 8};
+    for (int k = 0; k < p.used; ++k) {  // fold finished event sets into the totals
+        const PassProfile::Call& call = p.calls[k];
+        hipEvent_t* ev = p.events.data() + (size_t)k * (NMARK + 1 + NSUB);
         // a call that failed midway leaves a partly recorded set: skip it (its events are re-recorded by a later call)
-        bool ok = c->prof_marks[k] == eamm_ctx::NMARK + 1 && hipEventSynchronize(ev[eamm_ctx::NMARK]) == hipSuccess;
-        double ms_set[eamm_ctx::NSTAGE] = {0};
-        for (int i = 0; ok && i < eamm_ctx::NMARK; ++i) {
+        bool ok = call.complete && hipEventSynchronize(ev[NMARK]) == hipSuccess;
+        double ms_set[NSTAGE] = {0};
+        auto span = [&](hipEvent_t a, hipEvent_t b) {   // milliseconds from a to b; clears ok on failure
             float ms = 0.f;
-            ok = hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess;
-            ms_set[stage_of[i]] += ms;
-        }
-        const int nsub = c->prof_sub[k];
-        if (ok && nsub > 1) {  // Winograd form: even intervals are input transforms, odd ones the GEMM kernels
-            hipEvent_t* sub = ev + eamm_ctx::NMARK + 1;
+            ok = ok && hipEventElapsedTime(&ms, a, b) == hipSuccess;
+            return (double)ms;
+        };
+        for (int i = 0; ok && i < NMARK; ++i) ms_set[stage_of[i]] += span(ev[i], ev[i + 1]);
+        if (const int nsub = call.sub; ok && nsub > 1) {  // Winograd form: even intervals are input transforms, odd ones the GEMM kernels
+            hipEvent_t* sub = ev + NMARK + 1;
             double tr = 0;
-            for (int i = 0; ok && i + 1 < nsub; i += 2) {
-                float ms = 0.f;
-                ok = hipEventElapsedTime(&ms, sub[i], sub[i + 1]) == hipSuccess;
-                tr += ms;
-            }
+            for (int i = 0; ok && i + 1 < nsub; i += 2) tr += span(sub[i], sub[i + 1]);
             ms_set[5] += tr;
             ms_set[6] -= tr;
-            for (int i = 1; ok && i + 1 < nsub; i += 2) {   // the GEMM kernels' own durations on the main stream
-                float ms = 0.f;
-                ok = hipEventElapsedTime(&ms, sub[i], sub[i + 1]) == hipSuccess;
-                ms_set[9] += ms;
-            }
+            for (int i = 1; ok && i + 1 < nsub; i += 2) ms_set[9] += span(sub[i], sub[i + 1]);   // the GEMM kernels' own durations on the main stream
         }
         if (ok) {   // bottleneck windows of the whole-pass chains, on the clock of this call's first event
-            hipEvent_t* cv = c->prof_chain_ev.data() + (size_t)k * eamm_ctx::MAXCHAIN * 2;
-            const int nc = c->prof_nchain[k];
-            float t0[eamm_ctx::MAXCHAIN], t1[eamm_ctx::MAXCHAIN];
-            for (int j = 0; ok && j < nc; ++j)
-                ok = hipEventSynchronize(cv[2 * j + 1]) == hipSuccess && hipEventElapsedTime(&t0[j], ev[0], cv[2 * j]) == hipSuccess &&
-                     hipEventElapsedTime(&t1[j], ev[0], cv[2 * j + 1]) == hipSuccess;
+            hipEvent_t* cv = p.chain_ev.data() + (size_t)k * MAXCHAIN * 2;
+            const int nc = call.nchain;
+            double t0[MAXCHAIN], t1[MAXCHAIN];
+            for (int j = 0; ok && j < nc; ++j) {
+                ok = hipEventSynchronize(cv[2 * j + 1]) == hipSuccess;
+                t0[j] = span(ev[0], cv[2 * j]), t1[j] = span(ev[0], cv[2 * j + 1]);
+            }
             if (ok) {
-                int order[eamm_ctx::MAXCHAIN];
+                int order[MAXCHAIN];
                 for (int j = 0; j < nc; ++j) order[j] = j;
                 std::sort(order, order + nc, [&](int a, int b) { return t0[a] < t0[b]; });
                 double uni = 0, sum = 0, cur0 = 0, cur1 = -1;
@@ -636,34 +633,26 @@ int eamm_profile_read(eamm_ctx* c, double* stage_ms, int nstage, int64_t* calls,
                 if (cur1 >= cur0) uni += cur1 - cur0;
                 ms_set[10] = uni;
                 ms_set[11] = sum;
-                ms_set[12] = c->prof_flops[k] * 1e-9;
-                ms_set[13] = c->prof_flops_bneck[k] * 1e-9;
-                for (int i = 0; i < eamm_ctx::NMARK; ++i) ms_set[14 + i] = c->prof_stage_flops[(size_t)k * eamm_ctx::NMARK + i] * 1e-9;
+                ms_set[12] = call.flops * 1e-9;
+                ms_set[13] = call.flops_bneck * 1e-9;
+                for (int i = 0; i < NMARK; ++i) ms_set[14 + i] = call.stage_flops[i] * 1e-9;
             }
         }
         if (!ok) {
             (void)hipGetLastError();
-            ++dropped;
             continue;
         }
-        for (int i = 0; i < eamm_ctx::NSTAGE; ++i) c->prof_ms[i] += ms_set[i];
-        c->prof_calls += 1;
-        c->prof_frames += c->prof_n[k];
+        for (int i = 0; i < NSTAGE; ++i) p.ms[i] += ms_set[i];
+        p.ncalls += 1;
+        p.nframes += call.n;
     }
-    (void)dropped;
-    c->prof_used = 0;
-    c->prof_n.clear();
-    c->prof_sub.clear();
-    c->prof_marks.clear();
-    c->prof_nchain.clear();
-    c->prof_flops.clear();
-    c->prof_flops_bneck.clear();
-    for (int i = 0; i < nstage; ++i) stage_ms[i] = c->prof_ms[i];
-    if (calls) *calls = c->prof_calls;
-    if (frames) *frames = c->prof_frames;
+    p.used = 0;
+    for (int i = 0; i < nstage; ++i) stage_ms[i] = p.ms[i];
+    if (calls) *calls = p.ncalls;
+    if (frames) *frames = p.nframes;
     if (reset) {
-        for (double& v : c->prof_ms) v = 0;
-        c->prof_calls = c->prof_frames = 0;
+        for (double& v : p.ms) v = 0;
+        p.ncalls = p.nframes = 0;
     }
     return EAMM_OK;
 }
@@ -690,10 +679,10 @@ int eamm_describe_plan(const eamm_ctx* c, int n, char* buf, int cap) {
     char tmp[1024];
     const int len = snprintf(tmp, sizeof tmp,
                              "{\"frames\": %d, \"pass_chains\": %d, \"frames_per_chain\": %d, \"bottleneck_form\": %d, \"bottleneck_chains\": %d, "
-                             "\"wino4_groups\": %d, \"wino4_variant\": %d, \"hg_encoder\": %s, \"final\": \"%s\", \"warp_joint\": %d, "
+                             "\"wino4_groups\": %d, \"wino4_variant\": %d, \"hg_encoder\": %s, \"final\": \"%s\", "
                              "\"side_streams\": %d, \"experiments_build\": %d}",
                              n, pc, nk, form, bc, (form == 4 && pc == 1 && bc == 1) ? wino4_groups(c, n) : 1, wino4_variant_for(c, n), enc.c_str(),
-                             final_is_fused(c, nk) ? "col7q fused" : "col7 + shift-sum", c->warp_joint, (int)c->pool_streams.size(),
+                             final_is_fused(c, nk) ? "col7q fused" : "col7 + shift-sum", (int)c->pool_streams.size(),
                              eamm_build_experiments());
     if (buf && cap > 0) {
         const int m = std::min(len, cap - 1);

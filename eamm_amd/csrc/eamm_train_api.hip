@@ -9,7 +9,8 @@
 //     -> bn_nhwc_apply                          normalise, ReLU (+ the 2x2 average of DownBlock2d)
 // The forward is therefore RESUMABLE: eamm_train_begin lays it out as a list of steps, eamm_train_next runs them up to the
 // next statistics hand-over and returns 1 with the buffer to reduce, 0 when the pass is complete.  Everything else of the
-// pass (anti-aliasing, heat-maps, sparse motions, flow head, warps, final convolution) is the evaluation path's kernels.
+// pass (anti-aliasing, heat-maps, sparse motions, flow head, warps, final convolution) is the evaluation path's kernels and,
+// stage by stage, its launch sequences (stage_*, eamm_ctx.h; col7 = 0 here, so head and final layer take the im2col-style kernels).
 // This file is the graph-free FORWARD; the backward operators live in backward.hip, conv7_thin.hip, batchnorm*.hip and
 // motion_backward.hip and are composed by eamm_amd/train_graph.py (which also offers this forward, `train_route = "operators"`).
 #include "eamm_ctx.h"
@@ -74,9 +75,8 @@ int eamm_train_begin(eamm_ctx* c, const float* source, int n, const float* kd_va
             return fail(c, EAMM_ERR_ARG, "BatchNorm site %d (%s) has a null tensor", i, c->site_names[i].c_str());
     hipStream_t s = reinterpret_cast<hipStream_t>(stream_);
     const std::vector<eamm_bn_site> st(sites, sites + nsites);
-    const eamm_outputs out = *o;
-    const int H = c->H, W = c->W, h = c->h, w = c->w, hf = c->hf, wf = c->wf, K = c->K, nr = c->cfg.num_bottleneck_blocks;
-    const bool occ = c->cfg.estimate_occlusion_map != 0;
+    const int H = c->H, W = c->W, h = c->h, w = c->w, hf = c->hf, wf = c->wf, nr = c->cfg.num_bottleneck_blocks;
+    const FrameView v = make_view(c, 0, n, n, 0, kd_val, kd_jac, ks_val, ks_jac, o);   // the whole batch, one source per frame
     const int mode = sync ? EAMM_BN_SYNC : EAMM_BN_SINGLE;
     c->steps.clear();
     c->step_pc = 0;
@@ -123,11 +123,7 @@ int eamm_train_begin(eamm_ctx* c, const float* source, int n, const float* kd_va
     }
     // ---- dense motion (dense_motion.py:81-113)
     if (c->nb > 0) {
-        step([=]() -> int {
-            HIP_TRY(c, kp_prepare_launch(kd_val, kd_jac, ks_val, kd_jac ? ks_jac : nullptr, n, n, K, c->kp_rec, c->bad_flag, s));
-            HIP_TRY(c, motion_front_launch(c->kp_rec, c->src_small, n, n, K, h, w, c->cfg.kp_variance, c->Cp0, c->hg_in, out.sparse_deformed, s));
-            return 0;
-        });
+        step([=]() -> int { return stage_motion_front(c, v, s); });
         for (int i = 0; i < c->nb; ++i) {   // Encoder: DownBlock2d (util.py:956-960)
             conv(&c->hg_enc[i], nullptr, i == 0 ? c->hg_in : c->e_buf[i - 1], nullptr, h >> i, w >> i, nullptr, c->raw);
             bn_site(c->raw, n, h >> i, w >> i, c->enc_c[i], 1, c->e_buf[i]);
@@ -138,28 +134,9 @@ int eamm_train_begin(eamm_ctx* c, const float* source, int n, const float* kd_va
                  Win, nullptr, c->raw);
             bn_site(c->raw, n, 2 * Hin, 2 * Win, c->dec_c[i], 0, c->u_buf[i]);
         }
-        step([=]() -> int {   // mask / occlusion logits, softmax, flow, sigmoid (dense_motion.py:98-111): no BatchNorm here
-            ConvIO io = conv_io(c->u_buf[c->nb - 1], n, h, w, ACT_NONE, c->logits, c->partial, c->partial_elems);
-            io.in1 = c->hg_in;
-            ConvLayer head = c->head;
-            if (c->head_nc) {
-                head.Cout = 128;
-                HIP_TRY(c, conv_launch(head, io, s));
-                HIP_TRY(c, motion_head_rowsplit_launch(c->logits, 128, c->head_nc, c->head_bias, c->kp_rec, n, K, h, w, occ ? 1 : 0,
-                                                       c->deformation, c->occlusion, out.mask, out.occlusion_map, s));
-            } else {
-                head.Cout = 32;
-                HIP_TRY(c, conv_launch(head, io, s));
-                HIP_TRY(c, motion_head_launch(c->logits, c->kp_rec, n, K, h, w, occ ? 1 : 0, c->deformation, c->occlusion, out.mask,
-                                              out.occlusion_map, s));
-            }
-            if (out.deformation)
-                HIP_TRY(c, hipMemcpyAsync(out.deformation, c->deformation, (size_t)n * h * w * 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
-            // feature warp x occlusion (generator.py:79-84), 'deformed' (generator.py:86)
-            HIP_TRY(c, warp_features_launch(c->feat, c->deformation, occ ? c->occlusion : nullptr, n, n, hf, wf, c->Cb, h, w, c->xa, nullptr,
-                                            nullptr, nullptr, s));
-            if (out.deformed) HIP_TRY(c, warp_image_launch(c->src_full, c->deformation, n, n, H, W, h, w, out.deformed, s));
-            return 0;
+        step([=]() -> int {   // flow head (no BatchNorm here), then the warps; norm1 of r0 is a site below: no pre-activation
+            if (int rc = stage_flow_head(c, v, s)) return rc;
+            return stage_warp(c, v, s, false);
         });
     } else {
         step([=]() -> int {
@@ -183,15 +160,7 @@ int eamm_train_begin(eamm_ctx* c, const float* source, int n, const float* kd_va
         bn_site(c->raw, n, hf << (i + 1), wf << (i + 1), c->up_c[i], 0, c->up_buf[i]);
         cur = c->up_buf[i];
     }
-    step([=]() -> int {
-        const ConvIO io = conv_io(cur, n, H, W, ACT_NONE, c->final_part, c->partial, c->partial_elems);
-        ConvLayer fl = c->final_conv;
-        fl.Cout = 32;
-        HIP_TRY(c, conv_launch(fl, io, s));
-        HIP_TRY(c, final_shift_sum_launch(c->final_part, c->final_bias, n, H, W, out.prediction, s));
-        if (out.frames_u8) HIP_TRY(c, to_u8_launch(out.prediction, n, H, W, out.frames_u8, s));
-        return 0;
-    });
+    step([=]() -> int { return stage_final(c, v, s); });
     if (site != nsites) return fail(c, EAMM_ERR_STATE, "internal: %d sites laid out, %d expected", site, nsites);
     c->ns_cached = 0;   // the source cache now holds this batch's sources: not a clip's
     return EAMM_OK;
