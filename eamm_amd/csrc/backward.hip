@@ -140,13 +140,49 @@ struct WgradArgs {
     long long a_plane, b_plane;   // their strides in dy / x (floats)
 };
 
-// block (tile pair, tap, split): D[64 co][64 ci] += sum over the split's pixels; 4 waves of 32 x 32, v_mfma_f32_32x32x2_f32.
-// LDS per KC-pixel chunk: dY rows [KC][64] and (shifted, zero-padded) X rows [KC][64]: both as they lie in HBM.  The next
-// chunk's rows are in flight in registers while this chunk's MFMAs run; a row's (x, y) advances incrementally -- on gfx950 a
-// wave streaming f32 MFMAs starves the VALU instructions of its SIMD's other waves, so the loop carries as few as it can.
-template <int KC>
+// What the pixel-split weight-gradient kernels share.  A block of 4 waves (32 x 32 each) owns D[64 rows][64 columns] of one tap and one
+// pixel split; K is walked in chunks of WG_KC pixels.  LDS per chunk: the two operands' rows [WG_KC][64] as they lie in HBM (a pixel's
+// channels are contiguous).  The loader's thread owns rows lr and lr + 16 of a chunk and the 16-byte group lq of the 64 channels.
+constexpr int WG_KC = 32, WG_TM = 64, WG_TN = 64;
+constexpr int WG_LD = WG_TM + 4;   // +4: the two K rows of an MFMA step land on different banks
+
+// registers -> LDS, between the chunk's two barriers
+__device__ __forceinline__ void wgrad_store_chunk(float* As, float* Bs, const f32x4 (&ra)[2], const f32x4 (&rb)[2], int lr, int lq) {
+#pragma unroll
+    for (int h2 = 0; h2 < 2; ++h2) {
+        *reinterpret_cast<f32x4*>(As + (lr + 16 * h2) * WG_LD + lq * 4) = ra[h2];
+        *reinterpret_cast<f32x4*>(Bs + (lr + 16 * h2) * WG_LD + lq * 4) = rb[h2];
+    }
+}
+
+// one chunk's WG_KC / 2 v_mfma_f32_32x32x2_f32 steps; A[m][k]: lane -> m = lane % 32, k = lane / 32
+__device__ __forceinline__ void wgrad_mfma_chunk(const float* As, const float* Bs, int lane, int wm, int wn, f32x16& acc) {
+#pragma unroll
+    for (int s = 0; s < WG_KC / 2; ++s) {
+        const float av = As[(2 * s + (lane >> 5)) * WG_LD + wm * 32 + (lane & 31)];
+        const float bv = Bs[(2 * s + (lane >> 5)) * WG_LD + wn * 32 + (lane & 31)];
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc, 0, 0, 0);
+    }
+}
+
+// a wave's 32 x 32 of slab `slab` of partial [slabs][mt*64][nt*64].  D layout of the 32x32 MFMA: lane -> column n = lane % 32;
+// register r -> row m = (r % 4) + 8 * (r / 4) + 4 * (lane / 32)
+__device__ __forceinline__ void wgrad_store_slab(float* partial, size_t slab, int mt, int nt, int mti, int nti, int wm, int wn, int lane,
+                                                 const f32x16& acc) {
+    float* out = partial + (slab * (mt * WG_TM) + mti * WG_TM + wm * 32) * (size_t)(nt * WG_TN) + nti * WG_TN + wn * 32;
+    static_for<16>([&](auto rc) {
+        constexpr int r = decltype(rc)::value;
+        const int m = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        out[(size_t)m * (nt * WG_TN) + (lane & 31)] = acc[r];
+    });
+}
+
+// block (tile pair, tap, plane, split): D[64 co][64 ci] += sum over the split's pixels.  LDS per chunk: dY rows and (shifted,
+// zero-padded) X rows.  The next chunk's rows are in flight in registers while this chunk's MFMAs run; a row's (x, y) advances
+// incrementally -- on gfx950 a wave streaming f32 MFMAs starves the VALU instructions of its SIMD's other waves, so the loop carries
+// as few as it can.
 __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs p) {
-    constexpr int TM = 64, TN = 64, LD = TM + 4, RPT = KC / 16;   // +4: the two K rows of an MFMA step land on different banks
+    constexpr int KC = WG_KC, TM = WG_TM, TN = WG_TN, LD = WG_LD, RPT = 2;
     __shared__ __attribute__((aligned(16))) float As[KC * LD];
     __shared__ __attribute__((aligned(16))) float Bs[KC * LD];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -164,7 +200,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs p) {
     const float* const px_ = p.x + plane * p.b_plane;
     f32x16 acc;
     static_for<16>([&](auto rc) { acc[decltype(rc)::value] = 0.f; });
-    // loader: thread -> (rows lr + 16 j of the chunk, 16-byte group lq of the 64 channels)
     const int lq = tid & 15, lr = tid >> 4;
     const int co = mti * TM + lq * 4, ci = nti * TN + lq * 4;
     const bool co_ok = co < p.Cout, ci_ok = ci < p.Cin;
@@ -207,30 +242,80 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs p) {
     fetch(p0);
     for (int pc = p0; pc < p1; pc += KC) {
         __syncthreads();
-#pragma unroll
-        for (int h2 = 0; h2 < RPT; ++h2) {
-            *reinterpret_cast<f32x4*>(As + (lr + 16 * h2) * LD + lq * 4) = ra[h2];
-            *reinterpret_cast<f32x4*>(Bs + (lr + 16 * h2) * LD + lq * 4) = rb[h2];
-        }
+        wgrad_store_chunk(As, Bs, ra, rb, lr, lq);
         __syncthreads();
         if (pc + KC < p1) {
             advance();
             fetch(pc + KC);
         }
-#pragma unroll
-        for (int s = 0; s < KC / 2; ++s) {   // A[m][k]: lane -> m = lane % 32, k = lane / 32
-            const float av = As[(2 * s + (lane >> 5)) * LD + wm * 32 + (lane & 31)];
-            const float bv = Bs[(2 * s + (lane >> 5)) * LD + wn * 32 + (lane & 31)];
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc, 0, 0, 0);
-        }
+        wgrad_mfma_chunk(As, Bs, lane, wm, wn, acc);
     }
-    // D layout of the 32x32 MFMA: lane -> column n = lane % 32; register r -> row m = (r % 4) + 8 * (r / 4) + 4 * (lane / 32)
-    float* out = p.partial + (((size_t)split * taps * p.planes + (size_t)plane * taps + tap) * (p.mt * TM) + mti * TM + wm * 32) * (size_t)(p.nt * TN) + nti * TN + wn * 32;
-    static_for<16>([&](auto rc) {
-        constexpr int r = decltype(rc)::value;
-        const int m = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        out[(size_t)m * (p.nt * TN) + (lane & 31)] = acc[r];
-    });
+    wgrad_store_slab(p.partial, (size_t)split * taps * p.planes + (size_t)plane * taps + tap, p.mt, p.nt, mti, nti, wm, wn, lane, acc);
+}
+
+// The stride-2 form: a DENSE operand [B,H,W,Cd] indexed by the pixel p, whose channels are D's rows, and a GATHERED operand
+// [B,2H,2W,Cg] read at (2y + ky - pad, 2x + kx - pad) (zeros outside the map), whose channels are D's columns.  The stride-2
+// convolution's weight gradient has dense = dY, gathered = x, pad = ks / 2; ConvTranspose2d(k4, s2, p1)'s has dense = x, gathered = dY,
+// ks = 4, pad = 1.  The row address is recomputed per chunk (these layers are small; conv_wgrad_kernel's incremental form is for
+// the generator's).
+struct StridedWgradArgs {
+    const float* dense;      // [B,H,W,Cd]
+    const float* gathered;   // [B,2H,2W,Cg]
+    int H, W, Cd, Cg, ks, pad;
+    int P;                   // B*H*W
+    int per_split;           // pixels per split (a multiple of the 32-pixel chunk)
+    int splits, mt, nt;      // pixel splits, Cd tiles, Cg tiles (64 each)
+    float* partial;          // [splits][ks*ks][mt*64][nt*64]
+};
+
+// block (N tile, M tile, tap, split)
+__global__ __launch_bounds__(256) void strided_wgrad_kernel(const StridedWgradArgs p) {
+    constexpr int KC = WG_KC, TM = WG_TM, TN = WG_TN, LD = WG_LD;
+    __shared__ __attribute__((aligned(16))) float As[KC * LD];
+    __shared__ __attribute__((aligned(16))) float Bs[KC * LD];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    int L = blockIdx.x;
+    const int nti = L % p.nt; L /= p.nt;
+    const int mti = L % p.mt; L /= p.mt;
+    const int taps = p.ks * p.ks;
+    const int tap = L % taps; L /= taps;
+    const int split = L;
+    const int dyo = tap / p.ks - p.pad, dxo = tap % p.ks - p.pad;
+    const int p0 = split * p.per_split, p1 = min(p.P, p0 + p.per_split);
+    const int Hg = 2 * p.H, Wg = 2 * p.W;
+    f32x16 acc;
+    static_for<16>([&](auto rc) { acc[decltype(rc)::value] = 0.f; });
+    const int lq = tid & 15, lr = tid >> 4;
+    const int cd = mti * TM + lq * 4, cg = nti * TN + lq * 4;
+    const bool cd_ok = cd < p.Cd, cg_ok = cg < p.Cg;
+    f32x4 ra[2], rb[2];
+    auto fetch = [&](int pc) {
+#pragma unroll
+        for (int h2 = 0; h2 < 2; ++h2) {
+            const int pp = pc + lr + 16 * h2;
+            const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+            ra[h2] = z;
+            rb[h2] = z;
+            if (pp < p1) {
+                const int x = pp % p.W, t = pp / p.W;
+                const int y = t % p.H, b = t / p.H;
+                const int gy = 2 * y + dyo, gx = 2 * x + dxo;
+                if (cd_ok) ra[h2] = *reinterpret_cast<const f32x4*>(p.dense + (size_t)pp * p.Cd + cd);
+                if (cg_ok && (unsigned)gy < (unsigned)Hg && (unsigned)gx < (unsigned)Wg)
+                    rb[h2] = *reinterpret_cast<const f32x4*>(p.gathered + (((size_t)b * Hg + gy) * Wg + gx) * p.Cg + cg);
+            }
+        }
+    };
+    if (p0 < p1) fetch(p0);
+    for (int pc = p0; pc < p1; pc += KC) {
+        __syncthreads();
+        wgrad_store_chunk(As, Bs, ra, rb, lr, lq);
+        __syncthreads();
+        if (pc + KC < p1) fetch(pc + KC);
+        wgrad_mfma_chunk(As, Bs, lane, wm, wn, acc);
+    }
+    wgrad_store_slab(p.partial, (size_t)split * taps + tap, p.mt, p.nt, mti, nti, wm, wn, lane, acc);
 }
 
 // The same GEMM with the KW taps of one filter ROW in one block, for maps whose width is a multiple of the 32-pixel K chunk
@@ -241,7 +326,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs p) {
 // the matrix peak): dY 8 KB + X 8.5 KB per 3 x 262144 flop at 3x3.
 template <int KW>
 __global__ __launch_bounds__(256) void conv_wgrad_row_kernel(const WgradArgs p) {
-    constexpr int KC = 32, TM = 64, TN = 64, LD = TM + 4, HALF = KW / 2;
+    constexpr int KC = WG_KC, TM = WG_TM, TN = WG_TN, LD = WG_LD, HALF = KW / 2;
     __shared__ __attribute__((aligned(16))) float As[KC * LD];
     __shared__ __attribute__((aligned(16))) float Bs[(KC + KW - 1) * LD];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -283,11 +368,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_row_kernel(const WgradArgs p) 
     fetch();
     for (int pc = p0; pc < p1; pc += KC) {
         __syncthreads();
-#pragma unroll
-        for (int h2 = 0; h2 < 2; ++h2) {
-            *reinterpret_cast<f32x4*>(As + (lr + 16 * h2) * LD + lq * 4) = ra[h2];
-            *reinterpret_cast<f32x4*>(Bs + (lr + 16 * h2 + HALF) * LD + lq * 4) = rb[h2];
-        }
+        wgrad_store_chunk(As, Bs + HALF * LD, ra, rb, lr, lq);
         if (KW > 1 && is_halo) *reinterpret_cast<f32x4*>(Bs + (hoff + HALF) * LD + lq * 4) = rh;
         __syncthreads();
         if (pc + KC < p1) {
@@ -315,13 +396,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_row_kernel(const WgradArgs p) 
     const int taps = p.kh * KW;
     static_for<KW>([&](auto tc) {
         constexpr int t = decltype(tc)::value;
-        float* out = p.partial + (((size_t)split * taps + trow * KW + t) * (p.mt * TM) + mti * TM + wm * 32) * (size_t)(p.nt * TN) +
-                     nti * TN + wn * 32;
-        static_for<16>([&](auto rc) {
-            constexpr int r = decltype(rc)::value;
-            const int m = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-            out[(size_t)m * (p.nt * TN) + (lane & 31)] = acc[t][r];
-        });
+        wgrad_store_slab(p.partial, (size_t)split * taps + trow * KW + t, p.mt, p.nt, mti, nti, wm, wn, lane, acc[t]);
     });
 }
 
@@ -483,8 +558,49 @@ bool wgrad_wino4_applies(int B, int H, int W, int Cin, int Cout, int kh, int kw)
 long long wgrad_splits(long long tiles, long long K, long long min_k) {
     return std::max<long long>(1, std::min<long long>(1024 / std::max<long long>(1, tiles) + 1, K / min_k));
 }
-size_t round64(size_t n) { return (n + 63) / 64 * 64; }
+// strided_wgrad_kernel's plan: at most `most` pixel splits (what the workspace holds), each a multiple of the 32-pixel chunk
+struct StridedWgradPlan {
+    int mt, nt, splits, per_split;
+    size_t floats;
+};
+StridedWgradPlan strided_wgrad_plan(int P, int rows, int cols, int taps) {
+    StridedWgradPlan pl;
+    pl.mt = (rows + 63) / 64;
+    pl.nt = (cols + 63) / 64;
+    const int most = (int)wgrad_splits((long long)pl.mt * pl.nt * taps, P, 64);
+    pl.per_split = ((P + most - 1) / most + 31) / 32 * 32;
+    pl.splits = (P + pl.per_split - 1) / pl.per_split;
+    pl.floats = round64((size_t)most * taps * pl.mt * 64 * pl.nt * 64);
+    return pl;
+}
 }  // namespace
+
+size_t strided_wgrad_workspace_floats(int P, int rows, int cols, int ks) { return strided_wgrad_plan(P, rows, cols, ks * ks).floats; }
+
+hipError_t strided_wgrad_launch(const float* dense, const float* gathered, int B, int H, int W, int rows, int cols, int ks, int pad,
+                                float* dweight, float* workspace, hipStream_t s) {
+    const int taps = ks * ks;
+    const StridedWgradPlan pl = strided_wgrad_plan(B * H * W, rows, cols, taps);
+    StridedWgradArgs a{};
+    a.dense = dense;
+    a.gathered = gathered;
+    a.H = H;
+    a.W = W;
+    a.Cd = rows;
+    a.Cg = cols;
+    a.ks = ks;
+    a.pad = pad;
+    a.P = B * H * W;
+    a.per_split = pl.per_split;
+    a.splits = pl.splits;
+    a.mt = pl.mt;
+    a.nt = pl.nt;
+    a.partial = workspace;
+    note_mfma_flops(2.0 * taps * (double)a.splits * a.per_split * (a.mt * 64.0) * (a.nt * 64.0));
+    hipLaunchKernelGGL(strided_wgrad_kernel, dim3((unsigned)(a.mt * a.nt * taps * a.splits)), dim3(256), 0, s, a);
+    // the reduce writes [rows][columns][taps]
+    return conv_wgrad_reduce_launch(workspace, a.splits, taps, a.mt * 64, a.nt * 64, rows, cols, dweight, s);
+}
 
 bool conv_wgrad_takes_transformed(int B, int H, int W, int Cin, int Cout, int kh, int kw) {
     return wgrad_wino4_applies(B, H, W, Cin, Cout, kh, kw);
@@ -538,7 +654,7 @@ hipError_t conv_wgrad_launch(const float* x, const float* dy, int B, int H, int 
         a.splits = (int)((Mq + a.per_split - 1) / a.per_split);
         a.partial = partial;
         note_mfma_flops(2.0 * 36.0 * (double)Mq * (a.mt * 64.0) * (a.nt * 64.0));      // 36 transform-point GEMMs over the tiles
-        hipLaunchKernelGGL(conv_wgrad_kernel<32>, dim3((unsigned)(tiles * a.splits)), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(conv_wgrad_kernel, dim3((unsigned)(tiles * a.splits)), dim3(256), 0, s, a);
         const size_t pairs = (size_t)Cout * Cin;
         hipLaunchKernelGGL(wino4_wgrad_output_kernel, dim3((unsigned)std::min<size_t>((pairs + 255) / 256, 65535)), dim3(256), 0, s, partial,
                            a.splits, a.mt * 64, a.nt * 64, Cout, Cin, dweight);
@@ -557,7 +673,7 @@ hipError_t conv_wgrad_launch(const float* x, const float* dy, int B, int H, int 
         if (row && kw == 1) hipLaunchKernelGGL(conv_wgrad_row_kernel<1>, grid, dim3(256), 0, s, a);
         else if (row && kw == 3) hipLaunchKernelGGL(conv_wgrad_row_kernel<3>, grid, dim3(256), 0, s, a);
         else if (row) hipLaunchKernelGGL(conv_wgrad_row_kernel<7>, grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL(conv_wgrad_kernel<32>, grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL(conv_wgrad_kernel, grid, dim3(256), 0, s, a);
         if (hipError_t e = conv_wgrad_reduce_launch(workspace, a.splits, taps, a.mt * 64, a.nt * 64, Cout, Cin, dweight, s); e != hipSuccess) return e;
     }
     if (dbias != nullptr) {

@@ -26,7 +26,7 @@
 //     slab reduction kernel that applies the same epilogue;
 //   * blockIdx is remapped so that consecutive logical tiles (same M tile, all N tiles) share an XCD
 //     and therefore an L2.
-#include "conv_common.h"
+#include "conv_gather_gemm.h"
 #include <map>
 #include <mutex>
 #include <string>
@@ -44,7 +44,7 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs p) {
     constexpr int BM = WM * MT * 32, BN = WN * NT * 32;
     constexpr int BK = CONV_BK, LDK = CONV_LDK;
     constexpr int T = KH * KW;
-    constexpr int A_PER = BM / 32, B_PER = BN / 32;
+    constexpr int A_PER = BM / 32;
     static_assert(WM * WN == 4, "4 waves per block");
     static_assert(!PHASE || (KH == 2 && KW == 2), "phase mode is the collapsed nearest-x2 + 3x3");
 
@@ -52,10 +52,8 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs p) {
     float* As = smem;                 // [2][BM][LDK]
     float* Bs = smem + 2 * BM * LDK;  // [2][BN][LDK]
 
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int l31 = lane & 31, half = lane >> 5;
-    const int wm = wave / WN, wn = wave % WN;
+    const GatherLanes g = gather_lanes<WN>(threadIdx.x);
+    const int l31 = g.l31, half = g.half, wm = g.wm, wn = g.wn;
 
     int L = xcd_remap(blockIdx.x, gridDim.x);
     const int ntile = L % p.ntiles;
@@ -75,8 +73,8 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs p) {
     const int oy = PHASE ? ((phase >> 1) ? 0 : -1) : -(KH / 2);
     const int ox = PHASE ? ((phase & 1) ? 0 : -1) : -(KW / 2);
 
-    // ---- operand loader state: this thread stages rows arow+32j, 16 bytes at column acol
-    const int arow = tid >> 3, acol = (tid & 7) * 4;
+    // ---- operand loader state (the rows arow + 32 j of the tile that this thread stages)
+    const int arow = g.arow, acol = g.acol;
     int ry[A_PER], rx[A_PER], rb[A_PER];
 #pragma unroll
     for (int j = 0; j < A_PER; ++j) {
@@ -95,84 +93,28 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs p) {
     // Buffer descriptors (wave-uniform, built from kernel arguments): an out-of-range offset makes the
     // hardware return zeros, so zero padding and the M tail need no branch -- the loads stay in flight
     // under the MFMAs and are first waited for at the LDS store.
-    const __amdgpu_buffer_rsrc_t rs0 = __builtin_amdgcn_make_buffer_rsrc((void*)p.in0, 0, p.in0_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs1 =
-        __builtin_amdgcn_make_buffer_rsrc((void*)(p.in1 ? p.in1 : p.in0), 0, p.in1 ? p.in1_bytes : 0u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.w_bytes, 0x00020000);
-    constexpr unsigned OOB = 0xFFFFFFF0u;
+    const __amdgpu_buffer_rsrc_t rs0 = gather_rsrc(p.in0, p.in0_bytes);
+    const __amdgpu_buffer_rsrc_t rs1 = gather_rsrc(p.in1 ? p.in1 : p.in0, p.in1 ? p.in1_bytes : 0u);
+    const __amdgpu_buffer_rsrc_t rsw = gather_rsrc(p.w, p.w_bytes);
     const int wtile = (phase * p.ntiles + ntile) * p.nchunks;
 
-    u32x4 av[A_PER], bv[B_PER];
-    auto load_chunk = [&](int ci) {
+    // chunk ci = (channel chunk cc, tap): the channel chunk picks the input of the concatenation
+    auto chunk = [&](int ci) {
         const int cc = ci / T, tap = ci - cc * T;
         const int dy = tap / KW + oy, dx = tap % KW + ox;
         const int c0 = cc * BK;
         const bool first = c0 < p.C0;
-        const __amdgpu_buffer_rsrc_t rs = first ? rs0 : rs1;
         const int C = first ? p.C0 : p.C1;
         const int coff = (first ? c0 : c0 - p.C0) + acol;
-#pragma unroll
-        for (int j = 0; j < A_PER; ++j) {
+        return gather_chunk(first ? rs0 : rs1, [&, dy, dx, C, coff](int j) {
             const int yy = ry[j] + dy, xx = rx[j] + dx;
             const bool ok = ((unsigned)yy < (unsigned)p.H) & ((unsigned)xx < (unsigned)p.W);
-            const unsigned off = ok ? (unsigned)((rb[j] + yy * p.W + xx) * C + coff) * 4u : OOB;
-            av[j] = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0);
-        }
-        const unsigned woff = (unsigned)((wtile + ci) * (BN * BK) + tid * 4) * 4u;
-#pragma unroll
-        for (int j = 0; j < B_PER; ++j) bv[j] = __builtin_amdgcn_raw_buffer_load_b128(rsw, woff + j * 4096u, 0, 0);
-    };
-    auto store_chunk = [&](int st) {
-        float* a = As + st * BM * LDK + arow * LDK + acol;
-#pragma unroll
-        for (int j = 0; j < A_PER; ++j) *reinterpret_cast<u32x4*>(a + j * 32 * LDK) = av[j];
-        float* b = Bs + st * BN * LDK + arow * LDK + acol;
-#pragma unroll
-        for (int j = 0; j < B_PER; ++j) *reinterpret_cast<u32x4*>(b + j * 32 * LDK) = bv[j];
+            return ok ? (unsigned)((rb[j] + yy * p.W + xx) * C + coff) * 4u : GG_OOB;
+        }, wtile + ci);
     };
 
     f32x16 acc[MT][NT];
-    static_for<MT>([&](auto ic) {
-        static_for<NT>([&](auto jc) {
-            static_for<16>([&](auto rc) { acc[decltype(ic)::value][decltype(jc)::value][decltype(rc)::value] = 0.f; });
-        });
-    });
-
-    auto compute = [&](int st) {
-        const float* a_base = As + st * BM * LDK + (wm * MT * 32 + l31) * LDK + half * 4;
-        const float* b_base = Bs + st * BN * LDK + (wn * NT * 32 + l31) * LDK + half * 4;
-#pragma unroll
-        for (int s = 0; s < BK / 8; ++s) {
-            f32x4 a[MT], b[NT];
-#pragma unroll
-            for (int i = 0; i < MT; ++i) a[i] = *reinterpret_cast<const f32x4*>(a_base + i * 32 * LDK + s * 8);
-#pragma unroll
-            for (int j = 0; j < NT; ++j) b[j] = *reinterpret_cast<const f32x4*>(b_base + j * 32 * LDK + s * 8);
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int i = 0; i < MT; ++i)
-#pragma unroll
-                    for (int j = 0; j < NT; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i][t], b[j][t], acc[i][j], 0, 0, 0);
-        }
-    };
-
-    // ---- main loop: LDS double buffer, one barrier per K chunk
-    if (c_begin < c_end) {
-        load_chunk(c_begin);
-        store_chunk(0);
-        __syncthreads();
-        int st = 0;
-        for (int ci = c_begin; ci < c_end; ++ci) {
-            const bool more = ci + 1 < c_end;
-            if (more) load_chunk(ci + 1);  // buffer loads in flight under the MFMAs
-            compute(st);
-            if (more) store_chunk(st ^ 1);
-            __syncthreads();
-            st ^= 1;
-        }
-    }
+    gather_gemm<MT, NT, WM, WN>(acc, As, Bs, rsw, g, c_begin, c_end, chunk);
 
     // ---- epilogue
     conv_epilogue<MT, NT, BN>(p, acc, mbase, ntile, wm, wn, l31, half, phase, split);

@@ -3,15 +3,14 @@
 // Emotion_k layer2..layer4, :1291-1305).
 //
 // The same GEMM as conv_mfma.hip's register-staged kernel -- M = B*Ho*Wo output pixels, N = Cout, K = taps * Cin, exact fp32
-// via v_mfma_f32_32x32x2_f32, both operands staged HBM/L2 -> VGPR -> LDS with raw buffer loads (an out-of-range offset reads
-// zero: the padding), LDS double buffer, one barrier per 32-channel K chunk -- with the stride in the operand loader: output
-// pixel (oy, ox) reads input pixel (2 oy + ky - KS/2, 2 ox + kx - KS/2).  The weights are pack_conv's plain image
-// ([ntiles][nchunks][BN][BK]), the epilogue (bias, residual, activation) and split-K slabs are conv_common.h's, so nothing of
-// the stride-1 kernels changes.
+// via v_mfma_f32_32x32x2_f32 -- on the same main loop (conv_gather_gemm.h), with the stride in the row offsets that this kernel hands
+// to it: output pixel (oy, ox) reads input pixel (2 oy + ky - KS/2, 2 ox + kx - KS/2), out of the image reads zero.  The weights are
+// pack_conv's plain image ([ntiles][nchunks][BN][BK]), the epilogue (bias, residual, activation) and split-K slabs are
+// conv_common.h's, so nothing of the stride-1 kernels changes.
 //
 // This file is the FORWARD (the engine's eamm_emo_detect and, on a filter packed on the device, the differentiable operator
 // eamm_op_conv_s2); its data and weight gradients are conv_s2_backward.hip.
-#include "conv_common.h"
+#include "conv_gather_gemm.h"
 
 #include <algorithm>
 #include <cstring>
@@ -23,17 +22,15 @@ __global__ __launch_bounds__(256) void conv_s2_kernel(const ConvArgs p, int Hin,
     constexpr int BM = WM * MT * 32, BN = WN * NT * 32;
     constexpr int BK = CONV_BK, LDK = CONV_LDK;
     constexpr int T = KS * KS;
-    constexpr int A_PER = BM / 32, B_PER = BN / 32;
+    constexpr int A_PER = BM / 32;
     static_assert(WM * WN == 4, "4 waves per block");
 
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* As = smem;                 // [2][BM][LDK]
     float* Bs = smem + 2 * BM * LDK;  // [2][BN][LDK]
 
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int l31 = lane & 31, half = lane >> 5;
-    const int wm = wave / WN, wn = wave % WN;
+    const GatherLanes g = gather_lanes<WN>(threadIdx.x);
+    const int l31 = g.l31, half = g.half, wm = g.wm, wn = g.wn;
 
     int L = xcd_remap(blockIdx.x, gridDim.x);
     const int ntile = L % p.ntiles;
@@ -45,8 +42,8 @@ __global__ __launch_bounds__(256) void conv_s2_kernel(const ConvArgs p, int Hin,
     const int c_begin = split * p.chunks_per_split;
     const int c_end = min(p.nchunks, c_begin + p.chunks_per_split);
 
-    // operand loader: this thread stages rows arow+32j, 16 bytes at column acol; (ry, rx) = the input pixel of tap (0, 0) + pad
-    const int arow = tid >> 3, acol = (tid & 7) * 4;
+    // operand loader: (ry, rx) = the input pixel of tap (0, 0) + pad for the rows arow + 32 j that this thread stages
+    const int arow = g.arow, acol = g.acol;
     int ry[A_PER], rx[A_PER], rb[A_PER];
 #pragma unroll
     for (int j = 0; j < A_PER; ++j) {
@@ -64,77 +61,23 @@ __global__ __launch_bounds__(256) void conv_s2_kernel(const ConvArgs p, int Hin,
         }
     }
 
-    const __amdgpu_buffer_rsrc_t rs0 = __builtin_amdgcn_make_buffer_rsrc((void*)p.in0, 0, p.in0_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.w_bytes, 0x00020000);
-    constexpr unsigned OOB = 0xFFFFFFF0u;
+    const __amdgpu_buffer_rsrc_t rs0 = gather_rsrc(p.in0, p.in0_bytes);
+    const __amdgpu_buffer_rsrc_t rsw = gather_rsrc(p.w, p.w_bytes);
     const int wtile = ntile * p.nchunks;
 
-    u32x4 av[A_PER], bv[B_PER];
-    auto load_chunk = [&](int ci) {
+    auto chunk = [&](int ci) {
         const int cc = ci / T, tap = ci - cc * T;
         const int dy = tap / KS - KS / 2, dx = tap % KS - KS / 2;
         const int coff = cc * BK + acol;
-#pragma unroll
-        for (int j = 0; j < A_PER; ++j) {
+        return gather_chunk(rs0, [&, dy, dx, coff](int j) {
             const int yy = ry[j] + dy, xx = rx[j] + dx;
             const bool ok = ((unsigned)yy < (unsigned)Hin) & ((unsigned)xx < (unsigned)Win);
-            const unsigned off = ok ? (unsigned)((rb[j] + yy * Win + xx) * p.C0 + coff) * 4u : OOB;
-            av[j] = __builtin_amdgcn_raw_buffer_load_b128(rs0, off, 0, 0);
-        }
-        const unsigned woff = (unsigned)((wtile + ci) * (BN * BK) + tid * 4) * 4u;
-#pragma unroll
-        for (int j = 0; j < B_PER; ++j) bv[j] = __builtin_amdgcn_raw_buffer_load_b128(rsw, woff + j * 4096u, 0, 0);
-    };
-    auto store_chunk = [&](int st) {
-        float* a = As + st * BM * LDK + arow * LDK + acol;
-#pragma unroll
-        for (int j = 0; j < A_PER; ++j) *reinterpret_cast<u32x4*>(a + j * 32 * LDK) = av[j];
-        float* b = Bs + st * BN * LDK + arow * LDK + acol;
-#pragma unroll
-        for (int j = 0; j < B_PER; ++j) *reinterpret_cast<u32x4*>(b + j * 32 * LDK) = bv[j];
+            return ok ? (unsigned)((rb[j] + yy * Win + xx) * p.C0 + coff) * 4u : GG_OOB;
+        }, wtile + ci);
     };
 
     f32x16 acc[MT][NT];
-    static_for<MT>([&](auto ic) {
-        static_for<NT>([&](auto jc) {
-            static_for<16>([&](auto rc) { acc[decltype(ic)::value][decltype(jc)::value][decltype(rc)::value] = 0.f; });
-        });
-    });
-
-    auto compute = [&](int st) {
-        const float* a_base = As + st * BM * LDK + (wm * MT * 32 + l31) * LDK + half * 4;
-        const float* b_base = Bs + st * BN * LDK + (wn * NT * 32 + l31) * LDK + half * 4;
-#pragma unroll
-        for (int s = 0; s < BK / 8; ++s) {
-            f32x4 a[MT], b[NT];
-#pragma unroll
-            for (int i = 0; i < MT; ++i) a[i] = *reinterpret_cast<const f32x4*>(a_base + i * 32 * LDK + s * 8);
-#pragma unroll
-            for (int j = 0; j < NT; ++j) b[j] = *reinterpret_cast<const f32x4*>(b_base + j * 32 * LDK + s * 8);
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int i = 0; i < MT; ++i)
-#pragma unroll
-                    for (int j = 0; j < NT; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i][t], b[j][t], acc[i][j], 0, 0, 0);
-        }
-    };
-
-    if (c_begin < c_end) {
-        load_chunk(c_begin);
-        store_chunk(0);
-        __syncthreads();
-        int st = 0;
-        for (int ci = c_begin; ci < c_end; ++ci) {
-            const bool more = ci + 1 < c_end;
-            if (more) load_chunk(ci + 1);  // buffer loads in flight under the MFMAs
-            compute(st);
-            if (more) store_chunk(st ^ 1);
-            __syncthreads();
-            st ^= 1;
-        }
-    }
+    gather_gemm<MT, NT, WM, WN>(acc, As, Bs, rsw, g, c_begin, c_end, chunk);
 
     conv_epilogue<MT, NT, BN>(p, acc, mbase, ntile, wm, wn, l31, half, 0, split);
 }

@@ -8,6 +8,7 @@ namespace eamm {
 
 constexpr int CONV_BK = 32;           // K-chunk: 32 input channels of one filter tap
 constexpr int CONV_LDK = CONV_BK + 4; // LDS row stride (dwords): +16 B keeps ds_read_b128 conflict-free
+inline size_t round64(size_t n) { return (n + 63) / 64 * 64; }   // 256-byte aligned sections of a workspace
 constexpr int KP_STRIDE = 8;          // per (frame, keypoint) record: kd.xy, ks.xy, J00 J01 J10 J11
 
 enum Act { ACT_NONE = 0, ACT_RELU = 1, ACT_SIGMOID = 2 };
@@ -277,6 +278,14 @@ hipError_t conv_wgrad_launch(const float* x, const float* dy, int B, int H, int 
 bool conv_wgrad_takes_transformed(int B, int H, int W, int Cin, int Cout, int kh, int kw);
 // dW [Cout,Cin,taps] = the pixel-split slabs partial[splits][taps][Mpad][Npad] added in slice order (also the stride-2 weight gradient's)
 hipError_t conv_wgrad_reduce_launch(const float* partial, int splits, int taps, int Mpad, int Npad, int Cout, int Cin, float* dw, hipStream_t s);
+// The weight gradient of a stride-2 pair of maps (backward.hip's strided_wgrad_kernel): dW[r][c][ky][kx] = sum over the pixels (y, x) of
+// dense [B,H,W,rows] of dense[y, x][r] * gathered[2y + ky - pad, 2x + kx - pad][c], gathered [B,2H,2W,cols] (zeros outside), ks x ks taps;
+// one GEMM per tap, split over the pixels, the slabs summed in slice order into dweight [rows][cols][ks][ks].  workspace: the query's
+// floats (P = B*H*W), 16-byte aligned.  conv_s2_wgrad_launch: dense = dY, gathered = x, pad = ks / 2; deconv4s2_wgrad_launch: dense = x,
+// gathered = dY, ks = 4, pad = 1.
+size_t strided_wgrad_workspace_floats(int P, int rows, int cols, int ks);
+hipError_t strided_wgrad_launch(const float* dense, const float* gathered, int B, int H, int W, int rows, int cols, int ks, int pad,
+                                float* dweight, float* workspace, hipStream_t s);
 
 // conv_pack_dev.hip: the packings of conv_pack_host (register-staged kernel) and wino4_pack_host from a DEVICE OIHW tensor;
 // transposed = 1 reads the forward filter [Cin][Cout][kh][kw] transposed and flipped (the data gradient's filter)

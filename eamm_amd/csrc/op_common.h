@@ -53,8 +53,6 @@ bool op_workspace_ok(const float* workspace, size_t have, size_t need, bool alig
     return workspace && have >= need && (!aligned16 || op_aligned16(workspace));
 }
 
-size_t round64(size_t n) { return (n + 63) / 64 * 64; }   // 256-byte aligned sections of a workspace
-
 // the register-staged implicit GEMM's layer for a filter that is packed on the device (w and bias: the caller's sections)
 ConvLayer plain_conv_layer(int kh, int kw, int Cin, int Cout) {
     ConvLayer L;
