@@ -146,6 +146,8 @@ SIGNATURES = {
                                   C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                   C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "eamm_final_split_planes_elems": (C.c_size_t, [C.c_int]),
+    "eamm_final_split_planes": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "eamm_op_wino_transform": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_void_p, C.c_void_p]),
     "eamm_op_warp_ex": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,

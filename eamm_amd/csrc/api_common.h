@@ -244,6 +244,14 @@ int upload_conv_image(CtxBase* c, float** dst, const HostConv& f, const int* map
     return upload(c, dst, packed);
 }
 
+// The three-plane bf16 image of a row-split final layer (f: to_rowsplit's 7x1 filter with N = 21) for the split-bf16 form of the
+// fused column-patch kernel (conv_col7.hip)
+int upload_col7_split(CtxBase* c, float** dst, const HostConv& f, const int* map, int cin_packed) {
+    std::vector<float> planes(col7_split_packed_elems(cin_packed));
+    col7_pack_split_host(f.w.data(), f.Cout, f.Cin, map, cin_packed, reinterpret_cast<uint16_t*>(planes.data()));
+    return upload(c, dst, planes);
+}
+
 // -> ConvLayer: the register-staged 128 x BN kernel (BN 0: conv_tile_n's), or (dma_cfg > 0) an LDS-DMA tile (conv_dma_tile)
 int pack_conv(CtxBase* c, const HostConv& f, const int* map, int C0_packed, int C1_packed, LayerMode mode, int dma_cfg,
               ConvLayer* L, int BN = 0) {
@@ -311,10 +319,11 @@ int pack_wino(CtxBase* c, const HostConv& f, int tile, WinoLayer* L, bool split_
 // conv (+ optional BatchNorm folded behind it) -> packed device layer.
 // MODE_PLAIN: ks x ks convolution.  MODE_ROWSPLIT: ks x 1 convolution with N = (dx, co) (to_rowsplit); the bias is
 // returned in *row_bias instead of being applied by the convolution.  w_swizzled: a second image of the same weights in
-// the LDS-DMA (XOR-swizzled) layout for an N tile of w_swizzled_bn (0: the layer's), the consumer kernel's.
+// the LDS-DMA (XOR-swizzled) layout for an N tile of w_swizzled_bn (0: the layer's), the consumer kernel's.  w_col7_split (a
+// row-split final layer): a third image, upload_col7_split's.
 int build_layer(CtxBase* c, const std::vector<FoldSpec>& parts, int ks, int C0_real, int C0_packed, int C1_real,
                 int C1_packed, ConvLayer* L, LayerMode mode = MODE_PLAIN, std::vector<float>* row_bias = nullptr,
-                int dma_cfg = 0, float** w_swizzled = nullptr, int w_swizzled_bn = 0) {
+                int dma_cfg = 0, float** w_swizzled = nullptr, int w_swizzled_bn = 0, float** w_col7_split = nullptr) {
     if (mode != MODE_PLAIN && mode != MODE_ROWSPLIT) return fail(c, EAMM_ERR_ARG, "build_layer: plain or row-split layers only");
     HostConv f;
     if (int rc = fold_conv(c, parts, ks, C0_real + C1_real, &f)) return rc;
@@ -324,6 +333,8 @@ int build_layer(CtxBase* c, const std::vector<FoldSpec>& parts, int ks, int C0_r
     }
     const std::vector<int> map = channel_map(C0_real, C0_packed, C1_real, C1_packed);
     if (int rc = pack_conv(c, f, map.data(), C0_packed, C1_packed, MODE_PLAIN, dma_cfg, L)) return rc;
+    if (w_col7_split)
+        if (int rc = upload_col7_split(c, w_col7_split, f, map.data(), C0_packed + C1_packed)) return rc;
     if (!w_swizzled) return EAMM_OK;
     return upload_conv_image(c, w_swizzled, f, map.data(), C0_packed + C1_packed, w_swizzled_bn ? w_swizzled_bn : L->BN,
                              MODE_PLAIN, true);

@@ -16,6 +16,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <cstring>
 
 namespace eamm {
 
@@ -34,7 +35,7 @@ struct Col7Args {
     unsigned in_bytes, w_bytes;
     int C, B, H, W;
     int tiles_x, tiles_y, tiles;   // tiles per row / column / in total (B * tiles_y * tiles_x)
-    const float* w;        // packed [C/32][7][32][32], LDS-DMA swizzle
+    const float* w;        // packed [C/32][7][32][32], LDS-DMA swizzle; conv_col7b_kernel: col7_pack_split_host's three-plane bf16 image
     float* out;            // [B,H,W,32]   (plain form)
     const float* bias;     // [3]          (fused form)
     float* final_out;      // [B,3,H,W]    (fused form): sigmoid(7x7 convolution + bias)
@@ -425,6 +426,177 @@ __global__ __launch_bounds__(CWAVES * 64) void conv_col7q_kernel(const Col7Args 
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// The fused final layer with SPLIT-BF16 products (as SPLIT of wino4_gemm_kernel and FORM 1 of conv_patch_poly_kernel): every fp32
+// operand is the exact sum of three bf16 values taken by truncation, a = a1 + a2 + a3, and a * b is the six products a1b3, a3b1,
+// a2b1, a1b1, a2b2, a1b2 on v_mfma_f32_32x32x16_bf16 with fp32 accumulation (the dropped terms are <= 2^-24 relative).  Rows are
+// the wave's 32 pixels (2 tile rows x 16 columns, as conv_col7_kernel<true>), columns n = (dx, co) padded from 21 to 32: 7 taps x
+// 6 MFMAs of 32 cycles per 16 channels against 7 x 16 x 12 / 2 of 9.3 in the 4x4x1 form.
+//   * A lane's seven vertical taps are seven different patch pixels, so splitting the fragment after the LDS read (as the other two
+//     kernels do) would split every patch value seven times.  Here a value is split ONCE: the DMA lands fp32 in LDS, 16 channels
+//     of the 22 x 16 patch per unit (22 pieces of 1 KiB, one patch row each), and each wave splits the pieces IT fetched
+//     (wino4_split3) into a plane image [plane][k octet][pixel][8 bf16]: tap t is still the same image a constant 256 B further on,
+//     a wave's 32 pixels of a (tap, plane, octet) are 512 contiguous bytes (one conflict-free ds_read_b128), and because a wave
+//     reads back only its own DMA no barrier stands between landing and split, only the wave's vmcnt.
+//   * The weights come split from the host (col7_pack_split_host): [16-channel group][tap][plane][k octet][21 rows][8 bf16], whole
+//     in LDS (55 KiB); lanes of columns >= 21 re-read row 20 (a B column only reaches its own output column, never stored).
+//   * LDS: weights 56 KiB, ONE fp32 stage 22 KiB, TWO plane stages 2 x 33 KiB, carry ring 15.75 KiB = 163 584 B.  Unit u: the
+//     MFMAs read plane stage u & 1 while the DMA of unit u + 1 lands in the fp32 stage; then the wave splits its pieces into plane
+//     stage (u + 1) & 1, whose readers finished before the previous barrier: one barrier per unit.  The finished tile's partial
+//     products go to the plane stage just consumed.
+// Tile walk, patch addressing with hardware zero fill, carry ring and gather epilogue are the fused forms' above.
+namespace {
+constexpr int SG = 16;                                    // channels per unit
+constexpr int S_WBLK = 2 * PS * 16;                       // bytes of a (group, tap, plane) weight block: [octet][21 rows][8 bf16]
+constexpr int S_WGROUP = 7 * 3 * S_WBLK;                  // ... of a 16-channel group
+constexpr int S_WBYTES = (CMAXCH * 2 * S_WGROUP + 1023) / 1024 * 1024;   // weights region, whole DMA pieces (57 344 B)
+constexpr int S_ROWS = CPR;                               // DMA pieces per unit: one 16-pixel patch row x 16 channels = 1 KiB
+constexpr int S_F32 = S_ROWS * 1024;                      // the fp32 stage (22 528 B)
+constexpr int S_OCT = CPIX * 16;                          // bytes of a (plane, octet): 352 pixels x 8 bf16
+constexpr int S_PLANE = 2 * S_OCT;
+constexpr int S_PSTAGE = 3 * S_PLANE;                     // a plane stage (33 792 B)
+constexpr int S_LDS = S_WBYTES + S_F32 + 2 * S_PSTAGE + 2 * CARRY * 4;
+static_assert(S_LDS <= 160 * 1024, "LDS budget");
+static_assert(CT * CT * PS * 4 <= S_PSTAGE, "the tile's partial products fit a consumed plane stage");
+static_assert(CPR <= 3 * CWAVES, "at most three pieces per wave");
+}  // namespace
+
+__global__ __launch_bounds__(CWAVES * 64) void conv_col7b_kernel(const Col7Args p) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];  // weight planes, fp32 stage, [2] plane stages, [2][CARRY]
+    char* const Ws = reinterpret_cast<char*>(smem);
+    char* const Fs = Ws + S_WBYTES;
+    char* const Ps = Fs + S_F32;
+    float* const Carry = reinterpret_cast<float*>(Ps + 2 * S_PSTAGE);
+    const int groups = p.C / SG;
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l31 = lane & 31, half = lane >> 5;
+
+    const __amdgpu_buffer_rsrc_t rsi = __builtin_amdgcn_make_buffer_rsrc((void*)p.in, 0, p.in_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.w_bytes, 0x00020000);
+    constexpr unsigned OOB = 0xFFFFFFF0u;
+
+    const int first = blockIdx.x;
+    const int items = p.B * p.tiles_y;             // tile ROWS, each walked tile by tile from the left
+    const int my_items = first < items ? (items - first + (int)gridDim.x - 1) / (int)gridDim.x : 0;
+    const int units = my_items * p.tiles_x * groups;
+    if (units == 0) return;
+
+    // Patch piece i of this wave = patch row j = wave + 8 i (j < 22): DMA lane L lands at byte 16 L of the piece and fetches
+    // pixel L & 15, channels 8 h + 4 q .. + 3 of the group (h = (L >> 4) & 1, q = L >> 5): the split lane s = 16 h + pixel then
+    // reads its eight channels as the 16-byte slots s and 32 + s, both lane-linear.
+    const int d_px = lane & 15;
+    const int d_rel = d_px * p.C + 8 * ((lane >> 4) & 1) + 4 * (lane >> 5);
+    auto dma_patch_piece = [&](auto ic, const Col7Pos& pos) {
+        constexpr int i = decltype(ic)::value;
+        const int j = wave + CWAVES * i;
+        const int y = pos.ty0 + j - 3, x = pos.tx0 + d_px;
+        const bool ok = ((unsigned)y < (unsigned)p.H) & ((unsigned)x < (unsigned)p.W);
+        const int base = ((pos.b * p.H + y) * p.W + pos.tx0) * p.C + pos.cc * SG;       // wave-uniform
+        const unsigned off = ok ? (unsigned)(base + d_rel) * 4u : OOB;
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsi, (lds_ptr_t)(Fs + j * 1024), 16, off, 0, 0, 0);
+    };
+    // The wave's pieces, fp32 stage -> plane stage `dst`: round 0 lanes 0-31 piece wave, lanes 32-63 piece wave + 8; round 1
+    // lanes 0-31 piece wave + 16 (waves 0-5).  Lane s of a piece: pixel s & 15, k octet s >> 4.
+    auto split_pieces = [&](char* dst) {
+        static_for<2>([&](auto rc) {
+            constexpr int r = decltype(rc)::value;
+            const int j = r == 0 ? wave + CWAVES * half : wave + 2 * CWAVES;
+            if (r == 0 || (half == 0 && j < S_ROWS)) {
+                const char* src = Fs + j * 1024 + l31 * 16;
+                const f32x4 x0 = *reinterpret_cast<const f32x4*>(src), x1 = *reinterpret_cast<const f32x4*>(src + 512);
+                u32x4 pl[3];
+                wino4_split3(x0, x1, pl);
+                char* d = dst + (l31 >> 4) * S_OCT + (j * CT + (l31 & 15)) * 16;
+                static_for<3>([&](auto kc) { *reinterpret_cast<u32x4*>(d + decltype(kc)::value * S_PLANE) = pl[decltype(kc)::value]; });
+            }
+        });
+    };
+
+    // ---- prologue: all weight planes + the first unit's patch, split
+    for (int j = wave; j < groups * S_WGROUP / 1024 + 1; j += CWAVES)    // 1 KiB pieces; the image is padded to whole pieces
+        if (j * 1024 < (int)p.w_bytes)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (lds_ptr_t)(Ws + j * 1024), 16, (unsigned)(j * 1024 + lane * 16), 0, 0, 0);
+    Col7Pos cur{0, 0, first, 0, 0, 0};
+    col7_pos_decode<true>(cur, p);
+    static_for<3>([&](auto ic) {
+        if (wave + CWAVES * decltype(ic)::value < S_ROWS) dma_patch_piece(ic, cur);
+    });
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    split_pieces(Ps);
+    __syncthreads();
+
+    f32x16 acc;
+    static_for<16>([&](auto rc) { acc[decltype(rc)::value] = 0.f; });
+    // A: this lane's pixel of the wave's 32 (rows 2 wave, 2 wave + 1: patch pixel 32 wave + l31 at tap 0) and k octet;
+    // B: its weight row (column n = l31; columns >= 21 re-read row 20) and k octet
+    const int a_off = half * S_OCT + (32 * wave + l31) * 16;
+    const int b_off = half * (PS * 16) + min(l31, PS - 1) * 16;
+    const float bias_r[3] = {p.bias[0], p.bias[1], p.bias[2]};
+
+    for (int u = 0; u < units; ++u) {
+        const int st = u & 1;
+        const bool more = u + 1 < units;
+        const int b = cur.b, ty0 = cur.ty0, tx0 = cur.tx0, cc = cur.cc;
+        Col7Pos nxt = cur;
+        col7_pos_next<true>(nxt, p, groups, (int)gridDim.x);
+        const char* a_stage = Ps + st * S_PSTAGE + a_off;
+        const char* w_stage = Ws + cc * S_WGROUP + b_off;
+        // 7 taps x 6 MFMAs; three plane reads of each operand per tap, one per MFMA gap; the next unit's patch pieces (2 or 3
+        // per wave) ride behind the first three taps
+        u32x4 ap[2][3], wp[2][3];
+        auto fetch = [&](auto tc, int buf) {
+            constexpr int t = decltype(tc)::value;
+            static_for<3>([&](auto kc) {
+                constexpr int k = decltype(kc)::value;
+                ap[buf][k] = *reinterpret_cast<const u32x4*>(a_stage + k * S_PLANE + t * (CT * 16));
+                wp[buf][k] = *reinterpret_cast<const u32x4*>(w_stage + (t * 3 + k) * S_WBLK);
+            });
+        };
+        fetch(std::integral_constant<int, 0>{}, 0);
+        static_for<7>([&](auto tc) {
+            constexpr int t = decltype(tc)::value;
+            if constexpr (t + 1 < 7) fetch(std::integral_constant<int, t + 1>{}, (t + 1) & 1);
+            __builtin_amdgcn_sched_barrier(0);
+            static_for<6>([&](auto mc) {   // a1b3 | a3b1 a2b1 a1b1 | a2b2 a1b2
+                constexpr int m = decltype(mc)::value;
+                constexpr int pa = m == 0 ? 0 : m == 1 ? 2 : m == 2 ? 1 : m == 3 ? 0 : m == 4 ? 1 : 0;
+                constexpr int pb = m == 0 ? 2 : m <= 3 ? 0 : 1;
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, ap[t & 1][pa]),
+                                                              __builtin_bit_cast(bf16x8_t, wp[t & 1][pb]), acc, 0, 0, 0);
+            });
+            if constexpr (t < 3) {
+                __builtin_amdgcn_sched_barrier(0);
+                if (more && wave + CWAVES * t < S_ROWS) dma_patch_piece(tc, nxt);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        });
+        if (more) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            split_pieces(Ps + (st ^ 1) * S_PSTAGE);
+        }
+        if (cc == groups - 1) {
+            // every wave is done with this unit's plane stage (the next unit's planes went to the other one): it becomes the
+            // scratch for the tile's partial products P[row][column][dx*3 + co]
+            __syncthreads();
+            float* const scratch = reinterpret_cast<float*>(Ps + st * S_PSTAGE);
+            static_for<16>([&](auto rc) {
+                constexpr int r = decltype(rc)::value;
+                const int m = (r & 3) + 8 * (r >> 2) + 4 * half;
+                const int row = 2 * wave + (m >> 4), col = m & 15;
+                if (l31 < PS) scratch[(row * CT + col) * PS + l31] = acc[r];
+                acc[r] = 0.f;
+            });
+            __syncthreads();
+            col7_gather_tile(p, scratch, Carry, bias_r, b, ty0, tx0, tid);
+        }
+        __syncthreads();
+        cur = nxt;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // Same tile geometry for the row-split flow head (7x1 over N = 7 x (K+2) = 84 of 96, two concatenated inputs, 128 input
 // channels): the weights ([4][7][96][32] = 336 KiB) do not fit, so they stream one (chunk, tap) tile per barrier interval
 // (NT x 4 KiB, double buffered) next to the two patch stages; one workgroup per 16x16 tile.
@@ -581,8 +753,36 @@ hipError_t conv_col7s_launch(const float* in0, int C0, const float* in1, int C1,
     return hipGetLastError();
 }
 
+// floats of device memory the three-plane image of conv_col7b_kernel takes (whole 1 KiB DMA pieces)
+size_t col7_split_packed_elems(int cin_packed) { return ((size_t)(cin_packed / SG) * S_WGROUP + 1023) / 1024 * 256; }
+
+// The row-split 7x1 weights w [Cout <= 21][Cin][7] (to_rowsplit of the folded 7x7 filter: the fp32-ROUNDED values the fp32 image is
+// packed from) as three bf16 planes by truncation, w1 = top 16 bits of w, w2 = top 16 bits of w - w1, w3 = w - w1 - w2 (both
+// differences exact), so w1 + w2 + w3 is that float exactly.  Image [16-channel group][tap][plane][k octet][21 rows][8]: lane
+// (row n, octet h) of conv_col7b_kernel reads the group's channels 8 h .. 8 h + 7 with one ds_read_b128.
+void col7_pack_split_host(const float* w, int Cout, int Cin, const int* cin_map, int cin_packed, uint16_t* dst) {
+    const size_t total = 2 * col7_split_packed_elems(cin_packed);
+    for (size_t i = 0; i < total; ++i) dst[i] = 0;
+    auto bits = [](float f) { uint32_t b; memcpy(&b, &f, 4); return b; };
+    auto top = [](uint32_t b) { b &= 0xFFFF0000u; float f; memcpy(&f, &b, 4); return f; };
+    for (int n = 0; n < Cout && n < PS; ++n)
+        for (int cp = 0; cp < cin_packed; ++cp) {
+            const int c = cin_map ? cin_map[cp] : cp;
+            if (c < 0 || c >= Cin) continue;
+            for (int t = 0; t < 7; ++t) {
+                const float u = w[((size_t)n * Cin + c) * 7 + t];
+                const float r = u - top(bits(u)), r2 = r - top(bits(r));
+                const int g = cp / SG, h = (cp % SG) >> 3, e = cp & 7;
+                uint16_t* blk = dst + ((size_t)(g * 7 + t) * 3 * S_WBLK + h * (PS * 16) + n * 16) / 2 + e;
+                blk[0] = (uint16_t)(bits(u) >> 16);
+                blk[S_WBLK / 2] = (uint16_t)(bits(r) >> 16);
+                blk[S_WBLK] = (uint16_t)(bits(r2) >> 16);
+            }
+        }
+}
+
 static hipError_t col7_launch_impl(const float* in, int C, int B, int H, int W, const float* w_swizzled, float* out, const float* bias,
-                                   float* final_out, hipStream_t stream) {
+                                   float* final_out, hipStream_t stream, const float* w_split = nullptr) {
     const bool fused = final_out != nullptr;
     if (C % CONV_BK || C / CONV_BK > CMAXCH || C < CONV_BK) return hipErrorInvalidValue;
     Col7Args a{};
@@ -619,6 +819,17 @@ static hipError_t col7_launch_impl(const float* in, int C, int B, int H, int W, 
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     const int blocks = std::min(fused ? B * a.tiles_y : a.tiles, cus);
+    if (fused && w_split) {   // the split-bf16 product form on the layer's three-plane image
+        static lds_once_mask configured_b{0};
+        a.w = w_split;
+        a.w_bytes = (unsigned)(col7_split_packed_elems(C) * 4);
+        // The layer counts what its fp32 form issues (N = 24), whatever the product form: bench.py prices `stage_roofline.final`
+        // against the fp32 matrix peak, and the fp32-equivalent of the N = 32 columns issued here exceeded it (1.02 of the peak).
+        note_mfma_flops(2.0 * a.tiles * (CT * CT) * 7.0 * 24 * C);
+        if (hipError_t e = ensure_dynamic_lds(conv_col7b_kernel, S_LDS, &configured_b); e != hipSuccess) return e;
+        hipLaunchKernelGGL(conv_col7b_kernel, dim3(blocks), dim3(CWAVES * 64), S_LDS, stream, a);
+        return hipGetLastError();
+    }
     // EAMM_FINAL_MFMA4 = 0: the fused form on the 32x32x2 MFMA with N padded to 32 (round 3); default: the 4x4x1 multi-block form
     static const bool mfma4 = knob_int("EAMM_FINAL_MFMA4", 1) != 0;
     if (fused && mfma4) {
@@ -644,9 +855,9 @@ hipError_t conv_col7_launch(const float* in, int C, int B, int H, int W, const f
 }
 
 hipError_t conv_col7_fused_launch(const float* in, int C, int B, int H, int W, const float* w_swizzled, const float* bias,
-                                  float* out_nchw, hipStream_t stream) {
+                                  float* out_nchw, hipStream_t stream, const float* w_split) {
     if (!bias || !out_nchw) return hipErrorInvalidValue;
-    return col7_launch_impl(in, C, B, H, W, w_swizzled, nullptr, bias, out_nchw, stream);
+    return col7_launch_impl(in, C, B, H, W, w_swizzled, nullptr, bias, out_nchw, stream, w_split);
 }
 
 }  // namespace eamm

@@ -451,7 +451,7 @@ int eamm_finalize_weights(eamm_ctx* c) {
         std::vector<float> fb;
         const bool col7_ok = c->col7 && c->up_c.back() % 32 == 0 && c->up_c.back() <= 64;
         if ((rc = build_layer(c, {{"final", ""}}, 7, c->up_c.back(), c->up_c.back(), 0, 0, &c->final_conv,
-                              MODE_ROWSPLIT, &fb, 0, col7_ok ? &c->final_w_swz : nullptr)))
+                              MODE_ROWSPLIT, &fb, 0, col7_ok ? &c->final_w_swz : nullptr, 0, col7_ok ? &c->final_w3 : nullptr)))
             return rc;
         if (c->final_conv.Cout != 21) return fail(c, EAMM_ERR_KEY, "final.weight must have 3 output channels");
         if ((rc = upload(c, &c->final_bias, fb))) return rc;

@@ -128,6 +128,7 @@ struct eamm_ctx : eamm::CtxBase {
     float* final_bias = nullptr;   // bias of the final conv, applied by the shift-sum kernel
     float* final_part = nullptr;   // [F,H,W,32] (dx,co) partial products of the final 7x7 conv
     float* final_w_swz = nullptr;  // the 7x1 weights in LDS-DMA layout for the column-patch kernel (conv_col7.hip)
+    float* final_w3 = nullptr;     // ... and as three bf16 planes (col7_pack_split_host): the fused launches run split-bf16 products
     int col7 = 1;                  // EAMM_COL7: 0 = im2col-style kernel for the final convolution
     int final_fused = 1;           // EAMM_FINAL_FUSED: 0 = partial products to HBM + final_shift_sum_kernel (round 2)
     int final_fused_min_rows = 128; // ... from this many rows of 16x16 tiles per call (EAMM_FINAL_FUSED_MIN_ROWS)

@@ -426,7 +426,7 @@ int stage_final(eamm_ctx* c, const FrameView& v, hipStream_t s) {
     ConvLayer fl = c->final_conv;
     fl.Cout = 32;  // 32-float pixel stride; channels >= 21 have zero weights
     if (final_is_fused(c, v.n)) {
-        HIP_TRY(c, conv_col7_fused_launch(in, fl.C0, v.n, c->H, c->W, c->final_w_swz, c->final_bias, v.out.prediction, s));
+        HIP_TRY(c, conv_col7_fused_launch(in, fl.C0, v.n, c->H, c->W, c->final_w_swz, c->final_bias, v.out.prediction, s, c->final_w3));
     } else {
         if (c->final_w_swz && fl.BN == 32)
             HIP_TRY(c, conv_col7_launch(in, fl.C0, v.n, c->H, c->W, c->final_w_swz, v.final_part, s));
@@ -680,9 +680,10 @@ int eamm_describe_plan(const eamm_ctx* c, int n, char* buf, int cap) {
     const int len = snprintf(tmp, sizeof tmp,
                              "{\"frames\": %d, \"pass_chains\": %d, \"frames_per_chain\": %d, \"bottleneck_form\": %d, \"bottleneck_chains\": %d, "
                              "\"wino4_groups\": %d, \"wino4_variant\": %d, \"hg_encoder\": %s, \"final\": \"%s\", "
-                             "\"side_streams\": %d, \"experiments_build\": %d}",
+                             "\"final_products\": \"%s\", \"side_streams\": %d, \"experiments_build\": %d}",
                              n, pc, nk, form, bc, (form == 4 && pc == 1 && bc == 1) ? wino4_groups(c, n) : 1, wino4_variant_for(c, n), enc.c_str(),
-                             final_is_fused(c, nk) ? "col7q fused" : "col7 + shift-sum", (int)c->pool_streams.size(),
+                             final_is_fused(c, nk) ? "col7q fused" : "col7 + shift-sum",
+                             final_is_fused(c, nk) && c->final_w3 ? "split-bf16" : "fp32", (int)c->pool_streams.size(),
                              eamm_build_experiments());
     if (buf && cap > 0) {
         const int m = std::min(len, cap - 1);

@@ -35,6 +35,10 @@ const char* conv_refusal(const ConvOp& a) {
                           (a.kh == 1 && a.kw == 1 && staged && !a.up);
     if (!a.in0 || !a.w || !a.b || !a.out || !shape_ok || a.C0 % CONV_BK || a.C1 % CONV_BK || (a.up && (a.kh != 3 || a.kw != 3)))
         return "bad argument";
+    if ((a.tile_n == 4002 || a.tile_n == 4003) &&
+        (a.kh != 7 || a.kw != 7 || a.Cout != 3 || a.act != 2 || a.up || a.pool || a.resid || a.C1 || a.C0 % 32 || a.C0 > 64 || a.C0 < 32))
+        return a.tile_n == 4002 ? "unsupported fused final-layer configuration (tile code 4002)"
+                                : "unsupported fused final-layer configuration (tile code 4003)";
     if ((a.pre_s != nullptr) != (a.pre_t != nullptr)) return "pre_scale and pre_shift come together";
     if (a.pre_s && !wino) return "pre_scale / pre_shift belong to the Winograd input transform (tile codes 2000, 21xx)";
     const bool second = a.out2 || a.s2 || a.t2;
@@ -65,17 +69,16 @@ HostConv op_weights(const ConvOp& a, int Cin, bool with_bias = true) {
     return f;
 }
 
-// 4002: the final layer whole (7x7, 3 output channels, bias, sigmoid -> NCHW) on the fused column-patch kernel, with the
-// row-split weights of the engine's final_w_swz
+// 4002: the final layer whole (7x7, 3 output channels, bias, sigmoid -> NCHW) on the fused column-patch kernel as the engine
+// runs it: the row-split weights of its final_w_swz and their three-plane image final_w3 (split-bf16 products); 4003: the same
+// with fp32 products forced (no three-plane image)
 int op_conv_final(OpBuffers* t, const ConvOp& a) {
-    if (a.kh != 7 || a.kw != 7 || a.Cout != 3 || a.act != 2 || a.up || a.pool || a.resid || a.C1 || a.C0 % 32 || a.C0 > 64 || a.C0 < 32)
-        return fail(t, EAMM_ERR_ARG, "%s: unsupported fused final-layer configuration", a.name);
     HostConv f = op_weights(a, a.C0);
     const std::vector<float> bias = to_rowsplit(&f);
-    float *w = nullptr, *b = nullptr;
+    float *w = nullptr, *b = nullptr, *w3 = nullptr;
     int rc = upload_conv_image(t, &w, f, nullptr, a.C0, conv_tile_n(f.Cout), MODE_PLAIN, true);
-    if (rc || (rc = upload(t, &b, bias))) return rc;
-    auto fused_final = [&]() { return conv_col7_fused_launch(a.in0, a.C0, a.B, a.Hin, a.Win, w, b, a.out, a.s); };
+    if (rc || (rc = upload(t, &b, bias)) || (a.tile_n == 4002 && (rc = upload_col7_split(t, &w3, f, nullptr, a.C0)))) return rc;
+    auto fused_final = [&]() { return conv_col7_fused_launch(a.in0, a.C0, a.B, a.Hin, a.Win, w, b, a.out, a.s, w3); };
     HIP_TRY(t, fused_final());
     HIP_TRY(t, time_launches(a.s, a.iters, a.avg_ms, fused_final));
     return EAMM_OK;
@@ -189,7 +192,7 @@ int op_conv_gemm(OpBuffers* t, const ConvOp& a) {
 // eamm_op_conv: the family of tile_n (include/eamm_hip.h), then the caller's stream drained
 int op_conv_run(OpBuffers* t, const ConvOp& a) {
     int rc;
-    if (a.tile_n == 4002) rc = op_conv_final(t, a);
+    if (a.tile_n == 4002 || a.tile_n == 4003) rc = op_conv_final(t, a);
     else if (a.tile_n == 4000 || a.tile_n == 4001) rc = op_conv_col7(t, a);
     else if (a.tile_n == 3000 || a.tile_n == 3003 || a.tile_n == 3004) rc = op_conv_patch(t, a);
     else if (a.tile_n >= 2000 && a.tile_n < 2200) rc = op_conv_wino(t, a);
@@ -251,6 +254,23 @@ int eamm_op_conv(int device, const float* in0, int C0, const float* in1, int C1,
                         ConvOp{in0, in1, C0, C1, B, Hin, Win, up, w_host, b_host, Cout, kh, kw, act, pool, resid, splitk, tile_n, out, iters,
                                avg_ms, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, "eamm_op_conv", nullptr},
                         stream_);
+}
+
+// the final layer's host packing alone (no device): the row-split fp32 weights and their three-plane bf16 image
+size_t eamm_final_split_planes_elems(int C) { return (C == 32 || C == 64) ? 2 * col7_split_packed_elems(C) : 0; }
+int eamm_final_split_planes(const float* w_host, int C, float* rowsplit, uint16_t* planes) {
+    if (!w_host || !rowsplit || !planes || (C != 32 && C != 64))
+        return fail(nullptr, EAMM_ERR_ARG, "eamm_final_split_planes: bad argument (C = 32 | 64)");
+    HostConv f;
+    f.Cout = 3;
+    f.Cin = C;
+    f.kh = f.kw = 7;
+    f.w.assign(w_host, w_host + (size_t)3 * C * 49);
+    f.b.assign(3, 0.f);
+    to_rowsplit(&f);
+    std::copy(f.w.begin(), f.w.end(), rowsplit);
+    col7_pack_split_host(f.w.data(), f.Cout, f.Cin, nullptr, C, planes);
+    return EAMM_OK;
 }
 
 // the Winograd input transform alone, as the engine launches it: V[(tile + 2)^2][B * H/tile * W/tile][C]

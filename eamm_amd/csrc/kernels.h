@@ -130,8 +130,14 @@ hipError_t conv_col7_launch(const float* in, int C, int B, int H, int W, const f
                             hipStream_t stream);
 // the same with the horizontal gather, bias and sigmoid in the tile epilogue: out_nchw [B,3,H,W] = sigmoid(conv7x7 + bias)
 // (weights: the row-split image above built from a 3-output-channel 7x7 filter, bias [3] on the device)
+// w_split: the same weights as three bf16 planes (col7_pack_split_host), with which the products run in the split-bf16 form
+// (fp32-exact to 2^-24 relative); nullptr: fp32 MFMA products
 hipError_t conv_col7_fused_launch(const float* in, int C, int B, int H, int W, const float* w_swizzled, const float* bias,
-                                  float* out_nchw, hipStream_t stream);
+                                  float* out_nchw, hipStream_t stream, const float* w_split = nullptr);
+// the row-split weights [Cout <= 21][Cin][7] as three bf16 planes whose sum is the fp32 weight exactly; col7_split_packed_elems: the
+// image's size in FLOATS
+size_t col7_split_packed_elems(int cin_packed);
+void col7_pack_split_host(const float* w_rowsplit, int Cout, int Cin, const int* cin_map, int cin_packed, uint16_t* dst);
 
 // streamed-weight variant for the row-split flow head: two concatenated inputs, N = ntile32*32 (3 -> 96), weights packed with
 // conv_pack_host(..., kh 7, kw 1, BN 96, swizzle); out [B,H,W,pixel_stride]

@@ -494,7 +494,10 @@ int eamm_profile_read(eamm_ctx* ctx, double* stage_ms, int nstage, int64_t* call
  *   3004             the polyphase form with fp32-MFMA products forced (splitk as 3003)
  *   4000 / 4001      column-patch kernel of a row-split 7x1 convolution (weights [Cout][C][7][1], no bias applied, act 0):
  *                    4000 the final layer (Cout 32, C0 32 or 64, no in1), 4001 the flow head (Cout 96, two inputs)
- *   4002             the generator's final layer whole (7x7, Cout 3, act 2: out is NCHW [B,3,H,W])
+ *   4002             the generator's final layer whole (7x7, Cout 3, act 2, C0 32 or 64, no in1: out is NCHW [B,3,H,W]) as the
+ *                    engine runs it: every product as six bf16 MFMAs on exact three-way bf16 splits of the fp32 operands
+ *                    (fp32-exact to 2^-24 relative; an inf input gives NaN where the fp32 form saturates the sigmoid)
+ *   4003             the final layer with fp32-MFMA products forced; refuses what 4002 refuses
  * out NHWC [B,H(/2),W(/2),Cout] with H = Hin << up.  iters > 0 additionally times `iters` back-to-back launches with HIP
  * events on `stream` and stores the average milliseconds in *avg_ms; a failed launch returns EAMM_ERR_HIP and stores
  * no time. */
@@ -523,6 +526,13 @@ int eamm_op_conv_ex(int device, const float* in0, int C0, const float* in1, int 
                     int act, int pool, const float* resid, int splitk, int tile_n, float* out, int iters,
                     float* avg_ms, const float* pre_scale, const float* pre_shift, float* out2, const float* scale2,
                     const float* shift2, int nchw, int split_n, void* stream);
+
+/* The host packing behind tile code 4002, no device involved: weight_host [3][C][7][7] (C = 32 | 64) -> rowsplit [21][C][7], the
+ * 7x1 filter with n = dx * 3 + co the fp32 kernels' image is packed from, and planes, eamm_final_split_planes_elems(C) uint16: its
+ * three bf16 planes [C/16][tap 7][plane 3][k octet 2][row n 21][8] (channel = 16 group + 8 octet + element), zero-padded to whole
+ * KiB.  Plane values are the top halves of fp32 numbers whose sum is the rowsplit weight bit for bit. */
+size_t eamm_final_split_planes_elems(int C);
+int eamm_final_split_planes(const float* weight_host, int C, float* rowsplit, uint16_t* planes);
 
 /* The Winograd input transform of the 3x3 / pad 1 convolution on its own, as the engine launches it: x NHWC [B,H,W,C] ->
  * V[(tile + 2)^2][B * H/tile * W/tile][C] = B^T d B of every (tile + 2)^2 patch d (stride tile, one pixel of zero padding), tile = 2
