@@ -1,22 +1,30 @@
-// Column-patch kernel for the 7x1 (vertical) MFMA convolution behind the generator's final 7x7 convolution
-// (reference modules/generator.py:47,92: Conv2d(64 -> 3, 7x7, pad 3) + sigmoid).
+// Column-patch kernels for the 7x1 (vertical) MFMA convolutions: the generator's final 7x7 convolution (reference
+// modules/generator.py:47,92: Conv2d(64 -> 3, 7x7, pad 3) + sigmoid) and the row-split flow head.
 //
-// The final layer runs as a 7x1 convolution with N = (dx, co) = 21 "output channels" followed by a horizontal gather
-// (final_shift_sum_kernel, motion.hip).  The im2col-style kernel re-fetched its activation operand
-// once per vertical tap -- 7 x 268 MB through L2 per launch at 256^2 x 16 frames, which bounds it (5.6 TB/s of
-// L2 -> LDS traffic for 89 TFLOP/s).  Here a persistent workgroup walks 16x16-pixel tiles:
-//   * per 32-channel chunk the (16+6) x 16 input patch is DMA'd into LDS once (44 KiB); vertical tap t of output pixel
-//     (r, c) is patch pixel (r + t, c) = the same swizzled LDS image 2 KiB further on, so the seven taps' A fragments
-//     cost no address arithmetic at all (an immediate offset);
-//   * the whole weight tensor ([chunks][7][32][32] = 56 KiB for 64 input channels) stays resident in LDS;
-//   * the patch of the next (tile, chunk) unit streams in behind the 112 MFMAs of the current one (two stages).
-// Operand traffic drops from 7x to 22/16 = 1.4x the activation; the kernel is matrix-pipe bound (N = 21 of a 32-wide
-// tile is the remaining waste).  Output: the [B,H,W,32] partial products the gather kernel reads.
+// The final layer runs as a 7x1 convolution with N = (dx, co) = 21 "output channels" followed by a horizontal gather of the seven
+// dx taps.  The im2col-style kernel re-fetched its activation operand once per vertical tap -- 7 x 268 MB
+// through L2 per launch at 256^2 x 16 frames, which bounds it (5.6 TB/s of L2 -> LDS traffic for 89 TFLOP/s).  Here a persistent
+// workgroup walks 16x16-pixel tiles:
+//   * per channel chunk the (16+6) x 16 input patch is DMA'd into LDS once; vertical tap t of output pixel (r, c) is patch pixel
+//     (r + t, c) = the same LDS image a constant distance further on, so the seven taps' A fragments cost no address arithmetic
+//     at all (an immediate offset);
+//   * the whole weight tensor stays resident in LDS;
+//   * the patch of the next (tile, chunk) unit streams in behind the MFMAs of the current one.
+// Operand traffic drops from 7x to 22/16 = 1.4x the activation; the kernels are matrix-pipe bound.
+//
+// Which kernel runs when (conv_col7_launch / conv_col7_fused_launch; the engine fuses from final_fused_min_rows tile rows on):
+//   conv_col7_kernel   plain: 32x32x2 fp32 MFMAs, N padded to 32; the [B,H,W,32] partial products go to HBM and
+//                      final_shift_sum_kernel (motion.hip) gathers them.  Small launches, e.g. one frame per call; tile code 4000.
+//   conv_col7q_kernel  fused, fp32 products on the 4x4x1 multi-block MFMA (N = 24): gather, bias and sigmoid in the tile's
+//                      epilogue.  The training entry eamm_op_final_conv_sigmoid and tile code 4003.
+//   conv_col7b_kernel  fused, split-bf16 products (fp32-exact): the engine's default, tile code 4002.
+//   conv_col7s_kernel  the flow head (N = 84 of 96, streamed weights, one workgroup per tile); tile code 4001.
+// Shared: the tile walk (Col7Pos) and the work split (col7_units) by the three final-layer kernels; the fp32 patch stage
+// (Col7Patch), the weight prologue and the unit loop (col7_walk_f32) by the two fp32 ones, which differ in the MFMA body of a
+// unit and in what happens to a finished tile; the gather epilogue (col7_gather_tile) by the two fused ones.
 #include "conv_common.h"
 
 #include <algorithm>
-#include <cstdlib>
-#include <cstring>
 
 namespace eamm {
 
@@ -28,6 +36,7 @@ constexpr int CPR = CT + 6;              // patch rows (halo 3 above and below)
 constexpr int CPIX = CPR * CT;           // 352 patch pixels = 44 DMA instructions of 8 pixels
 constexpr int CWAVES = 8;
 constexpr int CMAXCH = 2;                // channel chunks whose weights fit beside the two patch stages
+constexpr size_t LDS_BUDGET = 160 * 1024;
 }  // namespace
 
 struct Col7Args {
@@ -37,17 +46,17 @@ struct Col7Args {
     int tiles_x, tiles_y, tiles;   // tiles per row / column / in total (B * tiles_y * tiles_x)
     const float* w;        // packed [C/32][7][32][32], LDS-DMA swizzle; conv_col7b_kernel: col7_pack_split_host's three-plane bf16 image
     float* out;            // [B,H,W,32]   (plain form)
-    const float* bias;     // [3]          (fused form)
-    float* final_out;      // [B,3,H,W]    (fused form): sigmoid(7x7 convolution + bias)
+    const float* bias;     // [3]          (fused forms)
+    float* final_out;      // [B,3,H,W]    (fused forms): sigmoid(7x7 convolution + bias)
     int dbg;               // diagnostic (EAMM_COL7_DBG, tools/final_layer_bench.py; wrong results): 1 no patch DMA in the loop, 2 no tile epilogue
 };
 
-// FUSED (round 3): the horizontal gather of the seven dx taps, the bias and the sigmoid happen in the tile's epilogue instead
+// The fused forms: the horizontal gather of the seven dx taps, the bias and the sigmoid happen in the tile's epilogue instead
 // of in final_shift_sum_kernel -- the [B,H,W,32] partial products (65.5 MB written + read back per 8 frames at 256x256)
 // never leave the CU.  Output column x needs the partial columns x-3 .. x+3, so a workgroup owns whole ROWS of tiles and
-// walks them left to right: when tile T (columns c0 .. c0+15) is finished its partial products go to LDS (the patch stage
-// that has just been consumed), the outputs of columns c0-3 .. c0+12 are formed from them and from the last six partial
-// columns of tile T-1 (a 2 x 8 KB carry ring in the last 16 KB of LDS), and columns 10..15 become the next carry.
+// walks them left to right: when tile T (columns c0 .. c0+15) is finished its partial products go to LDS (the stage that has
+// just been consumed), the outputs of columns c0-3 .. c0+12 are formed from them and from the last six partial columns of
+// tile T-1 (a 2 x 8 KB carry ring in the last 16 KB of LDS), and columns 10..15 become the next carry.
 
 namespace {
 constexpr int PS = 21;                         // partial products per pixel kept: (dx, co); odd stride: conflict-free column walks
@@ -138,173 +147,176 @@ __device__ __forceinline__ void col7_pos_next(Col7Pos& s, const Col7Args& p, int
     col7_pos_decode<ROWS>(s, p);     // (the divisions: once per tile row / tile, not per DMA piece)
 }
 
-// The patch pieces a lane issues: piece j = wave + 8 i (i = 0..5, j < 44) covers patch pixels 8 j .. 8 j + 7, a lane's pixel
-// q = 8 j + lane / 8 = (row q / 16 - 3, column q % 16) of the tile and its 16-byte slot never change -- decoded once.
-struct Col7Lane {
-    int qr[6], qc[6], rel[6];
-};
-__device__ __forceinline__ void col7_lane_init(Col7Lane& L, const Col7Args& p, int wave, int lane) {
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        const int q = (wave + CWAVES * i) * 8 + (lane >> 3);
-        L.qr[i] = (q >> 4) - 3;
-        L.qc[i] = q & 15;
-        L.rel[i] = (L.qr[i] * p.W + L.qc[i]) * p.C + (((lane & 7) ^ ((q >> 1) & 7)) << 2);
-    }
+// The work split that goes with the walk: the units of this workgroup (its items first + k * gridDim.x, all chunks of each tile).
+template <bool ROWS>
+__device__ __forceinline__ int col7_units(const Col7Args& p, int chunks) {
+    const int first = blockIdx.x, grid = (int)gridDim.x;
+    const int items = ROWS ? p.B * p.tiles_y : p.tiles;
+    const int my_items = first < items ? (items - first + grid - 1) / grid : 0;
+    return my_items * (ROWS ? p.tiles_x : 1) * chunks;
 }
 
-template <bool FUSED>
-__global__ __launch_bounds__(CWAVES * 64) void conv_col7_kernel(const Col7Args p) {
-    constexpr int BK = CONV_BK;
-    constexpr int A_STAGE = CPIX * BK;             // floats (44 KiB)
-    constexpr int W_TAP = 32 * BK;                 // one (chunk, tap) weight tile
-    constexpr int A_PIECES = CPIX / 8;             // 44
-    extern __shared__ __attribute__((aligned(16))) float smem[];  // [cchunks*7][32][32] weights, [2][A_STAGE] patches, FUSED: [2][CARRY]
-    const int cchunks = p.C / BK;
+// ---------------------------------------------------------------------------------------------------------
+// The two fp32 kernels: LDS = [cchunks * 7][32 n][32 k] weights (swizzled), [2] patch stages of (16+6) x 16 pixels x 32 k
+// (swizzled), fused: [2][CARRY].
+namespace {
+constexpr int A_STAGE = CPIX * CONV_BK;        // floats of a patch stage (44 KiB)
+constexpr int W_TAP = 32 * CONV_BK;            // floats of one (chunk, tap) weight tile
+constexpr int A_PIECES = CPIX / 8;             // 44 DMA pieces of 8 pixels
+constexpr size_t col7_f32_lds_bytes(int cchunks, bool fused) {
+    return sizeof(float) * (cchunks * 7 * W_TAP + 2 * A_STAGE + (fused ? 2 * CARRY : 0));
+}
+static_assert(col7_f32_lds_bytes(CMAXCH, true) <= LDS_BUDGET, "LDS budget");
+}  // namespace
+
+// The fp32 patch stage.  The pieces a lane issues: piece j = wave + 8 i (i = 0..5, j < 44) covers patch pixels 8 j .. 8 j + 7, a
+// lane's pixel q = 8 j + lane / 8 = (row q / 16 - 3, column q % 16) of the tile and its 16-byte slot never change -- decoded once.
+struct Col7Patch {
+    int qr[6], qc[6], rel[6];
+    int wave;
+    float* As;             // [2][A_STAGE]
+    __amdgpu_buffer_rsrc_t rsi;
+    __device__ __forceinline__ Col7Patch(const Col7Args& p, float* stages, int wave_, int lane)
+        : wave(wave_), As(stages), rsi(__builtin_amdgcn_make_buffer_rsrc((void*)p.in, 0, p.in_bytes, 0x00020000)) {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            const int q = (wave + CWAVES * i) * 8 + (lane >> 3);
+            qr[i] = (q >> 4) - 3;
+            qc[i] = q & 15;
+            rel[i] = (qr[i] * p.W + qc[i]) * p.C + (((lane & 7) ^ ((q >> 1) & 7)) << 2);
+        }
+    }
+    // patch piece i of the unit at `pos` into stage st (nothing where the wave has no piece i); pixels outside the image are
+    // zero-filled by the hardware through the out-of-range offset
+    template <int i>
+    __device__ __forceinline__ void piece(const Col7Args& p, const Col7Pos& pos, int st) const {
+        const int j = wave + CWAVES * i;
+        if (j >= A_PIECES) return;
+        const int y = pos.ty0 + qr[i], x = pos.tx0 + qc[i];
+        const bool ok = ((unsigned)y < (unsigned)p.H) & ((unsigned)x < (unsigned)p.W);
+        const int base = ((pos.b * p.H + pos.ty0) * p.W + pos.tx0) * p.C + pos.cc * CONV_BK;       // wave-uniform
+        const unsigned off = ok ? (unsigned)(base + rel[i]) * 4u : 0xFFFFFFF0u;
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsi, (lds_ptr_t)(As + st * A_STAGE + j * (8 * CONV_BK)), 16, off, 0, 0, 0);
+    }
+};
+
+// The program of an fp32 column-patch workgroup around its MFMA body: all weights and the first patch in the prologue, then per
+// unit   unit(patch stage, the chunk's weights, next_piece)   -- the body issues next_piece(integral_constant<i>), i = 0..5,
+// between its MFMAs: piece i of the next unit's patch into the other stage --, on a tile's last chunk
+// finish(position, the stage just consumed, carry ring)   (every wave may still be reading that stage), and one barrier.
+template <bool ROWS, typename Unit, typename Finish>
+__device__ __forceinline__ void col7_walk_f32(const Col7Args& p, float* smem, int wave, int lane, Unit&& unit, Finish&& finish) {
+    const int cchunks = p.C / CONV_BK;
     float* const Ws = smem;
     float* const As = smem + cchunks * 7 * W_TAP;
     float* const Carry = As + 2 * A_STAGE;
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l31 = lane & 31, half = lane >> 5;
-
-    const __amdgpu_buffer_rsrc_t rsi = __builtin_amdgcn_make_buffer_rsrc((void*)p.in, 0, p.in_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.w_bytes, 0x00020000);
-    constexpr unsigned OOB = 0xFFFFFFF0u;
-
-    // unit u of this workgroup = (tile first + (u / cchunks) * gridDim.x, chunk u % cchunks); FUSED: the workgroup's items are
-    // tile ROWS (first + k * gridDim.x), each walked tile by tile from the left
-    const int first = blockIdx.x;
-    const int items = FUSED ? p.B * p.tiles_y : p.tiles;
-    const int my_items = first < items ? (items - first + (int)gridDim.x - 1) / (int)gridDim.x : 0;
-    const int units = my_items * (FUSED ? p.tiles_x : 1) * cchunks;
-    Col7Lane L;
-    col7_lane_init(L, p, wave, lane);
-    // patch piece i (j = wave + 8 i) of the unit at `pos` into stage st
-    auto dma_patch_piece = [&](auto ic, const Col7Pos& pos, int st) {
-        constexpr int i = decltype(ic)::value;
-        const int j = wave + CWAVES * i;
-        const int y = pos.ty0 + L.qr[i], x = pos.tx0 + L.qc[i];
-        const bool ok = ((unsigned)y < (unsigned)p.H) & ((unsigned)x < (unsigned)p.W);
-        const int base = ((pos.b * p.H + pos.ty0) * p.W + pos.tx0) * p.C + pos.cc * BK;       // wave-uniform
-        const unsigned off = ok ? (unsigned)(base + L.rel[i]) * 4u : OOB;
-        float* dst = As + st * A_STAGE + j * (8 * BK);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsi, (lds_ptr_t)dst, 16, off, 0, 0, 0);
-    };
-
+    const int units = col7_units<ROWS>(p, cchunks);
     if (units == 0) return;
-    // ---- prologue: all weights + the first patch
+
+    const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.w_bytes, 0x00020000);
+    const Col7Patch patch(p, As, wave, lane);
     for (int j = wave; j < cchunks * 7 * 4; j += CWAVES) {   // 1 KiB pieces of the weight tensor
-        const unsigned off = (unsigned)(j * (8 * BK) + lane * 4) * 4u;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (lds_ptr_t)(Ws + j * (8 * BK)), 16, off, 0, 0, 0);
+        const unsigned off = (unsigned)(j * (8 * CONV_BK) + lane * 4) * 4u;
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (lds_ptr_t)(Ws + j * (8 * CONV_BK)), 16, off, 0, 0, 0);
     }
-    Col7Pos cur{0, 0, first, 0, 0, 0};
-    col7_pos_decode<FUSED>(cur, p);
-    static_for<6>([&](auto ic) {
-        if (wave + CWAVES * decltype(ic)::value < A_PIECES) dma_patch_piece(ic, cur, 0);
-    });
+    Col7Pos cur{0, 0, (int)blockIdx.x, 0, 0, 0};
+    col7_pos_decode<ROWS>(cur, p);
+    static_for<6>([&](auto ic) { patch.template piece<decltype(ic)::value>(p, cur, 0); });
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
-    f32x16 acc;
-    static_for<16>([&](auto rc) { acc[decltype(rc)::value] = 0.f; });
-
-    // this lane's pixel inside the tile: wave w owns rows 2w, 2w+1
-    const int trow = 2 * wave + (l31 >> 4), tcol = l31 & 15;
-    const int idx0 = trow * CT + tcol;                                 // patch pixel of tap 0 (dy = -3)
-    const int a_off = idx0 * BK + ((half ^ ((idx0 >> 1) & 7)) << 2);   // + 8*s for K step s via XOR; + tap * CT * BK
-    const int b_off = l31 * BK + ((half ^ ((l31 >> 1) & 7)) << 2);
-
-    float bias_r[3] = {0.f, 0.f, 0.f};
-    if constexpr (FUSED) {
-        bias_r[0] = p.bias[0]; bias_r[1] = p.bias[1]; bias_r[2] = p.bias[2];
-    }
+    const bool dma = !(p.dbg & 1), epilogue = !(p.dbg & 2);
     for (int u = 0; u < units; ++u) {
         const int st = u & 1;
-        const bool more = u + 1 < units;
-        const float* a_stage = As + st * A_STAGE;
-        const int b = cur.b, ty0 = cur.ty0, tx0 = cur.tx0, cc = cur.cc;
+        const bool more = dma && u + 1 < units;
         Col7Pos nxt = cur;
-        col7_pos_next<FUSED>(nxt, p, cchunks, (int)gridDim.x);
-        const float* w_stage = Ws + cc * 7 * W_TAP;
-        // 7 taps x 4 K steps x 4 MFMAs; the next unit's patch pieces (wave, wave+8, ...: 5 or 6 per wave) ride along
-        f32x4 a[2], bb[2];
-        auto fetch = [&](auto tc, auto sc_, int buf) {
-            constexpr int t = decltype(tc)::value, s = decltype(sc_)::value;
-            a[buf] = *reinterpret_cast<const f32x4*>(a_stage + ((a_off ^ (8 * s)) + t * CT * BK));
-            bb[buf] = *reinterpret_cast<const f32x4*>(w_stage + ((b_off ^ (8 * s)) + t * W_TAP));
-        };
-        fetch(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, 0);
-        static_for<28>([&](auto gc) {
-            constexpr int g = decltype(gc)::value;       // (tap, K step) index
-            if constexpr (g + 1 < 28)
-                fetch(std::integral_constant<int, (g + 1) / 4>{}, std::integral_constant<int, (g + 1) % 4>{}, (g + 1) & 1);
-            __builtin_amdgcn_sched_barrier(0);
-            static_for<4>([&](auto qc) {
-                constexpr int q = decltype(qc)::value;
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[g & 1][q], bb[g & 1][q], acc, 0, 0, 0);
-            });
-            if constexpr (g % 4 == 1 && g / 4 < 6) {     // one patch piece after every 16 MFMAs, 6 slots
-                __builtin_amdgcn_sched_barrier(0);
-                if (more && wave + CWAVES * (g / 4) < A_PIECES && !(p.dbg & 1)) dma_patch_piece(std::integral_constant<int, g / 4>{}, nxt, st ^ 1);
-                __builtin_amdgcn_sched_barrier(0);
-            }
+        col7_pos_next<ROWS>(nxt, p, cchunks, (int)gridDim.x);
+        unit(As + st * A_STAGE, Ws + cur.cc * 7 * W_TAP, [&](auto ic) {
+            if (more) patch.template piece<decltype(ic)::value>(p, nxt, st ^ 1);
         });
-        if (cc == cchunks - 1 && !(p.dbg & 2)) {
-            if constexpr (!FUSED) {
-                // epilogue of the tile: lanes 0..31 of a wave hold the 32 channels of one pixel -> 128-byte rows
-                static_for<16>([&](auto rc) {
-                    constexpr int r = decltype(rc)::value;
-                    const int m = (r & 3) + 8 * (r >> 2) + 4 * half;   // pixel of the wave's 32: row m / 16, column m % 16
-                    const int y = ty0 + 2 * wave + (m >> 4), x = tx0 + (m & 15);
-                    if (y < p.H && x < p.W) p.out[((size_t)(b * p.H + y) * p.W + x) * 32 + l31] = acc[r];
-                    acc[r] = 0.f;
-                });
-            } else {
-                // every wave is done with this unit's patch stage (the next unit reads the other one; its refill starts inside
-                // the next unit): it becomes the scratch for the tile's partial products P[row][column][dx*3 + co]
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __syncthreads();
-                float* const scratch = As + st * A_STAGE;
-                static_for<16>([&](auto rc) {
-                    constexpr int r = decltype(rc)::value;
-                    const int m = (r & 3) + 8 * (r >> 2) + 4 * half;
-                    const int row = 2 * wave + (m >> 4), col = m & 15;
-                    if (l31 < PS) scratch[(row * CT + col) * PS + l31] = acc[r];
-                    acc[r] = 0.f;
-                });
-                __syncthreads();
-                col7_gather_tile(p, scratch, Carry, bias_r, b, ty0, tx0, tid);
-            }
-        }
+        if (cur.cc == cchunks - 1 && epilogue) finish(cur, As + st * A_STAGE, Carry);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         cur = nxt;
     }
 }
 
+// The plain form: per unit 7 taps x 4 K steps x 4 MFMAs 32x32x2 (N = 21 padded to 32); a finished tile's partial products go
+// to p.out for final_shift_sum_kernel.
+__global__ __launch_bounds__(CWAVES * 64) void conv_col7_kernel(const Col7Args p) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l31 = lane & 31, half = lane >> 5;
+
+    f32x16 acc;
+    static_for<16>([&](auto rc) { acc[decltype(rc)::value] = 0.f; });
+
+    // this lane's pixel inside the tile: wave w owns rows 2w, 2w+1
+    const int trow = 2 * wave + (l31 >> 4), tcol = l31 & 15;
+    const int idx0 = trow * CT + tcol;                                      // patch pixel of tap 0 (dy = -3)
+    const int a_off = idx0 * CONV_BK + ((half ^ ((idx0 >> 1) & 7)) << 2);   // + 8*s for K step s via XOR; + tap * CT * BK
+    const int b_off = l31 * CONV_BK + ((half ^ ((l31 >> 1) & 7)) << 2);
+
+    col7_walk_f32<false>(
+        p, smem, wave, lane,
+        [&](const float* a_stage, const float* w_stage, auto&& next_piece) {
+            // the next unit's patch pieces (wave, wave+8, ...: 5 or 6 per wave) ride along
+            f32x4 a[2], bb[2];
+            auto fetch = [&](auto tc, auto sc_, int buf) {
+                constexpr int t = decltype(tc)::value, s = decltype(sc_)::value;
+                a[buf] = *reinterpret_cast<const f32x4*>(a_stage + ((a_off ^ (8 * s)) + t * CT * CONV_BK));
+                bb[buf] = *reinterpret_cast<const f32x4*>(w_stage + ((b_off ^ (8 * s)) + t * W_TAP));
+            };
+            fetch(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, 0);
+            static_for<28>([&](auto gc) {
+                constexpr int g = decltype(gc)::value;       // (tap, K step) index
+                if constexpr (g + 1 < 28)
+                    fetch(std::integral_constant<int, (g + 1) / 4>{}, std::integral_constant<int, (g + 1) % 4>{}, (g + 1) & 1);
+                __builtin_amdgcn_sched_barrier(0);
+                static_for<4>([&](auto qc) {
+                    constexpr int q = decltype(qc)::value;
+                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[g & 1][q], bb[g & 1][q], acc, 0, 0, 0);
+                });
+                if constexpr (g % 4 == 1 && g / 4 < 6) {     // one patch piece after every 16 MFMAs, 6 slots
+                    __builtin_amdgcn_sched_barrier(0);
+                    next_piece(std::integral_constant<int, g / 4>{});
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            });
+        },
+        [&](const Col7Pos& pos, float*, float*) {
+            // lanes 0..31 of a wave hold the 32 channels of one pixel -> 128-byte rows
+            static_for<16>([&](auto rc) {
+                constexpr int r = decltype(rc)::value;
+                const int m = (r & 3) + 8 * (r >> 2) + 4 * half;   // pixel of the wave's 32: row m / 16, column m % 16
+                const int y = pos.ty0 + 2 * wave + (m >> 4), x = pos.tx0 + (m & 15);
+                if (y < p.H && x < p.W) p.out[((size_t)(pos.b * p.H + y) * p.W + x) * 32 + l31] = acc[r];
+                acc[r] = 0.f;
+            });
+        });
+}
+
 // ---------------------------------------------------------------------------------------------------------
-// Round 4: the fused final layer on the MULTI-BLOCK MFMA v_mfma_f32_4x4x1_16b_f32.  N = (dx, co) = 21 of a
-// 32-wide tile multiplies zeros in a third of its matrix-pipe time; the 4x4x1 form has an N granule of FOUR: with the
-// A-block broadcast (cbsz = 4, abid = g) one instruction is D[i][lane p] += W[n = 4 g + i][k] * X[pixel p][k] -- 64 pixels
+// The fused fp32 form on the MULTI-BLOCK MFMA v_mfma_f32_4x4x1_16b_f32.  N = (dx, co) = 21 of a 32-wide tile multiplies zeros in
+// a third of its matrix-pipe time (the 32x32x2 form of round 3); the 4x4x1 form has an N granule of FOUR: with the A-block
+// broadcast (cbsz = 4, abid = g) one instruction is D[i][lane p] += W[n = 4 g + i][k] * X[pixel p][k] -- 64 pixels
 // (the lanes) x 4 columns x one k in 8 cycles, the same 64 FLOP / cycle / SIMD as the 32x32x2 form -- so six groups g cover
 // n = 0..23: 24 / 21 = 14 % padding instead of 52 %, 0.75 x the matrix-pipe cycles.  A wave owns 64 pixels (4 rows of the
 // 16x16 tile) and three of the six groups (waves 0-3: n 0..11, waves 4-7: n 12..23); per (tap, 16-byte slot of the channel
 // chunk) it reads ONE ds_read_b128 of the patch (lane = pixel: its 4 k values) and ONE of the weights (lane = n: W[n][4 k]),
-// and issues 4 k x 3 groups = 12 MFMAs on three rotating accumulators.  Same LDS images (weights [chunk][tap][32 n][32 k]
-// swizzled, patch (16+6) x 16 pixels x 32 k swizzled), same DMA pipeline, same tile walk, same gather epilogue as above.
-template <int NH, int EVERY, typename DmaPiece>
+// and issues 4 k x 3 groups = 12 MFMAs on three rotating accumulators.
+// (One patch piece of the next unit per tap, six of the seven taps: issuing them twice as densely at the start of the unit
+// measured the same -- 210.4 vs 213.4 us at 8 frames, 3915 vs 3912 frames/s in the pipeline.)
+template <int NH, typename NextPiece>
 __device__ __forceinline__ void col7q_unit(const float* a_stage, const float* w_stage, int a_off, int b_off, f32x4 (&acc)[3],
-                                           bool more, int wave, const Col7Pos& nxt, int st, int dbg, const DmaPiece& dma_patch_piece) {
-    constexpr int BK = CONV_BK;
-    constexpr int W_TAP = 32 * BK;
-    constexpr int A_PIECES = CPIX / 8;
+                                           NextPiece&& next_piece) {
+    constexpr int EVERY = 8;                         // (tap, slot) groups per patch piece of the next unit
     f32x4 xa[2], wb[2];
     auto fetch = [&](auto tc, auto sc_, int buf) {
         constexpr int t = decltype(tc)::value, sl = decltype(sc_)::value;
-        xa[buf] = *reinterpret_cast<const f32x4*>(a_stage + ((a_off ^ (4 * sl)) + t * CT * BK));
+        xa[buf] = *reinterpret_cast<const f32x4*>(a_stage + ((a_off ^ (4 * sl)) + t * CT * CONV_BK));
         wb[buf] = *reinterpret_cast<const f32x4*>(w_stage + ((b_off ^ (4 * sl)) + t * W_TAP));
     };
     fetch(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, 0);
@@ -320,94 +332,43 @@ __device__ __forceinline__ void col7q_unit(const float* a_stage, const float* w_
             acc[1] = __builtin_amdgcn_mfma_f32_4x4x1f32(wb[g & 1][q], xa[g & 1][q], acc[1], 4, 3 * NH + 1, 0);
             acc[2] = __builtin_amdgcn_mfma_f32_4x4x1f32(wb[g & 1][q], xa[g & 1][q], acc[2], 4, 3 * NH + 2, 0);
         });
-        if constexpr (g % EVERY == EVERY / 2 - 1 && g / EVERY < 6) {     // one patch piece of the next unit every EVERY groups, 6 slots
+        if constexpr (g % EVERY == EVERY / 2 - 1 && g / EVERY < 6) {
             __builtin_amdgcn_sched_barrier(0);
-            if (more && wave + CWAVES * (g / EVERY) < A_PIECES && !(dbg & 1)) dma_patch_piece(std::integral_constant<int, g / EVERY>{}, nxt, st ^ 1);
+            next_piece(std::integral_constant<int, g / EVERY>{});
             __builtin_amdgcn_sched_barrier(0);
         }
     });
 }
 
-template <int EVERY>
 __global__ __launch_bounds__(CWAVES * 64) void conv_col7q_kernel(const Col7Args p) {
-    constexpr int BK = CONV_BK;
-    constexpr int A_STAGE = CPIX * BK;             // floats (44 KiB)
-    constexpr int W_TAP = 32 * BK;
-    constexpr int A_PIECES = CPIX / 8;             // 44
-    extern __shared__ __attribute__((aligned(16))) float smem[];  // [cchunks*7][32][32] weights, [2][A_STAGE] patches, [2][CARRY]
-    const int cchunks = p.C / BK;
-    float* const Ws = smem;
-    float* const As = smem + cchunks * 7 * W_TAP;
-    float* const Carry = As + 2 * A_STAGE;
-
+    extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int pg = wave & 3, nh = wave >> 2;       // pixel group (rows 4 pg .. 4 pg + 3), half of the six n groups
-
-    const __amdgpu_buffer_rsrc_t rsi = __builtin_amdgcn_make_buffer_rsrc((void*)p.in, 0, p.in_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.w_bytes, 0x00020000);
-    constexpr unsigned OOB = 0xFFFFFFF0u;
-
-    const int first = blockIdx.x;
-    const int items = p.B * p.tiles_y;             // tile ROWS, each walked tile by tile from the left
-    const int my_items = first < items ? (items - first + (int)gridDim.x - 1) / (int)gridDim.x : 0;
-    const int units = my_items * p.tiles_x * cchunks;
-    Col7Lane L;
-    col7_lane_init(L, p, wave, lane);
-    // patch piece i (j = wave + 8 i) of the unit at `pos` into stage st
-    auto dma_patch_piece = [&](auto ic, const Col7Pos& pos, int st) {
-        constexpr int i = decltype(ic)::value;
-        const int j = wave + CWAVES * i;
-        const int y = pos.ty0 + L.qr[i], x = pos.tx0 + L.qc[i];
-        const bool ok = ((unsigned)y < (unsigned)p.H) & ((unsigned)x < (unsigned)p.W);
-        const int base = ((pos.b * p.H + pos.ty0) * p.W + pos.tx0) * p.C + pos.cc * BK;       // wave-uniform
-        const unsigned off = ok ? (unsigned)(base + L.rel[i]) * 4u : OOB;
-        float* dst = As + st * A_STAGE + j * (8 * BK);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsi, (lds_ptr_t)dst, 16, off, 0, 0, 0);
-    };
-
-    if (units == 0) return;
-    for (int j = wave; j < cchunks * 7 * 4; j += CWAVES) {   // 1 KiB pieces of the weight tensor
-        const unsigned off = (unsigned)(j * (8 * BK) + lane * 4) * 4u;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (lds_ptr_t)(Ws + j * (8 * BK)), 16, off, 0, 0, 0);
-    }
-    Col7Pos cur{0, 0, first, 0, 0, 0};
-    col7_pos_decode<true>(cur, p);
-    static_for<6>([&](auto ic) {
-        if (wave + CWAVES * decltype(ic)::value < A_PIECES) dma_patch_piece(ic, cur, 0);
-    });
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
 
     f32x4 acc[3];
     static_for<3>([&](auto gc) { acc[decltype(gc)::value] = f32x4{0.f, 0.f, 0.f, 0.f}; });
 
     // this lane's pixel inside the tile (srcB): row 4 pg + lane / 16, column lane % 16; tap 0 (dy = -3) is the same patch pixel
     const int idx0 = (4 * pg + (lane >> 4)) * CT + (lane & 15);
-    const int a_off = idx0 * BK + (((idx0 >> 1) & 7) << 2);            // ^ 4 * slot; + tap * CT * BK (keeps (idx >> 1) & 7)
+    const int a_off = idx0 * CONV_BK + (((idx0 >> 1) & 7) << 2);       // ^ 4 * slot; + tap * CT * BK (keeps (idx >> 1) & 7)
     // this lane's weight row (srcA): n = lane (only lanes 4 g .. 4 g + 3 of the broadcast block are read: n < 24)
     const int nrow = lane & 31;
-    const int b_off = nrow * BK + (((nrow >> 1) & 7) << 2);
-    float bias_r[3] = {p.bias[0], p.bias[1], p.bias[2]};
+    const int b_off = nrow * CONV_BK + (((nrow >> 1) & 7) << 2);
+    const float bias_r[3] = {p.bias[0], p.bias[1], p.bias[2]};
 
-    for (int u = 0; u < units; ++u) {
-        const int st = u & 1;
-        const bool more = u + 1 < units;
-        const float* a_stage = As + st * A_STAGE;
-        const int b = cur.b, ty0 = cur.ty0, tx0 = cur.tx0, cc = cur.cc;
-        Col7Pos nxt = cur;
-        col7_pos_next<true>(nxt, p, cchunks, (int)gridDim.x);
-        const float* w_stage = Ws + cc * 7 * W_TAP;
-        if (nh == 0)
-            col7q_unit<0, EVERY>(a_stage, w_stage, a_off, b_off, acc, more, wave, nxt, st, p.dbg, dma_patch_piece);
-        else
-            col7q_unit<1, EVERY>(a_stage, w_stage, a_off, b_off, acc, more, wave, nxt, st, p.dbg, dma_patch_piece);
-        if (cc == cchunks - 1 && !(p.dbg & 2)) {
+    col7_walk_f32<true>(
+        p, smem, wave, lane,
+        [&](const float* a_stage, const float* w_stage, auto&& next_piece) {
+            if (nh == 0) col7q_unit<0>(a_stage, w_stage, a_off, b_off, acc, next_piece);
+            else col7q_unit<1>(a_stage, w_stage, a_off, b_off, acc, next_piece);
+        },
+        [&](const Col7Pos& pos, float* scratch, float* Carry) {
+            // once every wave is done with the stage it takes the tile's partial products P[row][column][n], n = 12 nh + 4 g + i
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
-            float* const scratch = As + st * A_STAGE;     // the patch stage every wave has just finished reading
-            float* dst = scratch + idx0 * PS + 12 * nh;   // P[row][column][n], n = 12 nh + 4 g + i
+            float* dst = scratch + idx0 * PS + 12 * nh;
             static_for<3>([&](auto gc) {
                 constexpr int g = decltype(gc)::value;
                 static_for<4>([&](auto ic) {
@@ -417,24 +378,20 @@ __global__ __launch_bounds__(CWAVES * 64) void conv_col7q_kernel(const Col7Args 
                 });
             });
             __syncthreads();
-            col7_gather_tile(p, scratch, Carry, bias_r, b, ty0, tx0, tid);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        cur = nxt;
-    }
+            col7_gather_tile(p, scratch, Carry, bias_r, pos.b, pos.ty0, pos.tx0, tid);
+        });
 }
 
 // ---------------------------------------------------------------------------------------------------------
 // The fused final layer with SPLIT-BF16 products (as SPLIT of wino4_gemm_kernel and FORM 1 of conv_patch_poly_kernel): every fp32
-// operand is the exact sum of three bf16 values taken by truncation, a = a1 + a2 + a3, and a * b is the six products a1b3, a3b1,
-// a2b1, a1b1, a2b2, a1b2 on v_mfma_f32_32x32x16_bf16 with fp32 accumulation (the dropped terms are <= 2^-24 relative).  Rows are
-// the wave's 32 pixels (2 tile rows x 16 columns, as conv_col7_kernel<true>), columns n = (dx, co) padded from 21 to 32: 7 taps x
-// 6 MFMAs of 32 cycles per 16 channels against 7 x 16 x 12 / 2 of 9.3 in the 4x4x1 form.
+// operand is the exact sum of three bf16 values taken by truncation, a = a1 + a2 + a3, and a * b is the six terms of conv_common.h's
+// term table on v_mfma_f32_32x32x16_bf16 with fp32 accumulation.  Rows are the wave's 32 pixels (2 tile rows x 16 columns, as
+// conv_col7_kernel), columns n = (dx, co) padded from 21 to 32: 7 taps x 6 MFMAs of 32 cycles per 16 channels against
+// 7 x 16 x 12 / 2 of 9.3 in the 4x4x1 form.
 //   * A lane's seven vertical taps are seven different patch pixels, so splitting the fragment after the LDS read (as the other two
 //     kernels do) would split every patch value seven times.  Here a value is split ONCE: the DMA lands fp32 in LDS, 16 channels
 //     of the 22 x 16 patch per unit (22 pieces of 1 KiB, one patch row each), and each wave splits the pieces IT fetched
-//     (wino4_split3) into a plane image [plane][k octet][pixel][8 bf16]: tap t is still the same image a constant 256 B further on,
+//     (split3_bf16) into a plane image [plane][k octet][pixel][8 bf16]: tap t is still the same image a constant 256 B further on,
 //     a wave's 32 pixels of a (tap, plane, octet) are 512 contiguous bytes (one conflict-free ds_read_b128), and because a wave
 //     reads back only its own DMA no barrier stands between landing and split, only the wave's vmcnt.
 //   * The weights come split from the host (col7_pack_split_host): [16-channel group][tap][plane][k octet][21 rows][8 bf16], whole
@@ -443,7 +400,7 @@ __global__ __launch_bounds__(CWAVES * 64) void conv_col7q_kernel(const Col7Args 
 //     MFMAs read plane stage u & 1 while the DMA of unit u + 1 lands in the fp32 stage; then the wave splits its pieces into plane
 //     stage (u + 1) & 1, whose readers finished before the previous barrier: one barrier per unit.  The finished tile's partial
 //     products go to the plane stage just consumed.
-// Tile walk, patch addressing with hardware zero fill, carry ring and gather epilogue are the fused forms' above.
+// Work split, tile walk, carry ring and gather epilogue are shared with the kernels above; the staging is its own.
 namespace {
 constexpr int SG = 16;                                    // channels per unit
 constexpr int S_WBLK = 2 * PS * 16;                       // bytes of a (group, tap, plane) weight block: [octet][21 rows][8 bf16]
@@ -455,7 +412,7 @@ constexpr int S_OCT = CPIX * 16;                          // bytes of a (plane, 
 constexpr int S_PLANE = 2 * S_OCT;
 constexpr int S_PSTAGE = 3 * S_PLANE;                     // a plane stage (33 792 B)
 constexpr int S_LDS = S_WBYTES + S_F32 + 2 * S_PSTAGE + 2 * CARRY * 4;
-static_assert(S_LDS <= 160 * 1024, "LDS budget");
+static_assert(S_LDS <= LDS_BUDGET, "LDS budget");
 static_assert(CT * CT * PS * 4 <= S_PSTAGE, "the tile's partial products fit a consumed plane stage");
 static_assert(CPR <= 3 * CWAVES, "at most three pieces per wave");
 }  // namespace
@@ -477,10 +434,7 @@ __global__ __launch_bounds__(CWAVES * 64) void conv_col7b_kernel(const Col7Args 
     const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.w_bytes, 0x00020000);
     constexpr unsigned OOB = 0xFFFFFFF0u;
 
-    const int first = blockIdx.x;
-    const int items = p.B * p.tiles_y;             // tile ROWS, each walked tile by tile from the left
-    const int my_items = first < items ? (items - first + (int)gridDim.x - 1) / (int)gridDim.x : 0;
-    const int units = my_items * p.tiles_x * groups;
+    const int units = col7_units<true>(p, groups);
     if (units == 0) return;
 
     // Patch piece i of this wave = patch row j = wave + 8 i (j < 22): DMA lane L lands at byte 16 L of the piece and fetches
@@ -507,7 +461,7 @@ __global__ __launch_bounds__(CWAVES * 64) void conv_col7b_kernel(const Col7Args 
                 const char* src = Fs + j * 1024 + l31 * 16;
                 const f32x4 x0 = *reinterpret_cast<const f32x4*>(src), x1 = *reinterpret_cast<const f32x4*>(src + 512);
                 u32x4 pl[3];
-                wino4_split3(x0, x1, pl);
+                split3_bf16(x0, x1, pl);
                 char* d = dst + (l31 >> 4) * S_OCT + (j * CT + (l31 & 15)) * 16;
                 static_for<3>([&](auto kc) { *reinterpret_cast<u32x4*>(d + decltype(kc)::value * S_PLANE) = pl[decltype(kc)::value]; });
             }
@@ -518,7 +472,7 @@ __global__ __launch_bounds__(CWAVES * 64) void conv_col7b_kernel(const Col7Args 
     for (int j = wave; j < groups * S_WGROUP / 1024 + 1; j += CWAVES)    // 1 KiB pieces; the image is padded to whole pieces
         if (j * 1024 < (int)p.w_bytes)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (lds_ptr_t)(Ws + j * 1024), 16, (unsigned)(j * 1024 + lane * 16), 0, 0, 0);
-    Col7Pos cur{0, 0, first, 0, 0, 0};
+    Col7Pos cur{0, 0, (int)blockIdx.x, 0, 0, 0};
     col7_pos_decode<true>(cur, p);
     static_for<3>([&](auto ic) {
         if (wave + CWAVES * decltype(ic)::value < S_ROWS) dma_patch_piece(ic, cur);
@@ -559,10 +513,8 @@ __global__ __launch_bounds__(CWAVES * 64) void conv_col7b_kernel(const Col7Args 
             constexpr int t = decltype(tc)::value;
             if constexpr (t + 1 < 7) fetch(std::integral_constant<int, t + 1>{}, (t + 1) & 1);
             __builtin_amdgcn_sched_barrier(0);
-            static_for<6>([&](auto mc) {   // a1b3 | a3b1 a2b1 a1b1 | a2b2 a1b2
-                constexpr int m = decltype(mc)::value;
-                constexpr int pa = m == 0 ? 0 : m == 1 ? 2 : m == 2 ? 1 : m == 3 ? 0 : m == 4 ? 1 : 0;
-                constexpr int pb = m == 0 ? 2 : m <= 3 ? 0 : 1;
+            static_for<SPLIT_TERMS>([&](auto mc) {   // a1b3 | a3b1 a2b1 a1b1 | a2b2 a1b2
+                constexpr int pa = SPLIT_TERM_A[decltype(mc)::value], pb = SPLIT_TERM_B[decltype(mc)::value];
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, ap[t & 1][pa]),
                                                               __builtin_bit_cast(bf16x8_t, wp[t & 1][pb]), acc, 0, 0, 0);
             });
@@ -595,7 +547,6 @@ __global__ __launch_bounds__(CWAVES * 64) void conv_col7b_kernel(const Col7Args 
         cur = nxt;
     }
 }
-
 // ---------------------------------------------------------------------------------------------------------
 // Same tile geometry for the row-split flow head (7x1 over N = 7 x (K+2) = 84 of 96, two concatenated inputs, 128 input
 // channels): the weights ([4][7][96][32] = 336 KiB) do not fit, so they stream one (chunk, tap) tile per barrier interval
@@ -757,40 +708,32 @@ hipError_t conv_col7s_launch(const float* in0, int C0, const float* in1, int C1,
 size_t col7_split_packed_elems(int cin_packed) { return ((size_t)(cin_packed / SG) * S_WGROUP + 1023) / 1024 * 256; }
 
 // The row-split 7x1 weights w [Cout <= 21][Cin][7] (to_rowsplit of the folded 7x7 filter: the fp32-ROUNDED values the fp32 image is
-// packed from) as three bf16 planes by truncation, w1 = top 16 bits of w, w2 = top 16 bits of w - w1, w3 = w - w1 - w2 (both
-// differences exact), so w1 + w2 + w3 is that float exactly.  Image [16-channel group][tap][plane][k octet][21 rows][8]: lane
+// packed from) as three bf16 planes by truncation (split3_bf16_host), so w1 + w2 + w3 is that float exactly.  Image [16-channel group][tap][plane][k octet][21 rows][8]: lane
 // (row n, octet h) of conv_col7b_kernel reads the group's channels 8 h .. 8 h + 7 with one ds_read_b128.
 void col7_pack_split_host(const float* w, int Cout, int Cin, const int* cin_map, int cin_packed, uint16_t* dst) {
     const size_t total = 2 * col7_split_packed_elems(cin_packed);
     for (size_t i = 0; i < total; ++i) dst[i] = 0;
-    auto bits = [](float f) { uint32_t b; memcpy(&b, &f, 4); return b; };
-    auto top = [](uint32_t b) { b &= 0xFFFF0000u; float f; memcpy(&f, &b, 4); return f; };
     for (int n = 0; n < Cout && n < PS; ++n)
         for (int cp = 0; cp < cin_packed; ++cp) {
             const int c = cin_map ? cin_map[cp] : cp;
             if (c < 0 || c >= Cin) continue;
             for (int t = 0; t < 7; ++t) {
-                const float u = w[((size_t)n * Cin + c) * 7 + t];
-                const float r = u - top(bits(u)), r2 = r - top(bits(r));
+                uint16_t pl[3];
+                split3_bf16_host(w[((size_t)n * Cin + c) * 7 + t], pl);
                 const int g = cp / SG, h = (cp % SG) >> 3, e = cp & 7;
                 uint16_t* blk = dst + ((size_t)(g * 7 + t) * 3 * S_WBLK + h * (PS * 16) + n * 16) / 2 + e;
-                blk[0] = (uint16_t)(bits(u) >> 16);
-                blk[S_WBLK / 2] = (uint16_t)(bits(r) >> 16);
-                blk[S_WBLK] = (uint16_t)(bits(r2) >> 16);
+                for (int k = 0; k < 3; ++k) blk[k * (S_WBLK / 2)] = pl[k];
             }
         }
 }
 
-static hipError_t col7_launch_impl(const float* in, int C, int B, int H, int W, const float* w_swizzled, float* out, const float* bias,
-                                   float* final_out, hipStream_t stream, const float* w_split = nullptr) {
-    const bool fused = final_out != nullptr;
+// What the final layer's launches have in common: the shape checks and every argument but the weights' and the outputs'.
+static hipError_t col7_fill_args(Col7Args& a, const float* in, int C, int B, int H, int W) {
     if (C % CONV_BK || C / CONV_BK > CMAXCH || C < CONV_BK) return hipErrorInvalidValue;
-    Col7Args a{};
-    a.in = in;
-    const size_t ib = (size_t)B * H * W * C * 4, wb = (size_t)(C / CONV_BK) * 7 * 32 * CONV_BK * 4;
+    const size_t ib = (size_t)B * H * W * C * 4;
     if (ib >= 0xFFFFFFF0ull) return hipErrorInvalidValue;
+    a.in = in;
     a.in_bytes = (unsigned)ib;
-    a.w_bytes = (unsigned)wb;
     a.C = C;
     a.B = B;
     a.H = H;
@@ -798,66 +741,57 @@ static hipError_t col7_launch_impl(const float* in, int C, int B, int H, int W, 
     a.tiles_x = (W + CT - 1) / CT;
     a.tiles_y = (H + CT - 1) / CT;
     a.tiles = B * a.tiles_x * a.tiles_y;
-    a.w = w_swizzled;
-    a.out = out;
-    a.bias = bias;
-    a.final_out = final_out;
 #ifdef EAMM_EXPERIMENTS   // diagnostic builds only (make EXPERIMENTS=1): the product library never drops the DMA / the epilogue
     static const int dbg = (int)knob_int("EAMM_COL7_DBG", 0);
     a.dbg = dbg;
-#else
-    a.dbg = 0;
 #endif
-    const size_t lds = wb + sizeof(float) * (2 * CPIX * CONV_BK + (fused ? 2 * CT * 6 * 21 : 0));
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    static lds_once_mask configured{0}, configured_fused{0};
-    if (hipError_t e = fused ? ensure_dynamic_lds(conv_col7_kernel<true>, 160 * 1024, &configured_fused)
-                             : ensure_dynamic_lds(conv_col7_kernel<false>, 160 * 1024, &configured);
-        e != hipSuccess)
-        return e;
+    return hipSuccess;
+}
+
+// One persistent workgroup per CU at the most (LDS: one workgroup per CU is resident), over `items` tiles or tile rows.
+template <typename K>
+static hipError_t col7_launch_kernel(K kern, lds_once_mask* configured, size_t lds, int items, const Col7Args& a, hipStream_t stream) {
+    if (hipError_t e = ensure_dynamic_lds(kern, LDS_BUDGET, configured); e != hipSuccess) return e;
     int dev = 0, cus = 256;
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const int blocks = std::min(fused ? B * a.tiles_y : a.tiles, cus);
-    if (fused && w_split) {   // the split-bf16 product form on the layer's three-plane image
-        static lds_once_mask configured_b{0};
-        a.w = w_split;
-        a.w_bytes = (unsigned)(col7_split_packed_elems(C) * 4);
-        // The layer counts what its fp32 form issues (N = 24), whatever the product form: bench.py prices `stage_roofline.final`
-        // against the fp32 matrix peak, and the fp32-equivalent of the N = 32 columns issued here exceeded it (1.02 of the peak).
-        note_mfma_flops(2.0 * a.tiles * (CT * CT) * 7.0 * 24 * C);
-        if (hipError_t e = ensure_dynamic_lds(conv_col7b_kernel, S_LDS, &configured_b); e != hipSuccess) return e;
-        hipLaunchKernelGGL(conv_col7b_kernel, dim3(blocks), dim3(CWAVES * 64), S_LDS, stream, a);
-        return hipGetLastError();
-    }
-    // EAMM_FINAL_MFMA4 = 0: the fused form on the 32x32x2 MFMA with N padded to 32 (round 3); default: the 4x4x1 multi-block form
-    static const bool mfma4 = knob_int("EAMM_FINAL_MFMA4", 1) != 0;
-    if (fused && mfma4) {
-        // (one patch piece of the next unit per tap, six of the seven taps: issuing them twice as densely at the start of the
-        // unit measured the same -- 210.4 vs 213.4 us at 8 frames, 3915 vs 3912 frames/s in the pipeline)
-        static lds_once_mask configured_q{0};
-        note_mfma_flops(2.0 * a.tiles * (CT * CT) * 7.0 * 24 * C);      // N = 24 columns issued
-        if (hipError_t e = ensure_dynamic_lds(conv_col7q_kernel<8>, 160 * 1024, &configured_q); e != hipSuccess) return e;
-        hipLaunchKernelGGL(conv_col7q_kernel<8>, dim3(blocks), dim3(CWAVES * 64), lds, stream, a);
-        return hipGetLastError();
-    }
-    note_mfma_flops(2.0 * a.tiles * (CT * CT) * 7.0 * 32 * C);
-    if (fused)
-        hipLaunchKernelGGL(conv_col7_kernel<true>, dim3(blocks), dim3(CWAVES * 64), lds, stream, a);
-    else
-        hipLaunchKernelGGL(conv_col7_kernel<false>, dim3(blocks), dim3(CWAVES * 64), lds, stream, a);
+    hipLaunchKernelGGL(kern, dim3(std::min(items, cus)), dim3(CWAVES * 64), lds, stream, a);
     return hipGetLastError();
 }
 
 hipError_t conv_col7_launch(const float* in, int C, int B, int H, int W, const float* w_swizzled, float* out,
                             hipStream_t stream) {
-    return col7_launch_impl(in, C, B, H, W, w_swizzled, out, nullptr, nullptr, stream);
+    Col7Args a{};
+    if (hipError_t e = col7_fill_args(a, in, C, B, H, W); e != hipSuccess) return e;
+    a.w = w_swizzled;
+    a.w_bytes = (unsigned)(C / CONV_BK * 7 * W_TAP * sizeof(float));
+    a.out = out;
+    static lds_once_mask configured{0};
+    note_mfma_flops(2.0 * a.tiles * (CT * CT) * 7.0 * 32 * C);          // N = 32 columns issued
+    return col7_launch_kernel(conv_col7_kernel, &configured, col7_f32_lds_bytes(C / CONV_BK, false), a.tiles, a, stream);
 }
 
+// w_split (the layer's three-plane image) given: the split-bf16 product form; otherwise the fp32 form on the 4x4x1 MFMA.
 hipError_t conv_col7_fused_launch(const float* in, int C, int B, int H, int W, const float* w_swizzled, const float* bias,
                                   float* out_nchw, hipStream_t stream, const float* w_split) {
     if (!bias || !out_nchw) return hipErrorInvalidValue;
-    return col7_launch_impl(in, C, B, H, W, w_swizzled, nullptr, bias, out_nchw, stream, w_split);
+    Col7Args a{};
+    if (hipError_t e = col7_fill_args(a, in, C, B, H, W); e != hipSuccess) return e;
+    a.bias = bias;
+    a.final_out = out_nchw;
+    // The layer counts what its fp32 form issues (N = 24), whatever the product form: bench.py prices `stage_roofline.final`
+    // against the fp32 matrix peak, and the fp32-equivalent of the N = 32 columns issued by the split form exceeded it (1.02 of
+    // the peak).
+    note_mfma_flops(2.0 * a.tiles * (CT * CT) * 7.0 * 24 * C);
+    static lds_once_mask configured_b{0}, configured_q{0};
+    if (w_split) {
+        a.w = w_split;
+        a.w_bytes = (unsigned)(col7_split_packed_elems(C) * 4);
+        return col7_launch_kernel(conv_col7b_kernel, &configured_b, S_LDS, B * a.tiles_y, a, stream);
+    }
+    a.w = w_swizzled;
+    a.w_bytes = (unsigned)(C / CONV_BK * 7 * W_TAP * sizeof(float));
+    return col7_launch_kernel(conv_col7q_kernel, &configured_q, col7_f32_lds_bytes(C / CONV_BK, true), B * a.tiles_y, a, stream);
 }
 
 }  // namespace eamm

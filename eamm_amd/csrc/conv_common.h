@@ -3,6 +3,8 @@
 #include "kernels.h"
 
 #include <atomic>
+#include <cstdint>
+#include <cstring>
 #include <type_traits>
 
 namespace eamm {
@@ -40,12 +42,23 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 
+// ---- split-bf16 products (wino4_gemm_kernel's SPLIT form, FORM 1 of conv_patch_poly_kernel, conv_col7b_kernel): an fp32 operand
+// is the exact sum of three bf16 planes taken by truncation, a = a1 + a2 + a3, and a product a * b is issued as SIX bf16 MFMA terms
+// with fp32 accumulation.  Term t multiplies plane SPLIT_TERM_A[t] of A with plane SPLIT_TERM_B[t] of B, in issue order
+//     a1b3 | a3b1 a2b1 a1b1 | a2b2 a1b2
+// The three terms left out (a2b3, a3b2, a3b3) are <= 2^-24 relative to a * b, below the rounding of the fp32 sum itself.  The ORDER
+// is part of the numerical contract: fp32 accumulation is not associative, and the accuracy and bit-identity tests of the three
+// kernels pin the results of exactly this sequence.
+constexpr int SPLIT_TERMS = 6;
+constexpr int SPLIT_TERM_A[SPLIT_TERMS] = {0, 2, 1, 0, 1, 0};
+constexpr int SPLIT_TERM_B[SPLIT_TERMS] = {2, 0, 0, 0, 1, 1};
+
 // bf16 pair {hi16(lo), hi16(hi)}: one v_perm_b32
-__device__ __forceinline__ unsigned wino4_hi_pair(unsigned lo, unsigned hi) { return __builtin_amdgcn_perm(hi, lo, 0x07060302u); }
+__device__ __forceinline__ unsigned bf16_hi_pair(unsigned lo, unsigned hi) { return __builtin_amdgcn_perm(hi, lo, 0x07060302u); }
 
 // Eight fp32 values -> three planes of eight bf16, by truncation: a1 = top 16 bits of a, r = a - a1 (exact), a2 = top 16 bits
 // of r, a3 = r - a2 (exact, at most 8 significant bits: its low half is zero).  a1 + a2 + a3 == a; inf / NaN give NaN residuals.
-__device__ __forceinline__ void wino4_split3(const f32x4& x0, const f32x4& x1, u32x4 (&pl)[3]) {
+__device__ __forceinline__ void split3_bf16(const f32x4& x0, const f32x4& x1, u32x4 (&pl)[3]) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {   // a pair at a time: few temporaries
         unsigned b1[2], b2[2], b3[2];
@@ -57,9 +70,23 @@ __device__ __forceinline__ void wino4_split3(const f32x4& x0, const f32x4& x1, u
             b2[h] = __float_as_uint(r);
             b3[h] = __float_as_uint(r - __uint_as_float(b2[h] & 0xFFFF0000u));
         }
-        pl[0][i] = wino4_hi_pair(b1[0], b1[1]);
-        pl[1][i] = wino4_hi_pair(b2[0], b2[1]);
-        pl[2][i] = wino4_hi_pair(b3[0], b3[1]);
+        pl[0][i] = bf16_hi_pair(b1[0], b1[1]);
+        pl[1][i] = bf16_hi_pair(b2[0], b2[1]);
+        pl[2][i] = bf16_hi_pair(b3[0], b3[1]);
+    }
+}
+
+// The same split of one host float (the weight packers): u1 = top 16 bits of u, u2 = top 16 bits of u - u1, u3 = u - u1 - u2 (both
+// differences exact), so the three planes sum to u exactly.
+inline void split3_bf16_host(float u, uint16_t (&pl)[3]) {
+    for (int k = 0; k < 3; ++k) {
+        uint32_t b;
+        memcpy(&b, &u, 4);
+        pl[k] = (uint16_t)(b >> 16);
+        b &= 0xFFFF0000u;
+        float top;
+        memcpy(&top, &b, 4);
+        u -= top;
     }
 }
 

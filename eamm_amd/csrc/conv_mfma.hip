@@ -333,7 +333,7 @@ std::map<std::string, std::pair<long long, int>> g_knobs;   // value in effect; 
 // cannot change the plan silently; such a variable is recorded with "set": 2 (present, ignored).
 static bool knob_documented(const char* name) {
     static const char* const names[] = {"EAMM_PASS_CHAINS", "EAMM_BNECK_CHAINS", "EAMM_WINO_TILE", "EAMM_WINO_MIN_M", "EAMM_WINO4_MIN_M",
-                                        "EAMM_ENC_WINO", "EAMM_FINAL_FUSED", "EAMM_FINAL_MFMA4", "EAMM_COL7", "EAMM_FIRST7",
+                                        "EAMM_ENC_WINO", "EAMM_FINAL_FUSED", "EAMM_COL7", "EAMM_FIRST7",
                                         "EAMM_PRIVATE_STREAMS", "EAMM_WARP_JOINT", "EAMM_HEAD_ROWSPLIT",
                                         "EAMM_PATCH_POLY", "EAMM_KPA_THIN", "EAMM_WGRAD_WINO4", "EAMM_WGRAD_ROW", "EAMM_CONV_DEV_WINO4",
                                         "EAMM_WINO4_EPI_V", "EAMM_COL7_DBG", "EAMM_WINO4_VARIANT"};   // (the last three: refused / experiments build)

@@ -33,7 +33,7 @@
 //           relative): 108 MFMAs of 32 cycles per chunk and wave instead of 144 of 64.  The activations stay fp32 in HBM and LDS
 //           (same patch DMA, same swizzle); the row transform stays fp32 VALU and each transformed fragment -- the lane's 8 K
 //           values of the 32x32x16 operand are two of the 16-byte slots above, K steps 2S and 2S+1 -- is split in registers
-//           (wino4_split3).  The weights are split once on the host (patch_poly_pack_split_host), lane-linear 1 KiB images per
+//           (split3_bf16).  The weights are split once on the host (patch_poly_pack_split_host), lane-linear 1 KiB images per
 //           (point, plane).  LDS ring: the patch keeps its two 32-channel stages (2 x 41 KiB), the weight planes come in 16-channel
 //           half-chunks (27 KiB) on a ring of two: 136 KiB, one barrier per half-chunk (54 MFMAs per wave).
 #include "conv_common.h"
@@ -290,7 +290,7 @@ __global__ __launch_bounds__(ZWAVES * 64) void conv_patch_poly_kernel(const Patc
                 if constexpr (i == 0) r[h2] = xr[h2]; else r[h2] = pk_sub4(xr[h2], cr[h2]);
                 if constexpr (j == 0) r1[h2] = r[h2]; else r[h2] = pk_sub4(r[h2], r1[h2]);
             });
-            wino4_split3(r[0], r[1], ap);
+            split3_bf16(r[0], r[1], ap);
         };
         // Per point: its weight planes are read under its own split, the next point's pixels under its MFMAs.
         load_raw(std::integral_constant<int, 0>{});
@@ -302,10 +302,9 @@ __global__ __launch_bounds__(ZWAVES * 64) void conv_patch_poly_kernel(const Patc
             __builtin_amdgcn_sched_barrier(0);
             if constexpr (pt + 1 < 9) load_raw(std::integral_constant<int, pt + 1>{});
             __builtin_amdgcn_sched_barrier(0);
-            static_for<6>([&](auto tc) {   // a1b3 | a3b1 a2b1 a1b1 | a2b2 a1b2
+            static_for<SPLIT_TERMS>([&](auto tc) {   // a1b3 | a3b1 a2b1 a1b1 | a2b2 a1b2
                 constexpr int t = decltype(tc)::value;
-                constexpr int pa = t == 0 ? 0 : t == 1 ? 2 : t == 2 ? 1 : t == 3 ? 0 : t == 4 ? 1 : 0;
-                constexpr int pb = t == 0 ? 2 : t <= 3 ? 0 : 1;
+                constexpr int pa = SPLIT_TERM_A[t], pb = SPLIT_TERM_B[t];
                 acc[pt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, ap[pa]),
                                                                   __builtin_bit_cast(bf16x8_t, ub[pb]), acc[pt], 0, 0, 0);
             });
@@ -448,25 +447,21 @@ void patch_poly_pack_host(const float* w, int Cout, int Cin, const int* cin_map,
 }
 
 // The same U as three bf16 planes for FORM 1 of conv_patch_poly_kernel: the fp32-ROUNDED value of patch_poly_pack_host is split by
-// truncation, u1 = top 16 bits of u, u2 = top 16 bits of u - u1, u3 = u - u1 - u2 (both differences exact), so u1 + u2 + u3 is
-// that float exactly.  Image [ntile][16-channel half-chunk][point][3 planes][64 lanes][8]: a (point, plane) of a half-chunk is the
+// truncation (split3_bf16_host), so u1 + u2 + u3 is that float exactly.  Image [ntile][16-channel half-chunk][point][3 planes][64 lanes][8]: a (point, plane) of a half-chunk is the
 // 1 KiB a wave reads with ONE ds_read_b128 per lane, lane-linear (conflict-free).  Lane = 32 h + (output channel % 32) holds the
 // half-chunk's channels 4 h + e (e < 4) and 8 + 4 h + (e - 4) (e >= 4): the lane's two 16-byte slots of the fp32 patch pixel.
 void patch_poly_pack_split_host(const float* w, int Cout, int Cin, const int* cin_map, int cin_packed, uint16_t* dst) {
     const int hch = cin_packed / 16;
     const size_t total = 3 * patch_poly_packed_elems(cin_packed, Cout);
     for (size_t i = 0; i < total; ++i) dst[i] = 0;
-    auto bits = [](float f) { uint32_t b; memcpy(&b, &f, 4); return b; };
-    auto top = [](uint32_t b) { b &= 0xFFFF0000u; float f; memcpy(&f, &b, 4); return f; };
     patch_poly_for_each_u(w, Cout, Cin, cin_map, cin_packed, [&](int o, int cp, int pt, float u) {
         const int nt = o / ZBN, nl = o % ZBN;
         const int hc = cp / 16, kl = cp % 16;
         const int lane = ((kl >> 2) & 1) * 32 + nl, e = (kl >> 3) * 4 + (kl & 3);
-        const float r = u - top(bits(u)), r2 = r - top(bits(r));
+        uint16_t pl[3];
+        split3_bf16_host(u, pl);
         uint16_t* blk = dst + ((((size_t)nt * hch + hc) * 9 + pt) * 3) * 512 + lane * 8 + e;
-        blk[0] = (uint16_t)(bits(u) >> 16);
-        blk[512] = (uint16_t)(bits(r) >> 16);
-        blk[1024] = (uint16_t)(bits(r2) >> 16);
+        for (int k = 0; k < 3; ++k) blk[k * 512] = pl[k];
     });
 }
 

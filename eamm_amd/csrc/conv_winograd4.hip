@@ -368,8 +368,7 @@ __global__ __launch_bounds__(WM* WN * 64) void wino4_gemm_kernel(const Wino4Args
         // the MFMAs of one term (NT of them), with the older half's DMA pieces interleaved by MFMA count as in compute()
         auto term = [&](auto sc, auto tc) {
             constexpr int sub = decltype(sc)::value, t = decltype(tc)::value;
-            constexpr int pa = t == 0 ? 0 : t == 1 ? 2 : t == 2 ? 1 : t == 3 ? 0 : t == 4 ? 1 : 0;   // a1b3 | a3b1 a2b1 a1b1 | a2b2 a1b2
-            constexpr int pb = t == 0 ? 2 : t <= 3 ? 0 : 1;
+            constexpr int pa = SPLIT_TERM_A[t], pb = SPLIT_TERM_B[t];   // a1b3 | a3b1 a2b1 a1b1 | a2b2 a1b2
             static_for<NT>([&](auto jc) {
                 constexpr int j = decltype(jc)::value;
                 acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, ap[pa]), __builtin_bit_cast(bf16x8_t, ub[pb][j]),
@@ -391,7 +390,7 @@ __global__ __launch_bounds__(WM* WN * 64) void wino4_gemm_kernel(const Wino4Args
             constexpr int sub = decltype(sc)::value;
             fetch_u(sub, 2);
             __builtin_amdgcn_sched_barrier(0);
-            wino4_split3(araw[0], araw[1], ap);
+            split3_bf16(araw[0], araw[1], ap);
             __builtin_amdgcn_sched_barrier(0);
             fetch_u(sub, 0);
             __builtin_amdgcn_sched_barrier(0);
@@ -716,25 +715,21 @@ size_t wino4_packed_elems(int Cout, int Cin, int BN) {
 }
 
 // The same U as three bf16 planes for the SPLIT form of wino4_gemm_kernel: the fp32-ROUNDED value of wino4_pack_host is split by
-// truncation, u1 = top 16 bits of u, u2 = top 16 bits of u - u1, u3 = u - u1 - u2 (both differences exact), so u1 + u2 + u3 is
-// today's float exactly.  Image [ntiles][36 * Cin/32][BN/16][3 planes][64 lanes][8]: a chunk's (column block, plane) is the 1 KB a
+// truncation (split3_bf16_host), so u1 + u2 + u3 is that float exactly.  Image [ntiles][36 * Cin/32][BN/16][3 planes][64 lanes][8]: a chunk's (column block, plane) is the 1 KB a
 // wave reads with ONE ds_read_b128 per lane, lane-linear (conflict-free).  Lane = 16 g + (column % 16) holds the channels
 // 4 g + e (e < 4) and 16 + 4 g + (e - 4) (e >= 4) of the chunk -- the lane's two 16-byte slots of the fp32 V row.
 void wino4_pack_split_host(const float* w, int Cout, int Cin, int BN, uint16_t* dst) {
     const int BK = CONV_BK, cch = Cin / BK;
     const size_t total = 3 * wino4_packed_elems(Cout, Cin, BN);
     for (size_t i = 0; i < total; ++i) dst[i] = 0;
-    auto bits = [](float f) { uint32_t b; memcpy(&b, &f, 4); return b; };
-    auto top = [](uint32_t b) { b &= 0xFFFF0000u; float f; memcpy(&f, &b, 4); return f; };
     wino4_for_each_u(w, Cout, Cin, [&](int o, int c, int xi, float u) {
         const int nt = o / BN, nl = o % BN;
         const int cc = c / BK, kl = c % BK;
         const int lane = ((kl & 15) >> 2) * 16 + (nl & 15), e = (kl >> 4) * 4 + (kl & 3);
-        const float r = u - top(bits(u)), r2 = r - top(bits(r));
+        uint16_t pl[3];
+        split3_bf16_host(u, pl);
         uint16_t* blk = dst + ((((size_t)nt * 36 * cch + (size_t)xi * cch + cc) * (BN / 16) + nl / 16) * 3) * 512 + lane * 8 + e;
-        blk[0] = (uint16_t)(bits(u) >> 16);
-        blk[512] = (uint16_t)(bits(r) >> 16);
-        blk[1024] = (uint16_t)(bits(r2) >> 16);
+        for (int k = 0; k < 3; ++k) blk[k * 512] = pl[k];
     });
 }
 

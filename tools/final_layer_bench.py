@@ -1,8 +1,8 @@
 #!/usr/bin/env python
 """The final 7x7 layer (64 -> 3, + sigmoid) alone: eamm_op_conv tile 4002 = the fused column-patch kernel as the engine runs it
 (split-bf16 products) beside tile 4003 = the same with fp32-MFMA products, timed with HIP events (20 launches).  Run once per
-environment setting (the knobs are read once per process; they select the fp32 form's kernel):
-    EAMM_FINAL_MFMA4=0|1  EAMM_COL7_DBG=0|1|2|3   python tools/final_layer_bench.py [--tiles 4002,4003] [frames ...]"""
+environment setting (the knob is read once per process; the diagnostic build's fp32 kernels honour it):
+    EAMM_COL7_DBG=0|1|2|3   python tools/final_layer_bench.py [--tiles 4002,4003] [frames ...]"""
 import ctypes as C
 import os
 import sys
@@ -24,7 +24,7 @@ if argv and argv[0] == "--tiles":
 L = _lib.lib()
 dev = torch.device("cuda:0")
 st = torch.cuda.current_stream().cuda_stream
-tag = " ".join(f"{k}={os.environ[k]}" for k in ("EAMM_FINAL_MFMA4", "EAMM_COL7_DBG") if k in os.environ) or "default"
+tag = f"EAMM_COL7_DBG={os.environ['EAMM_COL7_DBG']}" if "EAMM_COL7_DBG" in os.environ else "default"
 for B in [int(a) for a in argv] or [8, 16]:
     g = torch.Generator().manual_seed(1)
     x = torch.rand(B, 256, 256, 64, generator=g).to(dev)
