@@ -1,9 +1,5 @@
-// Backward kernels of the path's two operator kinds ("backward of warp/conv kernels"), op level:
-//   * warp_features_backward_kernel -- gradient of  out = grid_sample(feat, flow, bilinear, zeros, align_corners=False) * occ
-//     (reference modules/generator.py:50-57, 79-84) with respect to the features, the flow and the occlusion map: what
-//     autograd derives from F.grid_sample and the multiply.  HBM-bound: dout read once, the four corner lines re-read,
-//     d_feat accumulated with float atomics (as ATen's grid_sampler backward does; with one source for all frames the frames'
-//     contributions land on the same map).
+// The convolutions' weight and bias gradients ("backward of warp/conv kernels"; the warp's backward is
+// beside its forward in warp.hip), op level:
 //   * conv_wgrad_kernel -- weight gradient of a stride-1 "same" KHxKW convolution on NHWC activations
 //     (reference modules/util.py:858-938, every Conv2d of the blocks): dW[co][ci][ky][kx] = sum_p dY[p][co] * X[p + (ky,kx)][ci],
 //     one fp32-MFMA GEMM per filter tap with M = Cout, N = Cin and K = the pixels of the batch, split over the pixel range;
@@ -11,7 +7,8 @@
 //     coalesced rows of each tensor.  conv_bias_grad_kernel: db[co] = sum_p dY[p][co].
 //   The DATA gradient of such a convolution is itself a "same" convolution of dY with the transposed, flipped filter, i.e. the
 //   forward kernels (eamm_op_conv) on repacked weights; BatchNorm's backward is in batchnorm.hip.
-// These are the kernels; eamm_amd/train_graph.py composes them (with batchnorm_nhwc.hip and motion_backward.hip) into the
+//   * strided_wgrad_kernel -- the same for a stride-2 pair of maps (the stride-2 convolution's and the transposed convolution's).
+// These are the kernels; eamm_amd/train_graph.py composes them (with warp.hip, batchnorm_nhwc.hip and motion_backward.hip) into the
 // generator's end-to-end backward: loss.backward() as in train.py:133.
 #include "conv_common.h"
 
@@ -19,111 +16,6 @@
 #include <cstdlib>
 
 namespace eamm {
-
-namespace {
-
-struct BilinearB {
-    int x0, y0;
-    float ax, ay;
-    bool valid;
-};
-// the forward's bilinear_setup (motion.hip), keeping the fractions for the derivative
-__device__ __forceinline__ BilinearB bilinear_setup_b(float gx, float gy, int W, int H) {
-    const float ix = ((gx + 1.f) * (float)W - 1.f) * 0.5f;
-    const float iy = ((gy + 1.f) * (float)H - 1.f) * 0.5f;
-    const float fx = floorf(ix), fy = floorf(iy);
-    BilinearB b;
-    b.x0 = (int)fminf(fmaxf(fx, -2.f), (float)W);
-    b.y0 = (int)fminf(fmaxf(fy, -2.f), (float)H);
-    b.ax = ix - fx;
-    b.ay = iy - fy;
-    b.valid = ix > -2.f && ix < (float)W + 1.f && iy > -2.f && iy < (float)H + 1.f;
-    return b;
-}
-
-}  // namespace
-
-// one thread per (pixel, 4 channels); LPP lanes per pixel (C / 4) reduce the flow / occlusion partials before one atomic
-__global__ __launch_bounds__(256) void warp_features_backward_kernel(const float* __restrict__ feat, const float* __restrict__ defo,
-                                                                     const float* __restrict__ occ, const float* __restrict__ dout,
-                                                                     int n, int ns, int hf, int wf, int C, float* __restrict__ dfeat,
-                                                                     float* __restrict__ ddefo, float* __restrict__ docc) {
-    const int c4n = C >> 2;
-    const size_t total = (size_t)n * hf * wf * c4n;
-    const bool pow2 = (c4n & (c4n - 1)) == 0 && c4n <= 64;
-    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
-        const int c4 = (int)(idx % c4n);
-        const size_t pix = idx / c4n;
-        const int f = (int)(pix / ((size_t)wf * hf));
-        const float2 g = reinterpret_cast<const float2*>(defo)[pix];
-        const float o = occ ? occ[pix] : 1.f;
-        const BilinearB b = bilinear_setup_b(g.x, g.y, wf, hf);
-        // a thread owns channels c4 + k * c4n (k = 0..3): the lanes of a pixel touch CONSECUTIVE floats, so each atomic
-        // instruction of the wave lands on whole cache lines (4 x fewer L2 atomic operations than a float4 per lane)
-        const float* gp = dout + pix * C + c4;
-        const float go[4] = {gp[0], gp[c4n], gp[2 * c4n], gp[3 * c4n]};
-        const size_t sbase = (size_t)((ns == 1) ? 0 : f) * hf * wf;
-        float dgx = 0.f, dgy = 0.f, dsum = 0.f;
-        if (b.valid) {
-            const float wx[2] = {1.f - b.ax, b.ax}, wy[2] = {1.f - b.ay, b.ay};
-#pragma unroll
-            for (int cy = 0; cy < 2; ++cy)
-#pragma unroll
-                for (int cx = 0; cx < 2; ++cx) {
-                    const int yy = b.y0 + cy, xx = b.x0 + cx;
-                    if ((unsigned)yy >= (unsigned)hf || (unsigned)xx >= (unsigned)wf) continue;   // zeros padding: no value, no gradient
-                    const size_t src = (sbase + (size_t)yy * wf + xx) * C + c4;
-                    const float* vp = feat + src;
-                    const float dot = go[0] * vp[0] + go[1] * vp[c4n] + go[2] * vp[2 * c4n] + go[3] * vp[3 * c4n];   // sum_c dout * feat
-                    const float w = wx[cx] * wy[cy];
-                    dsum = fmaf(w, dot, dsum);
-                    dgx = fmaf((cx ? 1.f : -1.f) * wy[cy], dot, dgx);                            // d w / d ix
-                    dgy = fmaf((cy ? 1.f : -1.f) * wx[cx], dot, dgy);                            // d w / d iy
-                    if (dfeat != nullptr) {
-                        float* d = dfeat + src;
-                        const float s = w * o;
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) atomicAdd(d + k * c4n, go[k] * s);
-                    }
-                }
-        }
-        // ix = ((gx + 1) W - 1) / 2: d ix / d gx = W / 2 (likewise y); the occlusion factor multiplies the sampled value
-        float pgx = dgx * o * 0.5f * (float)wf, pgy = dgy * o * 0.5f * (float)hf, po = dsum;
-        if (pow2) {   // the c4n lanes of a pixel are a power-of-two aligned group of the wave
-            for (int off = c4n >> 1; off > 0; off >>= 1) {
-                pgx += __shfl_xor(pgx, off, 64);
-                pgy += __shfl_xor(pgy, off, 64);
-                po += __shfl_xor(po, off, 64);
-            }
-            if (c4 == 0) {
-                if (ddefo != nullptr) {
-                    atomicAdd(ddefo + pix * 2, pgx);
-                    atomicAdd(ddefo + pix * 2 + 1, pgy);
-                }
-                if (docc != nullptr) atomicAdd(docc + pix, po);
-            }
-        } else {
-            if (ddefo != nullptr) {
-                atomicAdd(ddefo + pix * 2, pgx);
-                atomicAdd(ddefo + pix * 2 + 1, pgy);
-            }
-            if (docc != nullptr) atomicAdd(docc + pix, po);
-        }
-    }
-}
-
-hipError_t warp_features_backward_launch(const float* feat, const float* defo, const float* occ, const float* dout, int n, int ns,
-                                         int hf, int wf, int C, float* dfeat, float* ddefo, float* docc, hipStream_t s) {
-    if (C % 4 || n < 1) return hipErrorInvalidValue;
-    const size_t total = (size_t)n * hf * wf * (C / 4);
-    // the in-wave reduction needs every lane of a pixel's group alive: whole groups per block, and a grid that covers the
-    // tensor in one sweep of whole blocks (256 is a multiple of every power-of-two group size)
-    const size_t blocks = (total + 255) / 256;
-    if (blocks > (size_t)0x7FFFFFFF) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(warp_features_backward_kernel, dim3((unsigned)blocks), dim3(256), 0, s, feat, defo, occ, dout, n, ns, hf, wf, C,
-                       dfeat, ddefo, docc);
-    return hipGetLastError();
-}
 
 // ---------------------------------------------------------------------------------------------------------
 // convolution weight gradient

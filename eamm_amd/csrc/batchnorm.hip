@@ -10,7 +10,7 @@
 //   bn_finalize_kernel      mean, inverse standard deviation, running-statistics update, per-channel scale
 //   bn_apply_kernel         x read once more, y written once
 // Algorithmic bytes: 12 B per element (two reads, one write); the statistics are 8 B per channel.
-#include "kernels.h"
+#include "pointwise.h"
 
 #include <algorithm>
 
@@ -18,12 +18,6 @@ namespace eamm {
 
 namespace {
 constexpr int BN_THREADS = 256;
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
 }  // namespace
 
 // grid (C, S, R): block (c, s, r) covers images n = s, s + S, ... and the r-th of R slices of their HW plane.
@@ -52,8 +46,8 @@ __global__ __launch_bounds__(BN_THREADS) void bn_partial_sums_kernel(const float
         }
     }
     __shared__ double red[2][BN_THREADS / 64];
-    sum = wave_sum(sum);
-    ssum = wave_sum(ssum);
+    sum = wave_reduce<SumOp, Lanes::First>(sum);   // (valid in lane 0)
+    ssum = wave_reduce<SumOp, Lanes::First>(ssum);
     if ((threadIdx.x & 63) == 0) {
         red[0][threadIdx.x >> 6] = sum;
         red[1][threadIdx.x >> 6] = ssum;
@@ -97,8 +91,8 @@ __global__ __launch_bounds__(64) void bn_combine_kernel(const double* __restrict
         a += partial[((size_t)c * P + p) * 2];
         b += partial[((size_t)c * P + p) * 2 + 1];
     }
-    a = wave_sum(a);
-    b = wave_sum(b);
+    a = wave_reduce<SumOp, Lanes::First>(a);
+    b = wave_reduce<SumOp, Lanes::First>(b);
     if (lane == 0) {
         sums[c] = (float)a;
         sums[C + c] = (float)b;
@@ -229,8 +223,8 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_partial_kernel(const float*
         }
     }
     __shared__ double red[2][BN_THREADS / 64];
-    sa = wave_sum(sa);
-    sb = wave_sum(sb);
+    sa = wave_reduce<SumOp, Lanes::First>(sa);
+    sb = wave_reduce<SumOp, Lanes::First>(sb);
     if ((threadIdx.x & 63) == 0) {
         red[0][threadIdx.x >> 6] = sa;
         red[1][threadIdx.x >> 6] = sb;

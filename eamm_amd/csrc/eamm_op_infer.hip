@@ -58,7 +58,7 @@ int eamm_op_emotion_augment(int device, const float* aligned, int64_t n_src, int
     OP_DONE(emotion_augment_launch(aligned, n_src, t0, count, hinv, noise, p, out, s), "eamm_op_emotion_augment");
 }
 
-// ---- the frozen inference path's small kernels, one launch each (conv_first.hip, motion.hip, emotion.hip, audio.hip): what the engines
+// ---- the frozen inference path's small kernels, one launch each (conv_first.hip, motion.hip, warp.hip, conv_col7.hip, emotion.hip, audio.hip): what the engines
 // call per frame or once per clip, on the caller's buffers.  Nothing here but the argument checks and the engines' own *_launch calls.
 
 int eamm_op_first7(int device, const float* source, int ns, int H, int W, const float* w_host, const float* b_host, int Cout, float* out,

@@ -1,4 +1,4 @@
-// The differentiable operators of the training graph that are no convolutions: the warp's backward, the dense-motion front end and
+// The differentiable operators of the training graph that are no convolutions: the warp's backward (warp.hip), the dense-motion front end and
 // flow head, the key-point heads' reduction, Emotion_k's max-pool and `final` stack, AT_net2's LSTM layer and max-pools.
 #include "op_common.h"
 
@@ -69,7 +69,7 @@ int eamm_op_warp_backward(int device, const float* feat, const float* deformatio
     OP_DONE(e, "eamm_op_warp_backward");
 }
 
-// ---- differentiable dense-motion front end and flow head (motion.hip forward kernels, motion_backward.hip) -----------------------
+// ---- differentiable dense-motion front end and flow head (motion.hip, motion_backward.hip) ----------------------------------------
 int eamm_op_antialias_down(int device, const float* source, const float* aa_weight, int B, int H, int W, int inv_scale, float* small,
                            void* stream_) {
     // (inv_scale 2: forward only -- the engines' once-per-clip launch at that scale is compared with this one; the backward entry keeps 1 | 4)
@@ -148,7 +148,7 @@ int eamm_op_motion_head_backward(int device, const float* mask, const float* occ
     OP_DONE(e, "eamm_op_motion_head_backward");
 }
 
-// ---- the key-point heads' reduction as a differentiable operator (motion.hip forward kernels, kp_head_backward.hip) -----------------
+// ---- the key-point heads' reduction as a differentiable operator (kp_head.hip) ------------------------------------------------------
 size_t eamm_op_kp_head_workspace_floats(int B, int K) {
     return B < 1 || K < 1 ? 0 : std::max(kp_head_workspace_floats(B, K), kp_head_backward_workspace_floats(B, K));
 }

@@ -11,8 +11,8 @@
 // next statistics hand-over and returns 1 with the buffer to reduce, 0 when the pass is complete.  Everything else of the
 // pass (anti-aliasing, heat-maps, sparse motions, flow head, warps, final convolution) is the evaluation path's kernels and,
 // stage by stage, its launch sequences (stage_*, eamm_ctx.h; col7 = 0 here, so head and final layer take the im2col-style kernels).
-// This file is the graph-free FORWARD; the backward operators live in backward.hip, conv7_thin.hip, batchnorm*.hip and
-// motion_backward.hip and are composed by eamm_amd/train_graph.py (which also offers this forward, `train_route = "operators"`).
+// This file is the graph-free FORWARD; the backward operators live in backward.hip, warp.hip, conv7_thin.hip, batchnorm*.hip,
+// kp_head.hip and motion_backward.hip and are composed by eamm_amd/train_graph.py (which also offers this forward, `train_route = "operators"`).
 #include "eamm_ctx.h"
 
 namespace {

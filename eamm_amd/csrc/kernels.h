@@ -139,6 +139,9 @@ hipError_t conv_col7_fused_launch(const float* in, int C, int B, int H, int W, c
 size_t col7_split_packed_elems(int cin_packed);
 void col7_pack_split_host(const float* w_rowsplit, int Cout, int Cin, const int* cin_map, int cin_packed, uint16_t* dst);
 
+// the plain form's second half: the seven horizontal taps gathered, bias, sigmoid
+hipError_t final_shift_sum_launch(const float* part /*[n,H,W,32]: channel dx*3+co*/, const float* bias /*[3] dev*/,
+                                  int n, int H, int W, float* out /*[n,3,H,W]*/, hipStream_t s);
 // streamed-weight variant for the row-split flow head: two concatenated inputs, N = ntile32*32 (3 -> 96), weights packed with
 // conv_pack_host(..., kh 7, kw 1, BN 96, swizzle); out [B,H,W,pixel_stride]
 hipError_t conv_col7s_launch(const float* in0, int C0, const float* in1, int C1, int B, int H, int W, const float* w_swizzled,
@@ -182,40 +185,37 @@ void first7_pack_host(const float* w_oihw_7x7_folded, int Cout, float* dst /*[19
 hipError_t first7_launch(const float* src /*[ns,3,H,W]*/, const float* w_packed, const float* bias, int ns, int H, int W,
                          int Cout, float* out /*[ns,H,W,Cout]*/, hipStream_t stream);
 
-// ---- motion / warp / image kernels (motion.hip) ---------------------------------------------
+// ---- dense-motion kernels: key-point records, front end, flow head, source preparation; layout and format changes (motion.hip)
 hipError_t kp_prepare_launch(const float* kd_val, const float* kd_jac, const float* ks_val, const float* ks_jac,
                              int n, int ns, int K, float* kp_rec, int* bad_flag, hipStream_t s);
 hipError_t motion_front_launch(const float* kp_rec, const float* src_small /*[ns,h,w,4]*/, int n, int ns, int K,
                                int h, int w, float variance, int Cpad, float* hg_in /*[n,h,w,Cpad]*/,
                                float* sparse_deformed /*[n,K+1,channels,h,w] or null*/, hipStream_t s, int groups = 1,
-                               int channels = 3, size_t group_stride = 0);   // groups of three image channels (motion.hip)
+                               int channels = 3, size_t group_stride = 0);   // groups of three image channels
 hipError_t motion_head_launch(const float* logits /*[n,h,w,32]*/, const float* kp_rec, int n, int K, int h, int w,
                               int has_occ, float* deformation /*[n,h,w,2]*/, float* occlusion /*[n,h,w]*/,
                               float* mask_out /*[n,K+1,h,w] or null*/, float* occ_out /*[n,1,h,w] or null*/,
                               hipStream_t s);
+// the training entry's form: mask logits [n,h,w,ld] (channels 0..K), occlusion logit [n,h,w,ldo] (channel 0) or null
+hipError_t motion_head_forward_launch(const float* lm, int ld, const float* lo, int ldo, const float* rec, int n, int K, int h, int w,
+                                      float* mask, float* deformation, float* occlusion, hipStream_t s);
 hipError_t motion_head_rowsplit_launch(const float* part /*[n,h,w,PS]: channel dx*NC+co*/, int PS, int NC,
                                        const float* bias /*[NC] dev*/, const float* kp_rec, int n, int K, int h, int w,
                                        int has_occ, float* deformation, float* occlusion, float* mask_out,
                                        float* occ_out, hipStream_t s);
-hipError_t warp_features_launch(const float* feat /*[ns,hf,wf,C]*/, const float* deformation /*[n,h,w,2]*/,
-                                const float* occlusion /*[n,h,w] or null*/, int n, int ns, int hf, int wf, int C,
-                                int h, int w, float* out, float* out2, const float* s2, const float* t2,
-                                hipStream_t s);
 hipError_t broadcast_features_launch(const float* feat /*[ns,hf,wf,C]*/, int n, int ns, int hf, int wf, int C, float* out,
                                      float* out2, const float* s2, const float* t2, hipStream_t s);
-hipError_t warp_image_launch(const float* src /*[ns,3,H,W]*/, const float* deformation /*[n,h,w,2]*/, int n, int ns,
-                             int H, int W, int h, int w, float* out /*[n,channels,H,W]*/, hipStream_t s, int src_planes = 3,
-                             int channels = 3);
 hipError_t source_prepare_launch(const float* src /*[ns,3,H,W]*/, const float* aa_w /*[3,13,13] dev*/, int ns, int H,
                                  int W, int inv_scale, int Cpad, float* src_nhwc /*[ns,H,W,Cpad]*/,
                                  float* src_small /*[ns,h,w,4]*/, hipStream_t s);
-hipError_t final_shift_sum_launch(const float* part /*[n,H,W,32]: channel dx*3+co*/, const float* bias /*[3] dev*/,
-                                  int n, int H, int W, float* out /*[n,3,H,W]*/, hipStream_t s);
 hipError_t antialias_down_launch(const float* src /*[ns,3,H,W]*/, const float* aa_w, int ns, int H, int W,
                                  int inv_scale, int Cpad, float* dst /*[ns,h,w,Cpad]: RGB + zeros*/, hipStream_t s,
                                  int src_planes = 3, int first_channel = 0, int channels = 3, int slot = 0);
 hipError_t nchw_to_nhwc_pad_launch(const float* src /*[B,planes,H,W]*/, int B, int C, int H, int W, int Cpad,
                                    float* dst /*[B,H,W,Cpad]*/, hipStream_t s, int planes = 0 /*0: = C; else the first C of them*/);
+hipError_t to_u8_launch(const float* pred /*[n,3,H,W]*/, int n, int H, int W, uint8_t* out /*[n,H,W,3]*/,
+                        hipStream_t s);
+// ---- the key-point heads' reduction, forward and backward (kp_head.hip)
 hipError_t kp_head_launch(const float* logits /*[B,h,w,Cs]*/, int B, int K, int njm, int h, int w, int Cs, int pad,
                           float temperature, float* value /*[B,K,2]*/, float* jacobian /*[B,K,2,2] or null*/,
                           float* heatmap /*[B,K,h-6+2pad,w-6+2pad] or null*/, hipStream_t s,
@@ -223,13 +223,23 @@ hipError_t kp_head_launch(const float* logits /*[B,h,w,Cs]*/, int B, int K, int 
                           float* stats = nullptr /*[B,K,2]: the softmax's (maximum, denominator), what the backward reads*/);
 constexpr int KP_HEAD_SLICES = 8;
 size_t kp_head_workspace_floats(int B, int K);
-// backward of the heads' reduction (kp_head_backward.hip): any of the three gradients may be null; grad_logits is fully written
+// its backward: any of the three gradients may be null; grad_logits is fully written
 constexpr int KP_HEAD_BWD_SLICES = 32;
 size_t kp_head_backward_workspace_floats(int B, int K);
 hipError_t kp_head_backward_launch(const float* logits /*[B,h,w,Cs]*/, const float* stats /*[B,K,2]*/, const float* value /*[B,K,2]*/,
                                    const float* jacobian /*[B,K,2,2] or null*/, const float* g_value, const float* g_jacobian,
                                    const float* g_heatmap, int B, int K, int njm, int h, int w, int Cs, int pad, float temperature,
                                    float* grad_logits /*[B,h,w,Cs]*/, float* ws /* kp_head_backward_workspace_floats(B, K) */, hipStream_t s);
+// ---- the warps by the flow (warp.hip); the backward ACCUMULATES its three gradients into zeroed buffers
+hipError_t warp_features_launch(const float* feat /*[ns,hf,wf,C]*/, const float* deformation /*[n,h,w,2]*/,
+                                const float* occlusion /*[n,h,w] or null*/, int n, int ns, int hf, int wf, int C,
+                                int h, int w, float* out, float* out2, const float* s2, const float* t2,
+                                hipStream_t s);
+hipError_t warp_image_launch(const float* src /*[ns,3,H,W]*/, const float* deformation /*[n,h,w,2]*/, int n, int ns,
+                             int H, int W, int h, int w, float* out /*[n,channels,H,W]*/, hipStream_t s, int src_planes = 3,
+                             int channels = 3);
+hipError_t warp_features_backward_launch(const float* feat, const float* defo, const float* occ, const float* dout, int n, int ns,
+                                         int hf, int wf, int C, float* dfeat, float* ddefo, float* docc, hipStream_t s);
 // ---- training-mode BatchNorm forward (batchnorm.hip; SURVEY.md 8f row N4, first slice)
 size_t bn_workspace_floats(int N, int C, int HW);
 hipError_t bn_local_sums_launch(const float* x /*[N,C,HW]*/, int N, int C, int HW, float* sums /*[6C+2]*/, float* workspace,
@@ -271,13 +281,8 @@ hipError_t bn_nhwc_bwd_sums_launch(const float* x, const float* dy, const float*
                                    const BnFuse* fuse = nullptr);
 hipError_t bn_nhwc_bwd_apply_launch(const float* x, const float* dy, const float* mean, const float* scale, const float* bias,
                                     const float* coef, int B, int H, int W, int C, int relu, int pool, float* dx, hipStream_t s);
-hipError_t to_u8_launch(const float* pred /*[n,3,H,W]*/, int n, int H, int W, uint8_t* out /*[n,H,W,3]*/,
-                        hipStream_t s);
 
-// backward.hip: gradients of the warp (features, flow, occlusion; ACCUMULATING into zeroed buffers) and of a stride-1 "same"
-// convolution's weights and bias (NHWC activations, OIHW gradient)
-hipError_t warp_features_backward_launch(const float* feat, const float* defo, const float* occ, const float* dout, int n, int ns,
-                                         int hf, int wf, int C, float* dfeat, float* ddefo, float* docc, hipStream_t s);
+// backward.hip: gradients of a stride-1 "same" convolution's weights and bias (NHWC activations, OIHW gradient)
 size_t conv_wgrad_workspace_floats(int B, int H, int W, int Cin, int Cout, int kh, int kw);
 hipError_t conv_wgrad_launch(const float* x, const float* dy, int B, int H, int W, int Cin, int Cout, int kh, int kw, float* dweight,
                              float* dbias, float* workspace, size_t workspace_floats, hipStream_t s, const float* x_transformed = nullptr);
@@ -307,7 +312,7 @@ hipError_t conv7_thin_in_launch(const float* thin, const float* w, const float* 
 hipError_t conv7_thin_wgrad_launch(const float* thin, const float* wide, int B, int H, int W, int N, int thin_is_input, float* dw,
                                    float* workspace, hipStream_t s);
 
-// ---- backward of the dense-motion front end / flow head (motion_backward.hip; forward kernels in motion.hip)
+// ---- backward of the dense-motion kernels (motion_backward.hip)
 hipError_t antialias_down_backward_launch(const float* dsmall /*[B,h,w,4]*/, const float* aa_w, int B, int H, int W, int inv_scale,
                                           float* dsrc /*[B,3,H,W]*/, hipStream_t s);
 hipError_t kp_records_backward_launch(const float* kd_jac, const float* ks_jac, const float* drec, int n, int K, float* dkd_val,
@@ -316,8 +321,6 @@ size_t motion_backward_workspace_floats(int n, int K, int h, int w);
 hipError_t motion_front_backward_launch(const float* rec, const float* src_small, int n, int K, int h, int w, float variance, int Cpad,
                                         const float* dhg, const float* dsd, float* dsrc_small, float* drec, float* workspace,
                                         hipStream_t s);
-hipError_t motion_head_forward_launch(const float* lm, int ld, const float* lo, int ldo, const float* rec, int n, int K, int h, int w,
-                                      float* mask, float* deformation, float* occlusion, hipStream_t s);
 hipError_t motion_head_backward_launch(const float* mask, const float* occlusion, const float* rec, int n, int K, int h, int w,
                                        const float* dmask, const float* ddef, const float* docc, float* dlm, int ld, float* dlo, int ldo,
                                        float* drec, float* workspace, hipStream_t s);

@@ -7,59 +7,23 @@
 //   * kp_records_backward_kernel      -- J = J_source inverse(J_driving) (dense_motion.py:55-56) and the key-point values.
 //   * motion_front_backward_kernel    -- heat-maps (util.py:815-836, dense_motion.py:32-45), sparse motions T_k (:47-67) and the
 //     K+1 bilinear warps of the down-sampled source (:69-79): d hourglass-input / d sparse_deformed -> d records, d source.
-//   * motion_head_forward / backward  -- softmax over the K+1 mask logits, deformation = sum_k mask_k T_k, sigmoid occlusion
-//     (:98-111) on the two convolutions' NHWC outputs.
+//   * motion_head_backward_kernel     -- softmax over the K+1 mask logits, deformation = sum_k mask_k T_k, sigmoid occlusion
+//     (:98-111) on the two convolutions' NHWC outputs (the forward is motion.hip's motion_head_forward_kernel).
+// The grid, T_k, the sampling position and the workgroup sum are the forward kernels' own (pointwise.h).
 // All of it is HBM-bound element-wise / gather work on the 64x64 motion grid (a few MB per batch): one thread per pixel, the
 // per-key-point sums reduced per workgroup and then in a FIXED order over the workgroups (the key-point / record gradients are
 // deterministic).  NOT deterministic: the gradient of the down-sampled SOURCE image in motion_front_backward_kernel, which is
 // accumulated with float atomicAdd over the pixels and the K+1 motions that sampled a source pixel (as ATen's grid_sample
 // backward does): it varies in the last bits from run to run; the gradient tests' tolerances cover that.
-#include "kernels.h"
+#include "pointwise.h"
 
 #include <algorithm>
 
 namespace eamm {
 
 namespace {
-
-__device__ __forceinline__ float grid_coord_b(int j, int n) { return 2.f * ((float)j / (float)(n - 1)) - 1.f; }
-
-struct BilinearM {
-    int x0, y0;
-    float ax, ay;
-    bool valid;
-};
-// the forward's bilinear_setup (motion.hip) with the fractions kept for the derivative
-__device__ __forceinline__ BilinearM bilinear_setup_m(float gx, float gy, int W, int H) {
-    const float ix = ((gx + 1.f) * (float)W - 1.f) * 0.5f;
-    const float iy = ((gy + 1.f) * (float)H - 1.f) * 0.5f;
-    const float fx = floorf(ix), fy = floorf(iy);
-    BilinearM b;
-    b.x0 = (int)fminf(fmaxf(fx, -2.f), (float)W);
-    b.y0 = (int)fminf(fmaxf(fy, -2.f), (float)H);
-    b.ax = ix - fx;
-    b.ay = iy - fy;
-    b.valid = ix > -2.f && ix < (float)W + 1.f && iy > -2.f && iy < (float)H + 1.f;
-    return b;
-}
-
-constexpr int MB_THREADS = 256;
+constexpr int MB_THREADS = 64 * BLOCK_WAVES;   // the workgroup sums below are block_reduce's
 constexpr int MB_MAXK = 31;
-
-// sum of v over the workgroup's threads, result valid in thread 0 (fixed tree: deterministic)
-__device__ __forceinline__ float block_sum(float v, float* red /*[MB_THREADS / 64]*/) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    __syncthreads();                  // `red` may still be read from the previous call
-    if (lane == 0) red[wv] = v;
-    __syncthreads();
-    float s = 0.f;
-    if (threadIdx.x == 0)
-        for (int i = 0; i < MB_THREADS / 64; ++i) s += red[i];
-    return s;
-}
-
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -173,12 +137,12 @@ __global__ __launch_bounds__(MB_THREADS) void motion_front_backward_kernel(const
                                                                            float variance, int Cpad, const float* __restrict__ dhg,
                                                                            const float* __restrict__ dsd, float* __restrict__ dsrc_small,
                                                                            float* __restrict__ part) {
-    __shared__ float red[MB_THREADS / 64];
+    __shared__ float red[BLOCK_WAVES];
     const int f = blockIdx.y;
     const int pi = blockIdx.x * blockDim.x + threadIdx.x;
     const bool live = pi < h * w;
     const int y = live ? pi / w : 0, x = live ? pi - y * w : 0;
-    const float gx = grid_coord_b(x, w), gy = grid_coord_b(y, h);
+    const float gx = grid_coord(x, w), gy = grid_coord(y, h);
     const float4* src = src_small + (size_t)f * h * w;
     float* dsrc = dsrc_small ? dsrc_small + (size_t)f * h * w * 4 : nullptr;
     const float* rec = rec_all + (size_t)f * K * KP_STRIDE;
@@ -201,15 +165,10 @@ __global__ __launch_bounds__(MB_THREADS) void motion_front_backward_kernel(const
         }
         float tx = gx, ty = gy, rx = 0.f, ry = 0.f;
         const float* r = rec + (k > 0 ? k - 1 : 0) * KP_STRIDE;
-        if (k > 0) {
-            rx = gx - r[0];
-            ry = gy - r[1];
-            tx = fmaf(r[5], ry, r[4] * rx) + r[2];
-            ty = fmaf(r[7], ry, r[6] * rx) + r[3];
-        }
+        if (k > 0) sparse_motion(r, gx, gy, tx, ty, rx, ry);
         float dtx = 0.f, dty = 0.f;
         if (live) {
-            const BilinearM b = bilinear_setup_m(tx, ty, w, h);
+            const SamplePos b = sample_pos(tx, ty, w, h);
             if (b.valid) {
                 const float wx[2] = {1.f - b.ax, b.ax}, wy[2] = {1.f - b.ay, b.ay};
                 float dix = 0.f, diy = 0.f;
@@ -254,7 +213,7 @@ __global__ __launch_bounds__(MB_THREADS) void motion_front_backward_kernel(const
         const float vals[8] = {dkdx, dkdy, dksx, dksy, dtx * rx, dtx * ry, dty * rx, dty * ry};
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const float s = block_sum(live ? vals[j] : 0.f, red);
+            const float s = block_reduce<SumOp, Lanes::First>(live ? vals[j] : 0.f, red);
             if (threadIdx.x == 0) out[(k - 1) * KP_STRIDE + j] = s;
         }
     }
@@ -279,42 +238,8 @@ size_t motion_backward_workspace_floats(int n, int K, int h, int w) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// flow head on the two convolutions' outputs: mask logits [n,h,w,ld] (channels 0..K), occlusion logit [n,h,w,ldo] (channel 0)
+// flow head backward on the two convolutions' outputs: mask logits [n,h,w,ld] (channels 0..K), occlusion logit [n,h,w,ldo] (channel 0)
 // ---------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void motion_head_forward_kernel(const float* __restrict__ lm, int ld, const float* __restrict__ lo,
-                                                                  int ldo, const float* __restrict__ rec_all, int K, int h, int w,
-                                                                  float* __restrict__ mask, float* __restrict__ deformation,
-                                                                  float* __restrict__ occlusion) {
-    const int f = blockIdx.y;
-    const int pi = blockIdx.x * blockDim.x + threadIdx.x;
-    if (pi >= h * w) return;
-    const int y = pi / w, x = pi - y * w;
-    const float gx = grid_coord_b(x, w), gy = grid_coord_b(y, h);
-    const float* l = lm + ((size_t)f * h * w + pi) * ld;
-    const float* rec = rec_all + (size_t)f * K * KP_STRIDE;
-    float mx = l[0];
-    for (int k = 1; k <= K; ++k) mx = fmaxf(mx, l[k]);
-    float sum = 0.f;
-    for (int k = 0; k <= K; ++k) sum += expf(l[k] - mx);
-    float dx = 0.f, dy = 0.f;
-    const size_t plane = (size_t)h * w;
-    for (int k = 0; k <= K; ++k) {
-        const float mk = expf(l[k] - mx) / sum;
-        float tx = gx, ty = gy;
-        if (k > 0) {
-            const float* r = rec + (k - 1) * KP_STRIDE;
-            const float rx = gx - r[0], ry = gy - r[1];
-            tx = fmaf(r[5], ry, r[4] * rx) + r[2];
-            ty = fmaf(r[7], ry, r[6] * rx) + r[3];
-        }
-        dx = fmaf(mk, tx, dx);
-        dy = fmaf(mk, ty, dy);
-        mask[((size_t)f * (K + 1) + k) * plane + pi] = mk;
-    }
-    reinterpret_cast<float2*>(deformation)[(size_t)f * plane + pi] = make_float2(dx, dy);
-    if (lo) occlusion[(size_t)f * plane + pi] = 1.f / (1.f + expf(-lo[((size_t)f * plane + pi) * ldo]));
-}
-
 // d mask [n,K+1,h,w], d deformation [n,h,w,2], d occlusion [n,h,w] (any may be null) -> d logits (same layouts as the inputs,
 // channels beyond the used ones zeroed), partial d records
 __global__ __launch_bounds__(MB_THREADS) void motion_head_backward_kernel(const float* __restrict__ mask, const float* __restrict__ occlusion,
@@ -325,13 +250,13 @@ __global__ __launch_bounds__(MB_THREADS) void motion_head_backward_kernel(const 
                                                                           float* __restrict__ part) {
     // stacked: the occlusion logit is channel K + 1 of the mask logits' rows (one convolution produced both): its gradient goes
     // to dlm[.., K + 1] and dlo is null
-    __shared__ float red[MB_THREADS / 64];
+    __shared__ float red[BLOCK_WAVES];
     const int f = blockIdx.y;
     const int pi = blockIdx.x * blockDim.x + threadIdx.x;
     const bool live = pi < h * w;
     const int p = live ? pi : 0;
     const int y = p / w, x = p - y * w;
-    const float gx = grid_coord_b(x, w), gy = grid_coord_b(y, h);
+    const float gx = grid_coord(x, w), gy = grid_coord(y, h);
     const size_t plane = (size_t)h * w;
     const float* rec = rec_all + (size_t)f * K * KP_STRIDE;
     float2 gd = make_float2(0.f, 0.f);
@@ -341,12 +266,7 @@ __global__ __launch_bounds__(MB_THREADS) void motion_head_backward_kernel(const 
     for (int k = 0; k <= K; ++k) {
         const float mk = mask[((size_t)f * (K + 1) + k) * plane + p];
         float tx = gx, ty = gy;
-        if (k > 0) {
-            const float* r = rec + (k - 1) * KP_STRIDE;
-            const float rx = gx - r[0], ry = gy - r[1];
-            tx = fmaf(r[5], ry, r[4] * rx) + r[2];
-            ty = fmaf(r[7], ry, r[6] * rx) + r[3];
-        }
+        if (k > 0) sparse_motion(rec + (k - 1) * KP_STRIDE, gx, gy, tx, ty);
         const float u = (dmask ? dmask[((size_t)f * (K + 1) + k) * plane + p] : 0.f) + gd.x * tx + gd.y * ty;
         dot = fmaf(mk, u, dot);
     }
@@ -356,12 +276,7 @@ __global__ __launch_bounds__(MB_THREADS) void motion_head_backward_kernel(const 
         const float mk = mask[((size_t)f * (K + 1) + k) * plane + p];
         float tx = gx, ty = gy, rx = 0.f, ry = 0.f;
         const float* r = rec + (k > 0 ? k - 1 : 0) * KP_STRIDE;
-        if (k > 0) {
-            rx = gx - r[0];
-            ry = gy - r[1];
-            tx = fmaf(r[5], ry, r[4] * rx) + r[2];
-            ty = fmaf(r[7], ry, r[6] * rx) + r[3];
-        }
+        if (k > 0) sparse_motion(r, gx, gy, tx, ty, rx, ry);
         const float u = (dmask ? dmask[((size_t)f * (K + 1) + k) * plane + p] : 0.f) + gd.x * tx + gd.y * ty;
         if (live) dl[k] = mk * (u - dot);
         if (k == 0) continue;
@@ -369,7 +284,7 @@ __global__ __launch_bounds__(MB_THREADS) void motion_head_backward_kernel(const 
         const float vals[8] = {-(r[4] * dtx + r[6] * dty), -(r[5] * dtx + r[7] * dty), dtx, dty, dtx * rx, dtx * ry, dty * rx, dty * ry};
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const float s = block_sum(vals[j], red);
+            const float s = block_reduce<SumOp, Lanes::First>(vals[j], red);
             if (threadIdx.x == 0) out[(k - 1) * KP_STRIDE + j] = s;
         }
     }
@@ -388,14 +303,6 @@ __global__ __launch_bounds__(MB_THREADS) void motion_head_backward_kernel(const 
             for (int k = 1; k < ldo; ++k) d[k] = 0.f;
         }
     }
-}
-
-hipError_t motion_head_forward_launch(const float* lm, int ld, const float* lo, int ldo, const float* rec, int n, int K, int h, int w,
-                                      float* mask, float* deformation, float* occlusion, hipStream_t s) {
-    if (K < 1 || K > MB_MAXK || ld < K + 1 || (lo && ldo < 1)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(motion_head_forward_kernel, dim3((h * w + 255) / 256, n), dim3(256), 0, s, lm, ld, lo, ldo, rec, K, h, w, mask,
-                       deformation, occlusion);
-    return hipGetLastError();
 }
 
 hipError_t motion_head_backward_launch(const float* mask, const float* occlusion, const float* rec, int n, int K, int h, int w,

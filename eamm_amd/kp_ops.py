@@ -1,5 +1,5 @@
 """The key-point heads' reduction as a differentiable operator -- a ``torch.autograd.Function`` whose forward AND backward are
-libeamm_hip.so kernels (csrc/motion.hip ``kp_head_launch``, csrc/kp_head_backward.hip; C ABI ``eamm_op_kp_head`` /
+libeamm_hip.so kernels (csrc/kp_head.hip: ``kp_head_launch``, ``kp_head_backward_launch``; C ABI ``eamm_op_kp_head`` /
 ``eamm_op_kp_head_backward``).
 
 It carries reference modules/keypoint_detector.py:77-105 (``KPDetector``) and :180-205 (``KPDetector_a``) after the two 7x7

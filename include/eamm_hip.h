@@ -726,7 +726,7 @@ int eamm_op_motion_head_backward(int device, const float* mask, const float* occ
 
 /*
  * The key-point heads' reduction as a DIFFERENTIABLE operator (reference modules/keypoint_detector.py:77-105 / :180-205): the
- * forward is the detectors' own kernels (motion.hip), the backward is kp_head_backward.hip.  Device pointers; asynchronous on `stream`.
+ * forward is the detectors' own kernels, the backward beside them (kp_head.hip).  Device pointers; asynchronous on `stream`.
  *   eamm_op_kp_head            logits NHWC [B,h,w,Cs] = the "same"-padded 7x7 convolution's output with the `kp` and `jacobian` filters
  *                              stacked: channel k is key point k's logit, channel K + 4 m + c entry c of jacobian map m (njm = 0, 1 or
  *                              K maps).  The reference convolves with padding `pad`: only the window [off, off + oh) x [off, off + ow),

@@ -1,4 +1,4 @@
-"""KPDetector / KPDetector_a as trainable modules: the HIP backward of the heads' reduction (csrc/kp_head_backward.hip,
+"""KPDetector / KPDetector_a as trainable modules: the HIP backward of the heads' reduction (csrc/kp_head.hip,
 ``eamm_amd.kp_ops.kp_head``) and the detectors' differentiable forward, against the oracle differentiated by autograd in float64
 on the CPU (``oracle/eamm_oracle.py``: kp_head, kp_detector_forward, kp_detector_a_forward, generator_forward).
 
