@@ -266,6 +266,18 @@ SIGNATURES = {
                                      C.c_void_p, C.c_void_p]),
     "eamm_op_audio_conv1": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "eamm_op_audio_scale": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p]),
+    # the perceptual loss around its convolutions: pyramid level + normalisation, ReLU + max-pool, L1 (perceptual_ops.py); additive
+    "eamm_op_vgg_input": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                    C.c_void_p, C.c_void_p]),
+    "eamm_op_vgg_input_backward": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                             C.c_int, C.c_void_p, C.c_void_p]),
+    "eamm_op_relu_pool": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "eamm_op_relu_pool_backward": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                             C.c_void_p]),
+    "eamm_op_l1_pair_workspace_floats": (C.c_size_t, [C.c_longlong]),
+    "eamm_op_l1_pair": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                  C.c_void_p]),
+    "eamm_op_l1_pair_backward": (C.c_int, [C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 for _prefix, _config in FAMILIES.items():
     SIGNATURES.update({

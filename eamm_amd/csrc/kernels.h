@@ -413,6 +413,21 @@ hipError_t deconv4s2_dgrad_launch(const float* dy, const float* weight, int B, i
 hipError_t deconv4s2_wgrad_launch(const float* x, const float* dy, int B, int H, int W, int Cin, int Cout, float* dweight, float* dbias,
                                   float* workspace, size_t workspace_floats, hipStream_t s);
 
+// perceptual.hip: the pyramid perceptual loss around its convolutions.  vgg_input: one pyramid level of src [B,3,H,W] (inv 1: a copy)
+// -> out [B,h,w,32] = (level - mean) / std in channels 0..2, zeros above, and / or level [B,3,h,w] (either may be null); its backward
+// gathers g [B,h,w,Cg] (channels 0..2, divided by std) and / or glevel [B,3,h,w] -> dsrc [B,3,H,W].  relu_pool: x = relu(x) in place,
+// pooled (or null) = MaxPool2d(2, 2) of it, sizes floored; backward dx = (y > 0) * (dy + dp at its window's first maximum), dy / dp
+// nullable.  l1_pair: value[0] = weight * mean|a - b| through l1_pair_partials(n) doubles, g = (weight / n) sign(a - b).
+hipError_t vgg_input_launch(const float* src, const float* aa_w, const float* mean, const float* stdv, int B, int H, int W, int inv,
+                            float* out, float* level, hipStream_t s);
+hipError_t vgg_input_backward_launch(const float* g, int Cg, const float* glevel, const float* aa_w, const float* stdv, int B, int H, int W,
+                                     int inv, float* dsrc, hipStream_t s);
+hipError_t relu_pool_launch(float* x /*[B,H,W,C]*/, int B, int H, int W, int C, float* pooled /*[B,H/2,W/2,C]*/, hipStream_t s);
+hipError_t relu_pool_backward_launch(const float* y, const float* dy, const float* dp, int B, int H, int W, int C, float* dx, hipStream_t s);
+int l1_pair_partials(long long n);
+hipError_t l1_pair_launch(const float* a, const float* b, long long n, float weight, float* value, float* g, double* partial, hipStream_t s);
+hipError_t l1_pair_backward_launch(const float* g, long long n, const float* grad_value, float* out, hipStream_t s);
+
 hipError_t one_euro_launch(const float* x, int T, int E, float mincutoff, float beta, float dcutoff, float freq, float scale,
                            float* out, hipStream_t stream, float* state = nullptr, int resume = 0);
 

@@ -899,6 +899,39 @@ int eamm_op_emo_linear(int device, const float* x0, int K0, const float* x1, int
 int eamm_op_audio_conv1(int device, const float* x, const float* w, const float* b, int F, int H, int W, float* out, void* stream);
 int eamm_op_audio_scale(int device, float* x, size_t n, float scale, void* stream);
 
+/*
+ * The pyramid perceptual loss around its convolutions (reference modules/model.py:10-68, :236-248) as DIFFERENTIABLE operators
+ * (perceptual.hip); VGG19's convolutions themselves are eamm_op_conv_dev.  Device pointers; asynchronous on `stream`; no float
+ * atomics anywhere: every result is the same bits from run to run.
+ *   eamm_op_vgg_input            one pyramid level of image NCHW [B,3,H,W]: zero-pad 6, the depth-wise [3,1,13,13] sigma-1.5 buffer,
+ *                                every inv_scale-th row and column (util.py:1044-1052; inv_scale any integer >= 1 dividing H and W,
+ *                                1: the image itself) -> out_nhwc [B,H/s,W/s,32]: (level - mean[c]) / std[c] in channels 0..2, exact
+ *                                zeros in 3..31 (conv1_1's input), and / or level_nchw [B,3,H/s,W/s], the un-normalised level
+ *                                (ImagePyramide's output).  Either output may be NULL, not both.
+ *   eamm_op_vgg_input_backward   grad_nhwc [B,h,w,grad_channels] (channels 0..2 are read; grad_channels a multiple of 4: 32, or 4
+ *                                from conv1_1's data gradient with the filter cut to four input channels) and / or grad_level
+ *                                [B,3,h,w] -> grad_image [B,3,H,W], fully written: the transposed Gaussian as a gather.
+ *   eamm_op_relu_pool            x [B,H,W,C] (C a multiple of 32) = relu(x) IN PLACE; pooled (or NULL) [B,H/2,W/2,C] =
+ *                                MaxPool2d(2, 2) of it, sizes floored: an odd last row or column feeds no window.
+ *   eamm_op_relu_pool_backward   dx = (y > 0) * (dy + dp routed to its window's FIRST maximum in row-major order); dy [B,H,W,C] (the
+ *                                gradient arriving at y itself) and dp [B,H/2,W/2,C] may each be NULL, not both.
+ *   eamm_op_l1_pair              value[0] = weight * mean|a - b| over n elements as a fixed-order two-stage sum (the order depends on
+ *                                n alone), grad[n] = (weight / n) * sign(a - b) with sign(0) = 0; workspace:
+ *                                eamm_op_l1_pair_workspace_floats(n) floats, 16-byte aligned.
+ *   eamm_op_l1_pair_backward     out[n] = grad[n] * grad_value[0] (grad_value on the device).
+ */
+int eamm_op_vgg_input(int device, const float* image, const float* aa_weight, const float* mean, const float* std_, int B, int H, int W,
+                      int inv_scale, float* out_nhwc, float* level_nchw, void* stream);
+int eamm_op_vgg_input_backward(int device, const float* grad_nhwc, int grad_channels, const float* grad_level, const float* aa_weight,
+                               const float* std_, int B, int H, int W, int inv_scale, float* grad_image, void* stream);
+int eamm_op_relu_pool(int device, float* x, int B, int H, int W, int C, float* pooled, void* stream);
+int eamm_op_relu_pool_backward(int device, const float* y, const float* dy, const float* dp, int B, int H, int W, int C, float* dx,
+                               void* stream);
+size_t eamm_op_l1_pair_workspace_floats(long long n);
+int eamm_op_l1_pair(int device, const float* a, const float* b, long long n, float weight, float* value, float* grad, float* workspace,
+                    size_t workspace_floats, void* stream);
+int eamm_op_l1_pair_backward(int device, const float* grad, long long n, const float* grad_value, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
