@@ -1,0 +1,192 @@
+"""Guard-band placement of operator operands: every tensor a test hands to the library is a view into a large buffer (``torch.empty``;
+the arena takes a further one when the first is full), between two bands of a NaN pattern, at the weakest alignment include/eamm_hip.h
+documents.  A store past an output or a workspace damages a
+band, a load past an input brings a NaN into the result, and a kernel that needs more alignment than documented meets a pointer
+that is 16 bytes off a 256-byte boundary.  Plain helper module: no pytest hooks, no fixtures, works on CPU tensors as well.
+
+    arena = Arena("cuda:0", skew=16)
+    x = arena.place(host_tensor, "in")          # a copy of the data
+    y = arena.place((n, h, w, c), "out")        # NaN-filled
+    ws = arena.place(n_floats, "work")          # NaN-filled: a read before the first write shows
+    ... launch ...; torch.cuda.synchronize()
+    arena.check()
+
+``Plain(device)`` has the same call signature and does what the tests did before there was an arena (``.to(device)``,
+``torch.full(nan)``); the case helpers take either as their ``place=`` argument.  Both remember the "out" and "inout" views they
+handed out, in order, so that two runs of one case can be compared bit for bit (``same_outputs``)."""
+import torch
+
+GUARD_WORD = 0x7FC5A5A5          # a quiet NaN with a payload: poisons what reads it, and is recognisable in a dump
+MIN_BAND = 64 << 10              # covers a row-pitch or tile overrun beside a small operand
+MAX_BAND = 16 << 20
+ALIGN = 256                      # a view starts at 0 mod ALIGN, plus the skew
+SKEWS = (0, 16)                  # 16 bytes is what the header documents; nothing below it is ever launched on
+ROLES = ("in", "out", "inout", "work")
+CHUNK = 64 << 20                 # the arena grows by buffers of at least this size; an operand and its bands lie in one of them
+
+
+def band_bytes(own_bytes):
+    """At least the operand's own size (an index one image or one slab too far), at least 64 KiB, at most 16 MiB; whole 256-byte
+    units so that the next view's alignment is independent of it."""
+    n = min(MAX_BAND, max(MIN_BAND, int(own_bytes)))
+    return (n + ALIGN - 1) // ALIGN * ALIGN
+
+
+def _shape_of(t_or_shape):
+    if isinstance(t_or_shape, int):
+        return (t_or_shape,)
+    return tuple(t_or_shape.shape) if isinstance(t_or_shape, torch.Tensor) else tuple(int(s) for s in t_or_shape)
+
+
+def _fill_value(dtype):
+    """What an "out" view starts as outside an arena: NaN, or all-ones bits for an integer type (as the uint8 frame tests do)."""
+    return float("nan") if dtype.is_floating_point else -1 if dtype.is_signed else torch.iinfo(dtype).max
+
+
+def _bits(t):
+    return t.detach().contiguous().reshape(-1).view(torch.uint8)
+
+
+class Plain:
+    """The placement the tests used before: a fresh tensor per operand."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self.placed = 0
+        self.outs = []
+
+    def place(self, t_or_shape, role, dtype=torch.float32, skew=0, name=None):
+        assert role in ROLES, role
+        name = name or f"{role}{self.placed}"
+        self.placed += 1
+        if role in ("in", "inout"):
+            v = t_or_shape.to(self.device)
+        elif role == "out":
+            v = torch.full(_shape_of(t_or_shape), _fill_value(dtype), dtype=dtype, device=self.device)
+        else:
+            v = torch.empty(_shape_of(t_or_shape), dtype=dtype, device=self.device)
+        if role in ("out", "inout"):
+            self.outs.append((name, v))
+        return v
+
+    __call__ = place
+
+
+class Arena:
+    def __init__(self, device, skew=0, chunk=CHUNK):
+        assert skew in SKEWS, skew
+        self.device = torch.device(device)
+        self.skew = skew
+        self.chunk = chunk
+        self.base = None                                # the buffer the next operand goes into
+        self.records = []
+        self.outs = []
+
+    def _grow(self, need):
+        self.base = torch.empty(max(self.chunk, need + ALIGN), dtype=torch.uint8, device=self.device)
+        self.origin = (-self.base.data_ptr()) % ALIGN   # offset of the first 256-byte boundary
+        self.top = self.origin
+
+    @staticmethod
+    def _words(base, lo, hi):
+        return base[lo:hi].view(torch.int32)
+
+    def place(self, t_or_shape, role, dtype=torch.float32, skew=None, name=None):
+        assert role in ROLES, role
+        skew = self.skew if skew is None else skew
+        assert skew in SKEWS, skew
+        data = None
+        if role in ("in", "inout"):
+            data = t_or_shape.detach().contiguous()
+            dtype = data.dtype
+        shape = _shape_of(t_or_shape)
+        numel = 1
+        for s in shape:
+            numel *= s
+        nbytes = numel * torch.empty((), dtype=dtype).element_size()
+        band = band_bytes(nbytes)
+        if self.base is None or self.top + 2 * band + nbytes + 2 * ALIGN > self.base.numel():
+            self._grow(2 * band + nbytes + 2 * ALIGN)
+        lead = self.top                                  # 0 mod 256
+        start = lead + band + skew                       # the leading band is `band + skew` bytes wide
+        end = start + nbytes
+        trail_end = self.origin + (end - self.origin + band + ALIGN - 1) // ALIGN * ALIGN
+        assert trail_end <= self.base.numel()
+        trail = (end + 3) // 4 * 4                       # a byte tensor may end inside a guard word: those bytes are compared apart
+        self.top = trail_end
+        self._words(self.base, lead, trail_end).fill_(_as_int32(GUARD_WORD))       # bands and the view itself: NaN before any data
+        view = self.base[start:end].view(dtype).view(shape)
+        assert view.data_ptr() % ALIGN == skew and view.is_contiguous()
+        if data is not None:
+            view.copy_(data)
+        name = name or f"{role}{len(self.records)}"
+        rec = dict(name=name, role=role, view=view, base=self.base, lead=(lead, start), trail=(trail, trail_end), odd=(end, trail),
+                   odd_bytes=self.base[end:trail].cpu().clone(),
+                   snapshot=_bits(data).cpu().clone() if role == "in" else None)
+        self.records.append(rec)
+        if role in ("out", "inout"):
+            self.outs.append((name, view))
+        return view
+
+    __call__ = place
+
+    def damage(self):
+        """One entry per damaged guard band: operand name, side ("before" / "after"), the first and last damaged 4-byte word counted
+        from the band's low end, and how many words differ."""
+        found = []
+        for rec in self.records:
+            for side, (lo, hi) in (("before", rec["lead"]), ("after", rec["trail"])):
+                bad = self._words(rec["base"], lo, hi) != _as_int32(GUARD_WORD)
+                if bool(bad.any()):
+                    idx = bad.nonzero().reshape(-1)
+                    found.append(dict(name=rec["name"], side=side, first=int(idx[0]), last=int(idx[-1]), count=int(idx.numel()),
+                                      band_words=(hi - lo) // 4))
+            lo, hi = rec["odd"]
+            if hi > lo and not torch.equal(rec["base"][lo:hi].cpu(), rec["odd_bytes"]):
+                found.append(dict(name=rec["name"], side="after, in the bytes that fill its last word", first=0, last=0, count=1, band_words=1))
+        return found
+
+    def changed_inputs(self):
+        return [rec["name"] for rec in self.records
+                if rec["role"] == "in" and not torch.equal(_bits(rec["view"]).cpu(), rec["snapshot"])]
+
+    def nan_outputs(self, nan_ok=()):
+        return [rec["name"] for rec in self.records
+                if rec["role"] == "out" and rec["name"] not in nan_ok and rec["view"].dtype.is_floating_point
+                and bool(torch.isnan(rec["view"]).any())]
+
+    def check(self, nan_ok=()):
+        """After the device has finished (``torch.cuda.synchronize()``): no guard word changed, no "in" view changed, no NaN left in
+        an "out" view other than those named in ``nan_ok``."""
+        lines = []
+        for d in self.damage():
+            where = (f"{(d['band_words'] - d['last']) * 4} to {(d['band_words'] - d['first']) * 4} bytes before its start"
+                     if d["side"] == "before" else f"{d['first'] * 4} to {d['last'] * 4 + 3} bytes past its end")
+            lines.append(f"guard {d['side']} operand {d['name']!r} damaged: {d['count']} words, offsets {d['first']}..{d['last']} "
+                         f"of the band ({where})")
+        lines += [f"input operand {n!r} was written to" for n in self.changed_inputs()]
+        lines += [f"output operand {n!r} holds NaN (unwritten, or computed from a guard word)" for n in self.nan_outputs(nan_ok)]
+        assert not lines, "; ".join(lines)
+
+
+def _as_int32(word):
+    return word - (1 << 32) if word >= 1 << 31 else word
+
+
+def _same_bits(x, y):
+    """Bit-equal, a NaN of any payload equal to a NaN: an element nobody wrote is torch's NaN in one run and a guard word in the other."""
+    if x.shape != y.shape or x.dtype != y.dtype:
+        return False
+    x, y = x.detach().cpu(), y.detach().cpu()
+    if x.dtype.is_floating_point:
+        nx, ny = torch.isnan(x), torch.isnan(y)
+        if not torch.equal(nx, ny):
+            return False
+        x, y = torch.where(nx, torch.zeros_like(x), x), torch.where(ny, torch.zeros_like(y), y)
+    return torch.equal(_bits(x), _bits(y))
+
+
+def same_outputs(a, b):
+    """Names of the "out" / "inout" operands of two placers' runs of one case that are not bit-identical."""
+    assert [n for n, _ in a.outs] == [n for n, _ in b.outs], "the two runs placed different outputs"
+    return [n for (n, x), (_, y) in zip(a.outs, b.outs) if not _same_bits(x, y)]

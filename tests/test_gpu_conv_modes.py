@@ -18,6 +18,7 @@ import torch
 import torch.nn.functional as F
 
 from eamm_amd import _lib
+from guarded import Plain
 
 pytestmark = pytest.mark.gpu
 
@@ -104,12 +105,13 @@ def transform_problem(tile, B, H, W, C, pow2=False, positive=False):
     return x, s, t
 
 
-def run_transform(x, s, t, tile):
+def run_transform(x, s, t, tile, place=None):
     B, H, W, C = x.shape
     P = tile + 2
-    V = torch.full((P * P, B * (H // tile) * (W // tile), C), float("nan"), device=dev())
-    xd = x.to(dev())
-    sd, td = (s.to(dev()), t.to(dev())) if s is not None else (None, None)
+    place = place or Plain(dev())     # .to(dev()) / torch.full(nan); tests/guarded.py's Arena puts the operands between guard bands
+    V = place((P * P, B * (H // tile) * (W // tile), C), "out", name="V")
+    xd = place(x, "in", name="x")
+    sd, td = (place(s, "in", name="pre_scale"), place(t, "in", name="pre_shift")) if s is not None else (None, None)
     assert sd is None or (sd.numel() == C and td.numel() == C)
     _lib.check(_lib.lib().eamm_op_wino_transform(0, ptr(xd), ptr(sd), ptr(td), B, H, W, C, tile, ptr(V), stream()), None)
     torch.cuda.synchronize()
@@ -199,22 +201,24 @@ def conv_ref(x0, x1, w, b, res, up=0, act=0, pool=0, pre=None):
     return F.avg_pool2d(y, 2) if pool else y
 
 
-def run_conv(x0, x1, w, b, res, *, up=0, act=0, pool=0, splitk=0, tile=0, pre=None, second=None, want_nchw=0, split_n=0, plain_entry=False):
+def run_conv(x0, x1, w, b, res, *, up=0, act=0, pool=0, splitk=0, tile=0, pre=None, second=None, want_nchw=0, split_n=0, plain_entry=False,
+             place=None):
     """One eamm_op_conv_ex call (plain_entry: eamm_op_conv) on NHWC device copies of the NCHW problem -> (out, out2 or None) on the CPU"""
     B, C0, H, W = x0.shape
     Cout, cin, ks, _ = w.shape
     C1 = cin - C0
-    d0, d1 = nhwc(x0).to(dev()), (nhwc(x1).to(dev()) if x1 is not None else None)
-    dres = nhwc(res).to(dev()) if res is not None else None
+    place = place or Plain(dev())
+    d0, d1 = place(nhwc(x0), "in", name="in0"), (place(nhwc(x1), "in", name="in1") if x1 is not None else None)
+    dres = place(nhwc(res), "in", name="resid") if res is not None else None
     Ho, Wo = H << up, W << up
     if split_n:
-        out = torch.full((B, Ho, Wo, split_n), float("nan"), device=dev())
-        out2 = torch.full((B, Ho, Wo, 4), float("nan"), device=dev())
+        out = place((B, Ho, Wo, split_n), "out", name="out")
+        out2 = place((B, Ho, Wo, 4), "out", name="out2")
     else:
-        out = torch.full((B, Cout, Ho, Wo) if want_nchw else (B, Ho >> pool, Wo >> pool, Cout), float("nan"), device=dev())
-        out2 = torch.full((B, Ho, Wo, Cout), float("nan"), device=dev()) if second is not None else None
-    pre_d = [v.to(dev()) for v in pre] if pre is not None else [None, None]
-    sec_d = [v.to(dev()) for v in second] if second is not None else [None, None]
+        out = place((B, Cout, Ho, Wo) if want_nchw else (B, Ho >> pool, Wo >> pool, Cout), "out", name="out")
+        out2 = place((B, Ho, Wo, Cout), "out", name="out2") if second is not None else None
+    pre_d = [place(v, "in", name=f"pre{i}") for i, v in enumerate(pre)] if pre is not None else [None, None]
+    sec_d = [place(v, "in", name=f"second{i}") for i, v in enumerate(second)] if second is not None else [None, None]
     assert all(v is None or v.numel() == C0 for v in pre_d) and all(v is None or v.numel() == Cout for v in sec_d)
     wc, bc = w.contiguous(), b.contiguous()
     head = (0, ptr(d0), C0, ptr(d1), C1, B, H, W, up, ptr(wc), ptr(bc), Cout, ks, ks, act, pool, ptr(dres), splitk, tile, ptr(out), 0, None)
@@ -367,17 +371,18 @@ WARP_CASES = {
 }
 
 
-def run_warp(feat, defo, om, n, ns, hf, wf, C, h, w, second=None, plain_entry=False):
-    f_d, d_d = nhwc(feat).to(dev()), defo.contiguous().to(dev())
-    o_d = om[:, 0].contiguous().to(dev())
-    out = torch.full((n, hf, wf, C), float("nan"), device=dev())
+def run_warp(feat, defo, om, n, ns, hf, wf, C, h, w, second=None, plain_entry=False, place=None):
+    place = place or Plain(dev())
+    f_d, d_d = place(nhwc(feat), "in", name="features"), place(defo.contiguous(), "in", name="deformation")
+    o_d = place(om[:, 0].contiguous(), "in", name="occlusion")
+    out = place((n, hf, wf, C), "out", name="out")
     head = (0, ptr(f_d), ptr(d_d), ptr(o_d), n, ns, hf, wf, C, h, w, ptr(out), 0, None)
     if plain_entry:
         _lib.check(_lib.lib().eamm_op_warp(*head, stream()), None)
         torch.cuda.synchronize()
         return out.cpu(), None
-    out2 = torch.full((n, hf, wf, C), float("nan"), device=dev())
-    s2, t2 = (v.to(dev()) for v in second)
+    out2 = place((n, hf, wf, C), "out", name="out2")
+    s2, t2 = (place(v, "in", name=f"second{i}") for i, v in enumerate(second))
     assert s2.numel() == C and t2.numel() == C
     _lib.check(_lib.lib().eamm_op_warp_ex(*head, ptr(out2), ptr(s2), ptr(t2), stream()), None)
     torch.cuda.synchronize()

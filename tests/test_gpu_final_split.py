@@ -16,6 +16,7 @@ import torch
 import torch.nn.functional as F
 
 from eamm_amd import _lib
+from guarded import Plain
 
 pytestmark = pytest.mark.gpu
 
@@ -68,14 +69,15 @@ def reference(x, w, b):
     return torch.sigmoid(F.conv2d(x.double(), w.double(), b.double(), padding=3))
 
 
-def launch(name, x=None, tile_n=4002):
+def launch(name, x=None, tile_n=4002, place=None):
     """One eamm_op_conv call of the case (optionally on another input / tile code) -> NCHW float32 output on the CPU."""
     c = CASES[name]
     x0, w, b, _ = problem(name)
     x = x0 if x is None else x
     dev = torch.device("cuda:0")
-    d = x.permute(0, 2, 3, 1).contiguous().to(dev)
-    out = torch.full((c["B"], 3, c["H"], c["W"]), float("nan"), device=dev)
+    place = place or Plain(dev)     # .to(dev) / torch.full(nan); tests/guarded.py's Arena puts the operands between guard bands
+    d = place(x.permute(0, 2, 3, 1).contiguous(), "in", name="in0")
+    out = place((c["B"], 3, c["H"], c["W"]), "out", name="out")
     wc, bc = w.contiguous(), b.contiguous()
     rc = _lib.lib().eamm_op_conv(0, d.data_ptr(), c["C"], None, 0, c["B"], c["H"], c["W"], 0, wc.data_ptr(), bc.data_ptr(), 3, 7, 7, 2,
                                  0, None, 0, tile_n, out.data_ptr(), 0, None, torch.cuda.current_stream().cuda_stream)
@@ -84,9 +86,9 @@ def launch(name, x=None, tile_n=4002):
     return out.cpu()
 
 
-def measure(name, tile_n=4002):
+def measure(name, tile_n=4002, place=None):
     """-> (max |out - float64|, output)"""
-    out = launch(name, tile_n=tile_n)
+    out = launch(name, tile_n=tile_n, place=place)
     assert torch.isfinite(out).all(), "output has unwritten / non-finite elements"
     return float((out.double() - problem(name)[3]).abs().max()), out
 

@@ -10,16 +10,13 @@ import torch
 import torch.nn.functional as F
 
 from eamm_amd import _op
+from guarded import Plain
 from eamm_amd.weights import antialias_kernel, synthetic_keypoints
 from test_gpu_motion_ops import _close, _reference_front
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 NAN = float("nan")
-
-
-def _nan(*shape):
-    return torch.full(shape, NAN, device=DEV)
 
 
 def _run(name, *args):
@@ -49,13 +46,14 @@ for _c in (64, 96):
 
 
 @pytest.mark.parametrize("cout,ns,H,W", FIRST7)
-def test_first7_matches_conv2d(cout, ns, H, W):
+def test_first7_matches_conv2d(cout, ns, H, W, place=None):
+    place = place or Plain(DEV)
     g = torch.Generator().manual_seed(cout + 7 * H + W)
     x = torch.rand(ns, 3, H, W, generator=g)
     w = (torch.randn(cout, 3, 7, 7, generator=g) * (2.0 / 147) ** 0.5).contiguous()
     b = (0.1 * torch.randn(cout, generator=g)).contiguous()
     want = F.relu(F.conv2d(x.double(), w.double(), b.double(), padding=3)).permute(0, 2, 3, 1)
-    xd, out = x.to(DEV), _nan(ns, H, W, cout)
+    xd, out = place(x, "in"), place((ns, H, W, cout), "out")
     _run("eamm_op_first7", xd, ns, H, W, w, b, cout, out)
     # the bound of the direct fp32-MFMA forms in test_gpu_ops.py: K = 147, only the summation order differs
     _whole(out, want, 2e-5 * max(1.0, float(want.abs().max())), f"first7 Cout {cout} [{ns},{H},{W}]")
@@ -101,23 +99,26 @@ def _check_head(tag, bufs, want, has_occ, with_outs):
     print(tag + ": " + ", ".join(f"{a} {e:.2e}" for a, e in errs.items()) + " of max(1, max|want|) (bound 2e-06)")
 
 
-def _head_buffers(n, K, h, w, with_outs):
-    return (_nan(n, h, w, 2), _nan(n, h, w), _nan(n, K + 1, h, w) if with_outs else None, _nan(n, 1, h, w) if with_outs else None)
+def _head_buffers(n, K, h, w, with_outs, place=None):
+    place = place or Plain(DEV)
+    return (place((n, h, w, 2), "out", name="deformation"), place((n, h, w), "out", name="occlusion"),
+            place((n, K + 1, h, w), "out", name="mask_out") if with_outs else None, place((n, 1, h, w), "out", name="occ_out") if with_outs else None)
 
 
 @pytest.mark.parametrize("n,h,w", [(3, 12, 20), (1, 17, 19), (2, 16, 16)])     # h * w = 240 < 256; 323: a 67-thread tail block; 256
 @pytest.mark.parametrize("K", [1, 10, 30])                                     # K = 30: the occlusion logit is lane 31
-def test_motion_head_inference_kernel(K, n, h, w):
+def test_motion_head_inference_kernel(K, n, h, w, place=None):
+    place = place or Plain(DEV)
     g = torch.Generator().manual_seed(100 * K + h)
     kd, ks = synthetic_keypoints(n, K, seed=4), synthetic_keypoints(n, K, seed=6)
-    rec = _records(kd, ks)
+    rec = place(_records(kd, ks), "in", name="records")
     for has_occ in (0, 1):
         logits = torch.randn(n, h, w, 32, generator=g)
         logits[..., K + 1 + has_occ:] = NAN                                    # the channels above the used ones must not reach an output
         want = _head_reference(logits.double(), kd, ks, K, has_occ)
-        ld = logits.to(DEV)
+        ld = place(logits, "in", name="logits")
         for with_outs in (False, True):                                        # mask_out / occ_out both NULL, both given
-            bufs = _head_buffers(n, K, h, w, with_outs)
+            bufs = _head_buffers(n, K, h, w, with_outs, place)
             _run("eamm_op_motion_head_infer", ld, rec, n, K, h, w, has_occ, *bufs)
             _check_head(f"head K {K} occ {has_occ} outs {with_outs} [{n},{h},{w}]", bufs, want, has_occ, with_outs)
 
@@ -127,12 +128,13 @@ def test_motion_head_inference_kernel(K, n, h, w):
 # partial second tile; three tiles.
 @pytest.mark.parametrize("w", [5, 20, 64, 70, 131])
 @pytest.mark.parametrize("K,has_occ", [(10, 1), (10, 0), (5, 1), (16, 1)])
-def test_motion_head_rowsplit_kernel(K, has_occ, w):
+def test_motion_head_rowsplit_kernel(K, has_occ, w, place=None):
+    place = place or Plain(DEV)
     n, h, PS = 2, 3, 128
     NC = K + 1 + has_occ
     g = torch.Generator().manual_seed(1000 * K + 10 * w + has_occ)
     kd, ks = synthetic_keypoints(n, K, seed=4), synthetic_keypoints(n, K, seed=6)
-    rec = _records(kd, ks)
+    rec = place(_records(kd, ks), "in", name="records")
     part = 0.5 * torch.randn(n, h, w, PS, generator=g)
     part[..., 7 * NC:] = NAN
     bias = torch.randn(NC, generator=g)
@@ -140,14 +142,14 @@ def test_motion_head_rowsplit_kernel(K, has_occ, w):
     taps = F.pad(part[..., :7 * NC].double().reshape(n, h, w, 7, NC), (0, 0, 0, 0, 3, 3))
     logits64 = bias.double() + sum(taps[:, :, dx:dx + w, dx] for dx in range(7))
     want = _head_reference(logits64, kd, ks, K, has_occ)
-    bufs = _head_buffers(n, K, h, w, True)
-    _run("eamm_op_motion_head_rowsplit", part.to(DEV), PS, NC, bias.to(DEV), rec, n, K, h, w, has_occ, *bufs)
+    bufs = _head_buffers(n, K, h, w, True, place)
+    _run("eamm_op_motion_head_rowsplit", place(part, "in", name="part"), PS, NC, place(bias, "in", name="bias"), rec, n, K, h, w, has_occ, *bufs)
     _check_head(f"rowsplit NC {NC} w {w}", bufs, want, has_occ, True)
     # the plain form on the reference logits rounded to fp32 agrees with the row-split form within the same bound
     l32 = torch.full((n, h, w, 32), NAN)
     l32[..., :NC] = logits64.float()
-    plain = _head_buffers(n, K, h, w, True)
-    _run("eamm_op_motion_head_infer", l32.to(DEV), rec, n, K, h, w, has_occ, *plain)
+    plain = _head_buffers(n, K, h, w, True, place)
+    _run("eamm_op_motion_head_infer", place(l32, "in", name="logits"), rec, n, K, h, w, has_occ, *plain)
     _check_head(f"plain on rowsplit's logits NC {NC} w {w}", plain, want, has_occ, True)
     for a, b, what in zip(bufs, plain, ("deformation", "occlusion", "mask_out", "occ_out")):
         if has_occ or what in ("deformation", "mask_out"):
@@ -157,7 +159,8 @@ def test_motion_head_rowsplit_kernel(K, has_occ, w):
 # ---- final_shift_sum_kernel: 128-pixel row tile, 3-pixel halo each side ------------------------------------------------------------
 # W: narrower than the halo; one partial tile; exactly one tile; a seam with a 3-pixel second tile; two seams and a partial last tile
 @pytest.mark.parametrize("W", [5, 20, 128, 131, 300])
-def test_final_shift_sum(W):
+def test_final_shift_sum(W, place=None):
+    place = place or Plain(DEV)
     n, H = 2, 3
     g = torch.Generator().manual_seed(W)
     part = torch.randn(n, H, W, 32, generator=g)
@@ -165,8 +168,8 @@ def test_final_shift_sum(W):
     bias = torch.randn(3, generator=g)
     taps = F.pad(part[..., :21].double().reshape(n, H, W, 7, 3), (0, 0, 0, 0, 3, 3))
     want = torch.sigmoid(bias.double() + sum(taps[:, :, dx:dx + W, dx] for dx in range(7))).permute(0, 3, 1, 2)
-    out = _nan(n, 3, H, W)
-    _run("eamm_op_final_shift_sum", part.to(DEV), bias.to(DEV), n, H, W, out)
+    out = place((n, 3, H, W), "out")
+    _run("eamm_op_final_shift_sum", place(part, "in", name="part"), place(bias, "in", name="bias"), n, H, W, out)
     _whole(out, want, 2e-6, f"final_shift_sum W {W}")              # absolute, as test_fused_final_layer_matches_torch
 
 
@@ -175,14 +178,15 @@ def _u8_reference(p):
     return np.clip(np.rint(p.astype(np.float32) * np.float32(255)), 0, 255).astype(np.uint8)
 
 
-def _to_u8(pred):
+def _to_u8(pred, place=None):
+    place = place or Plain(DEV)
     n, _, H, W = pred.shape
-    out = torch.full((n, H, W, 3), 0xFF, dtype=torch.uint8, device=DEV)
-    _run("eamm_op_to_u8", torch.from_numpy(pred).to(DEV), n, H, W, out)
+    out = place((n, H, W, 3), "out", dtype=torch.uint8)       # 0xFF bytes
+    _run("eamm_op_to_u8", place(torch.from_numpy(pred), "in"), n, H, W, out)
     return out.cpu().numpy()
 
 
-def test_to_u8_is_bit_exact_at_every_rounding_edge():
+def test_to_u8_is_bit_exact_at_every_rounding_edge(place=None):
     """Every k / 255 with its two fp32 neighbours, every half-way value (k + 0.5) / 255 with its two neighbours, signed zero,
     values just and far outside [0, 1], both infinities.  The reference is the same IEEE operations the kernel performs (one fp32
     multiply, round-half-even, clamp), so no tolerance applies.  These 1543 values do not fit the 315 elements of a [3,3,5,7]
@@ -201,7 +205,7 @@ def test_to_u8_is_bit_exact_at_every_rounding_edge():
     pred = pred[rs.permutation(pred.size)].reshape(n, 3, 5, 7)
     with np.errstate(invalid="ignore"):
         want = _u8_reference(pred).transpose(0, 2, 3, 1)
-    got = _to_u8(pred)
+    got = _to_u8(pred, place)
     assert got.shape == want.shape and np.array_equal(got, want), np.argwhere(got != want)[:8]
     assert want.min() == 0 and want.max() == 255 and len(np.unique(want)) == 256
 
@@ -221,7 +225,8 @@ def test_to_u8_sends_nan_to_zero():
 
 
 # ---- warp_image_kernel: grid-stride, grid capped at 16384 blocks -----------------------------------------------------------------
-def _warp_image_case(n, ns, H, W, h, w, src_planes, channels, seed):
+def _warp_image_case(n, ns, H, W, h, w, src_planes, channels, seed, place=None):
+    place = place or Plain(DEV)
     g = torch.Generator().manual_seed(seed)
     src = torch.randn(ns, src_planes, H, W, generator=g)
     ident = torch.stack(torch.meshgrid(torch.linspace(-1, 1, h), torch.linspace(-1, 1, w), indexing="ij")[::-1], -1)
@@ -231,8 +236,8 @@ def _warp_image_case(n, ns, H, W, h, w, src_planes, channels, seed):
         d = F.interpolate(d.permute(0, 3, 1, 2), size=(H, W), mode="bilinear").permute(0, 2, 3, 1)
     s64 = src[:, :channels].double()
     want = F.grid_sample(s64 if ns == n else s64.expand(n, -1, -1, -1), d, mode="bilinear", padding_mode="zeros", align_corners=False)
-    out = _nan(n, channels, H, W)
-    _run("eamm_op_warp_image", src.to(DEV), defo.to(DEV), n, ns, H, W, h, w, src_planes, channels, out)
+    out = place((n, channels, H, W), "out")
+    _run("eamm_op_warp_image", place(src, "in", name="source"), place(defo, "in", name="deformation"), n, ns, H, W, h, w, src_planes, channels, out)
     # as test_warp_features_matches_grid_sample
     _whole(out, want, 2e-5 * max(1.0, float(want.abs().max())), f"warp_image [{n},{ns},{H},{W}] flow {h}x{w} planes {src_planes}/{channels}")
 
@@ -260,13 +265,14 @@ def test_warp_image_grid_stride_remainder():
 
 
 # ---- source_to_nhwc_kernel + the once-per-clip anti-alias launch (source_prepare_launch) -------------------------------------------
-def _source_prepare_case(ns, H, W, inv, seed):
+def _source_prepare_case(ns, H, W, inv, seed, place=None):
+    place = place or Plain(DEV)
     g = torch.Generator().manual_seed(seed)
     src = torch.rand(ns, 3, H, W, generator=g)
     aa = antialias_kernel(3)
     h, w = H // inv, W // inv
-    sd, ad = src.to(DEV), aa.to(DEV)
-    nhwc, small, small_op = _nan(ns, H, W, 32), _nan(ns, h, w, 4), _nan(ns, h, w, 4)
+    sd, ad = place(src, "in", name="source"), place(aa, "in", name="aa_kernel")
+    nhwc, small, small_op = place((ns, H, W, 32), "out", name="nhwc"), place((ns, h, w, 4), "out", name="small"), place((ns, h, w, 4), "out", name="small_op")
     _run("eamm_op_source_prepare", sd, ad, ns, H, W, inv, 32, nhwc, small)
     _run("eamm_op_antialias_down", sd, ad, ns, H, W, inv, small_op)
     assert torch.equal(nhwc.cpu(), F.pad(src.permute(0, 2, 3, 1), (0, 29))), "the NHWC copy is not pad(permute(source))"
@@ -293,13 +299,14 @@ def test_source_prepare_grid_stride_remainder():
 # ---- broadcast_features_kernel.  Its grid is capped at 65536 blocks of 256 float4: a remainder case would need 268 MB, left out. ----
 @pytest.mark.parametrize("ns", [1, 3])
 @pytest.mark.parametrize("with_out2", [True, False])
-def test_broadcast_features(ns, with_out2):
+def test_broadcast_features(ns, with_out2, place=None):
+    place = place or Plain(DEV)
     n, hf, wf, C = 3, 4, 6, 32
     g = torch.Generator().manual_seed(ns)
     feat = torch.randn(ns, hf, wf, C, generator=g)
     s, t = torch.randn(C, generator=g), torch.randn(C, generator=g)
-    out, out2 = _nan(n, hf, wf, C), _nan(n, hf, wf, C) if with_out2 else None
-    _run("eamm_op_broadcast_features", feat.to(DEV), n, ns, hf, wf, C, out, out2, s.to(DEV), t.to(DEV))
+    out, out2 = place((n, hf, wf, C), "out", name="out"), place((n, hf, wf, C), "out", name="out2") if with_out2 else None
+    _run("eamm_op_broadcast_features", place(feat, "in", name="features"), n, ns, hf, wf, C, out, out2, place(s, "in", name="scale"), place(t, "in", name="shift"))
     want = feat if ns == n else feat.expand(n, -1, -1, -1)
     assert torch.equal(out.cpu(), want), "out is not the source frame"
     if with_out2:
@@ -313,10 +320,11 @@ def test_broadcast_features(ns, with_out2):
 
 
 # ---- nchw_to_nhwc_pad_kernel with its `planes` argument: bit-exact -------------------------------------------------------------------
-def _pad_case(B, C, planes, H, W, Cpad, seed):
+def _pad_case(B, C, planes, H, W, Cpad, seed, place=None):
+    place = place or Plain(DEV)
     src = torch.randn(B, planes, H, W, generator=torch.Generator().manual_seed(seed))
-    dst = _nan(B, H, W, Cpad)
-    _run("eamm_op_nchw_to_nhwc_pad", src.to(DEV), B, C, planes, H, W, Cpad, dst)
+    dst = place((B, H, W, Cpad), "out")
+    _run("eamm_op_nchw_to_nhwc_pad", place(src, "in"), B, C, planes, H, W, Cpad, dst)
     assert torch.equal(dst.cpu(), F.pad(src[:, :C].permute(0, 2, 3, 1), (0, Cpad - C)))
 
 
@@ -334,16 +342,18 @@ def test_nchw_to_nhwc_pad_grid_stride_remainder():
 
 # ---- the emotion detector's tail (emotion.hip) -----------------------------------------------------------------------------------------
 @pytest.mark.parametrize("B,P,C", [(1, 1, 64), (9, 16, 512), (3, 49, 96)])      # 64 threads of one block; 18 whole blocks; 288 = a 32-thread tail
-def test_emo_avgpool(B, P, C):
+def test_emo_avgpool(B, P, C, place=None):
+    place = place or Plain(DEV)
     x = torch.randn(B, P, C, generator=torch.Generator().manual_seed(P))
-    out = _nan(B, C)
-    _run("eamm_op_emo_avgpool", x.to(DEV), B, P, C, out)
+    out = place((B, C), "out")
+    _run("eamm_op_emo_avgpool", place(x, "in"), B, P, C, out)
     # a serial fp32 sum of P terms
     _whole(out, x.double().mean(dim=1), P * 2.0 ** -24 * float(x.abs().max()), f"emo_avgpool [{B},{P},{C}]")
 
 
 @pytest.mark.parametrize("B", [1, 9])      # 1260 and 11340 outputs: a 236- and a 76-thread tail block
-def test_emo_embed(B):
+def test_emo_embed(B, place=None):
+    place = place or Plain(DEV)
     rs = np.random.RandomState(B)
     six = rs.uniform(-2, 2, (B, 10, 6)).astype(np.float32)
     six[0, 0, :3] = (0.0, 2.0, -2.0)
@@ -356,8 +366,8 @@ def test_emo_embed(B):
     want = np.stack(parts, axis=2).reshape(B, 1260)        # [B,10,21,6]: d, then (sin, cos) per frequency, each over the six numbers
     value = torch.from_numpy(np.ascontiguousarray(six[..., :2]))
     jac = torch.from_numpy(np.ascontiguousarray(six[..., 2:]))
-    out = _nan(B, 1260)
-    _run("eamm_op_emo_embed", value.to(DEV), jac.to(DEV), B, out)
+    out = place((B, 1260), "out")
+    _run("eamm_op_emo_embed", place(value, "in", name="value"), place(jac, "in", name="jacobian"), B, out)
     got = out.cpu().double().numpy()
     assert np.isfinite(got).all()
     err = np.abs(got - want)
@@ -372,7 +382,8 @@ def test_emo_embed(B):
 # x1 NULL, one block, nb = 1; fcp0 / fa0-like widths with an nb = 1 tail workgroup and a 44-thread tail block; one whole workgroup,
 # odd K and O = 257 = one thread in the second block; two whole workgroups and an nb = 1 tail
 @pytest.mark.parametrize("B,K0,K1,O,relu", [(1, 64, 0, 64, 0), (9, 1260, 512, 300, 1), (8, 33, 7, 257, 1), (17, 128, 64, 256, 0)])
-def test_emo_linear(B, K0, K1, O, relu):
+def test_emo_linear(B, K0, K1, O, relu, place=None):
+    place = place or Plain(DEV)
     g = torch.Generator().manual_seed(K0 + O)
     x0 = torch.randn(B, K0, generator=g)
     x1 = torch.randn(B, K1, generator=g) if K1 else None
@@ -382,15 +393,16 @@ def test_emo_linear(B, K0, K1, O, relu):
     want = x @ wt.double() + bias.double()
     if relu:
         want = F.relu(want)
-    out = _nan(B, O)
-    _run("eamm_op_emo_linear", x0.to(DEV), K0, None if x1 is None else x1.to(DEV), K1, wt.to(DEV), bias.to(DEV), O, B, relu,
-         out)
+    out = place((B, O), "out")
+    _run("eamm_op_emo_linear", place(x0, "in", name="x0"), K0, None if x1 is None else place(x1, "in", name="x1"), K1, place(wt, "in", name="wt"),
+         place(bias, "in", name="bias"), O, B, relu, out)
     _whole(out, want, 2e-5 * max(1.0, float(want.abs().max())), f"emo_linear [{B},{K0}+{K1}] -> {O} relu {relu}")
 
 
 # ---- the audio front end (audio.hip) -------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("Fr,H,W", [(1, 28, 12), (5, 28, 12), (2, 3, 5)])       # the network's window, one and five; a map where every pixel is border
-def test_audio_conv1(Fr, H, W):
+def test_audio_conv1(Fr, H, W, place=None):
+    place = place or Plain(DEV)
     g = torch.Generator().manual_seed(Fr + H)
     x = 2 * torch.rand(Fr, H, W, generator=g) - 1
     w = 0.5 * torch.randn(64, 1, 3, 3, generator=g) * (2.0 / 9) ** 0.5
@@ -400,17 +412,18 @@ def test_audio_conv1(Fr, H, W):
     assert float((w.abs().sum(dim=(1, 2, 3)) + b.abs()).max()) < 3.3
     want = F.relu(F.conv2d(x[:, None].double(), w.double(), b.double(), padding=1)).permute(0, 2, 3, 1)
     wt = w.reshape(64, 9).t().contiguous()                                      # [9][64], tap-major: the engine's layout
-    out = _nan(Fr, H, W, 64)
-    _run("eamm_op_audio_conv1", x.to(DEV), wt.to(DEV), b.to(DEV), Fr, H, W, out)
+    out = place((Fr, H, W, 64), "out")
+    _run("eamm_op_audio_conv1", place(x, "in", name="x"), place(wt, "in", name="wt"), place(b, "in", name="bias"), Fr, H, W, out)
     _whole(out, want, 2e-6, f"audio_conv1 [{Fr},{H},{W}]")
 
 
 @pytest.mark.parametrize("n", [1, 255, 257, 100003])                            # one thread; a 255-thread block; one thread past a block; 391 blocks
-def test_audio_scale_is_bit_exact(n):
+def test_audio_scale_is_bit_exact(n, place=None):
+    place = place or Plain(DEV)
     s = 1.6
     x = torch.randn(n + 64, generator=torch.Generator().manual_seed(n))
     x[n:] = 1.0                                                                  # the guard i < n: the floats behind the vector stay
-    xd = x.to(DEV)
+    xd = place(x, "inout")
     _run("eamm_op_audio_scale", xd, n, s)
     want = x.numpy().copy()
     want[:n] = want[:n] * np.float32(s)

@@ -5,6 +5,7 @@ import torch
 import torch.nn.functional as F
 
 from eamm_amd import _lib
+from guarded import Plain
 
 pytestmark = pytest.mark.gpu
 
@@ -29,7 +30,7 @@ def nhwc(t):
     return t.permute(0, 2, 3, 1).contiguous()
 
 
-def run_case(B, H, W, C0, C1, Cout, ks, kw=0, up=0, act=0, pool=0, resid=False, splitk=0, tile_n=0, seed=0, zero_bias=False):
+def run_case(B, H, W, C0, C1, Cout, ks, kw=0, up=0, act=0, pool=0, resid=False, splitk=0, tile_n=0, seed=0, zero_bias=False, place=None):
     kw = kw or ks
     g = torch.Generator().manual_seed(seed)
     cin = C0 + C1
@@ -43,10 +44,11 @@ def run_case(B, H, W, C0, C1, Cout, ks, kw=0, up=0, act=0, pool=0, resid=False, 
     res = torch.randn(B, Cout, Ho, Wo, generator=g) if resid else None
     want = ref_conv(in0, in1, w, b, ks, kw, up, act, pool, res)
     dev = torch.device("cuda:0")
-    d0 = nhwc(in0).to(dev)
-    d1 = nhwc(in1).to(dev) if C1 else None
-    dres = nhwc(res).to(dev) if resid else None
-    out = torch.full((B, Ho >> pool, Wo >> pool, Cout), float("nan"), device=dev)
+    place = place or Plain(dev)     # .to(dev) / torch.full(nan); tests/guarded.py's Arena puts the operands between guard bands
+    d0 = place(nhwc(in0), "in", name="in0")
+    d1 = place(nhwc(in1), "in", name="in1") if C1 else None
+    dres = place(nhwc(res), "in", name="resid") if resid else None
+    out = place((B, Ho >> pool, Wo >> pool, Cout), "out", name="out")
     L = _lib.lib()
     wc, bc = w.contiguous(), b.contiguous()
     rc = L.eamm_op_conv(0, d0.data_ptr(), C0, d1.data_ptr() if C1 else None, C1, B, H, W, up,
@@ -215,7 +217,7 @@ def test_conv_linearity_property():
 
 
 # ---- the HBM-bound kernel of the path on its own: feature warp x occlusion (reference generator.py:50-57, 79-84) -------
-def _warp_case(n, ns, hf, wf, C, h, w, occ=True, seed=0, poison=False):
+def _warp_case(n, ns, hf, wf, C, h, w, occ=True, seed=0, poison=False, place=None):
     g = torch.Generator().manual_seed(seed)
     feat = torch.randn(ns, C, hf, wf, generator=g)
     if poison:   # a non-finite BORDER value must not leak into samples whose out-of-range corner is zero padding
@@ -234,9 +236,10 @@ def _warp_case(n, ns, hf, wf, C, h, w, occ=True, seed=0, poison=False):
     if occ:
         want = want * o
     dev = torch.device("cuda:0")
-    f_d, d_d = nhwc(feat).to(dev), defo.contiguous().to(dev)
-    o_d = om[:, 0].contiguous().to(dev) if occ else None
-    out = torch.full((n, hf, wf, C), float("nan"), device=dev)
+    place = place or Plain(dev)
+    f_d, d_d = place(nhwc(feat), "in", name="features"), place(defo.contiguous(), "in", name="deformation")
+    o_d = place(om[:, 0].contiguous(), "in", name="occlusion") if occ else None
+    out = place((n, hf, wf, C), "out", name="out")
     rc = _lib.lib().eamm_op_warp(0, f_d.data_ptr(), d_d.data_ptr(), o_d.data_ptr() if occ else None, n, ns, hf, wf, C, h, w,
                                  out.data_ptr(), 0, None, torch.cuda.current_stream().cuda_stream)
     _lib.check(rc, None)
@@ -276,15 +279,16 @@ def test_warp_zero_padding_is_exact_beside_a_non_finite_border_pixel():
     ("many_rows", 5, 128, 128, 64),           # more tile rows (40) than ... not than CUs; several images
     ("more_rows_than_cus", 20, 256, 16, 32),  # 320 tile rows on <= 256 persistent workgroups: a workgroup walks two rows
 ])
-def test_fused_final_layer_matches_torch(name, B, H, W, C):
+def test_fused_final_layer_matches_torch(name, B, H, W, C, place=None):
     g = torch.Generator().manual_seed(hash(name) % 1000)
     x = torch.randn(B, C, H, W, generator=g)
     w = torch.randn(3, C, 7, 7, generator=g) * (2.0 / (C * 49)) ** 0.5
     b = 0.1 * torch.randn(3, generator=g)
     want = torch.sigmoid(F.conv2d(x, w, b, padding=3))
     dev = torch.device("cuda:0")
-    xd = nhwc(x).to(dev)
-    out = torch.full((B, 3, H, W), float("nan"), device=dev)
+    place = place or Plain(dev)
+    xd = place(nhwc(x), "in", name="in0")
+    out = place((B, 3, H, W), "out", name="out")
     wc, bc = w.contiguous(), b.contiguous()
     rc = _lib.lib().eamm_op_conv(0, xd.data_ptr(), C, None, 0, B, H, W, 0, wc.data_ptr(), bc.data_ptr(), 3, 7, 7, 2, 0, None, 0, 4002,
                                  out.data_ptr(), 0, None, torch.cuda.current_stream().cuda_stream)

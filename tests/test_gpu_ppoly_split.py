@@ -17,6 +17,7 @@ import torch
 import torch.nn.functional as F
 
 from eamm_amd import _lib
+from guarded import Plain
 
 pytestmark = pytest.mark.gpu
 
@@ -79,15 +80,16 @@ def reference(x, w, b, act):
     return F.relu(want) if act else want
 
 
-def launch(name, x=None, tile_n=3003):
+def launch(name, x=None, tile_n=3003, place=None):
     """One eamm_op_conv call of the case (optionally on another input / tile code) -> NHWC float32 output on the CPU."""
     c = CASES[name]
     x0, w, b, _ = problem(name)
     x = x0 if x is None else x
     dev = torch.device("cuda:0")
-    d0 = nhwc(x[:, :c["C0"]]).to(dev)
-    d1 = nhwc(x[:, c["C0"]:]).to(dev) if c["C1"] else None
-    out = torch.full((c["B"], 2 * c["H"], 2 * c["W"], c["Cout"]), float("nan"), device=dev)
+    place = place or Plain(dev)     # .to(dev) / torch.full(nan); tests/guarded.py's Arena puts the operands between guard bands
+    d0 = place(nhwc(x[:, :c["C0"]]), "in", name="in0")
+    d1 = place(nhwc(x[:, c["C0"]:]), "in", name="in1") if c["C1"] else None
+    out = place((c["B"], 2 * c["H"], 2 * c["W"], c["Cout"]), "out", name="out")
     wc, bc = w.contiguous(), b.contiguous()
     rc = _lib.lib().eamm_op_conv(0, d0.data_ptr(), c["C0"], d1.data_ptr() if d1 is not None else None, c["C1"], c["B"], c["H"], c["W"],
                                  1, wc.data_ptr(), bc.data_ptr(), c["Cout"], 3, 3, c.get("act", 0), 0, None, c.get("splitk", 0),
@@ -97,10 +99,10 @@ def launch(name, x=None, tile_n=3003):
     return out.cpu()
 
 
-def measure(name, tile_n=3003):
+def measure(name, tile_n=3003, place=None):
     """-> (max |out - float64| / max |float64|, max |out - float64|, max |float64|, output)"""
     want = problem(name)[3]
-    out = launch(name, tile_n=tile_n)
+    out = launch(name, tile_n=tile_n, place=place)
     assert torch.isfinite(out).all(), "output has unwritten / non-finite elements"
     err = float((out.permute(0, 3, 1, 2).double() - want).abs().max())
     top = float(want.abs().max())

@@ -15,6 +15,7 @@ import torch
 import torch.nn.functional as F
 
 from eamm_amd import _lib
+from guarded import Plain
 
 pytestmark = pytest.mark.gpu
 
@@ -68,15 +69,16 @@ def problem(name):
     return x, w, b, res, want
 
 
-def launch(name, x=None, tile_n=None):
+def launch(name, x=None, tile_n=None, place=None):
     """One eamm_op_conv call of the case (optionally on another input / tile code) -> NHWC float32 output on the CPU."""
     c = CASES[name]
     x0, w, b, res, _ = problem(name)
     x = x0 if x is None else x
     dev = torch.device("cuda:0")
-    dx = nhwc(x).to(dev)
-    dres = nhwc(res).to(dev) if res is not None else None
-    out = torch.full((c["B"], c["H"], c["W"], c["Cout"]), float("nan"), device=dev)
+    place = place or Plain(dev)     # .to(dev) / torch.full(nan); tests/guarded.py's Arena puts the operands between guard bands
+    dx = place(nhwc(x), "in", name="in0")
+    dres = place(nhwc(res), "in", name="resid") if res is not None else None
+    out = place((c["B"], c["H"], c["W"], c["Cout"]), "out", name="out")
     wc, bc = w.contiguous(), b.contiguous()
     rc = _lib.lib().eamm_op_conv(0, dx.data_ptr(), c["Cin"], None, 0, c["B"], c["H"], c["W"], 0, wc.data_ptr(), bc.data_ptr(),
                                  c["Cout"], 3, 3, c.get("act", 0), 0, dres.data_ptr() if dres is not None else None, 0,
@@ -86,10 +88,10 @@ def launch(name, x=None, tile_n=None):
     return out.cpu()
 
 
-def measure(name):
+def measure(name, place=None):
     """-> (max |out - float64| / max |float64|, max |out - float64|, max |float64|, output)"""
     want = problem(name)[4]
-    out = launch(name)
+    out = launch(name, place=place)
     assert torch.isfinite(out).all(), "output has unwritten / non-finite elements"
     err = float((out.permute(0, 3, 1, 2).double() - want).abs().max())
     top = float(want.abs().max())
