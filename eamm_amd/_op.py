@@ -1,4 +1,5 @@
-"""The one way Python calls a handle-less operator entry (``eamm_op_*``, include/eamm_hip.h): every entry takes the device index
+"""The one way Python calls a handle-less operator entry (``eamm_op_*``, or ``eamm_disc_*`` with ``family="disc"``;
+include/eamm_hip.h): every entry takes the device index
 first and the stream last, a workspace-taking one its ``(workspace, workspace_floats)`` pair in front of the stream, and reports
 through ``eamm_last_error(NULL)``.  The handle families go through ``_handle.Handle`` instead."""
 from __future__ import annotations
@@ -26,19 +27,20 @@ def need_gpu(t: torch.Tensor, module: str, what: str):
         raise RuntimeError(f"{what}: float32 tensors only, got {t.dtype}")
 
 
-def call(name: str, dev: torch.device, *args, work: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None):
-    """``eamm_op_<name>(dev.index, *args[, work, work.numel()], stream)`` on ``dev``: tensors (and None) among ``args`` are passed
+def call(name: str, dev: torch.device, *args, work: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None,
+         family: str = "op"):
+    """``eamm_<family>_<name>(dev.index, *args[, work, work.numel()], stream)`` on ``dev``: tensors (and None) among ``args`` are passed
     by address, everything else as it is; ``stream`` defaults to the current stream of ``dev``.  Enqueues only; a non-zero return
     raises ``EammError`` with the library's message."""
     argv = [a if type(a) in _PLAIN else C.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a for a in args]
     if work is not None:
         argv += (ptr(work), work.numel())
     with torch.cuda.device(dev):
-        _lib.check(getattr(_lib.lib(), "eamm_op_" + name)(dev.index, *argv, stream_ptr(dev, stream)), None)
+        _lib.check(getattr(_lib.lib(), f"eamm_{family}_{name}")(dev.index, *argv, stream_ptr(dev, stream)), None)
 
 
-def workspace(name: str, dev: torch.device, *dims: int) -> torch.Tensor:
-    """An uninitialised workspace of ``eamm_op_<name>_workspace_floats(*dims)`` floats on ``dev`` (one float where that is 0: the
+def workspace(name: str, dev: torch.device, *dims: int, family: str = "op") -> torch.Tensor:
+    """An uninitialised workspace of ``eamm_<family>_<name>_workspace_floats(*dims)`` floats on ``dev`` (one float where that is 0: the
     entry then refuses the shape itself)."""
-    n = getattr(_lib.lib(), f"eamm_op_{name}_workspace_floats")(*dims)
+    n = getattr(_lib.lib(), f"eamm_{family}_{name}_workspace_floats")(*dims)
     return torch.empty(max(1, n), dtype=torch.float32, device=dev)

@@ -149,11 +149,13 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs p) {
 // [B,2H,2W,Cg] read at (2y + ky - pad, 2x + kx - pad) (zeros outside the map), whose channels are D's columns.  The stride-2
 // convolution's weight gradient has dense = dY, gathered = x, pad = ks / 2; ConvTranspose2d(k4, s2, p1)'s has dense = x, gathered = dY,
 // ks = 4, pad = 1.  The row address is recomputed per chunk (these layers are small; conv_wgrad_kernel's incremental form is for
-// the generator's).
+// the generator's).  The stride and the gathered map's size are arguments: the discriminator's valid 4x4 convolution has stride 1,
+// pad 0 and a gathered map [B,H+3,W+3,Cg] (dense = dY, gathered = x).
 struct StridedWgradArgs {
     const float* dense;      // [B,H,W,Cd]
-    const float* gathered;   // [B,2H,2W,Cg]
+    const float* gathered;   // [B,Hg,Wg,Cg]: Hg = 2H, Wg = 2W for the stride-2 pairs
     int H, W, Cd, Cg, ks, pad;
+    int stride, Hg, Wg;
     int P;                   // B*H*W
     int per_split;           // pixels per split (a multiple of the 32-pixel chunk)
     int splits, mt, nt;      // pixel splits, Cd tiles, Cg tiles (64 each)
@@ -175,7 +177,7 @@ __global__ __launch_bounds__(256) void strided_wgrad_kernel(const StridedWgradAr
     const int split = L;
     const int dyo = tap / p.ks - p.pad, dxo = tap % p.ks - p.pad;
     const int p0 = split * p.per_split, p1 = min(p.P, p0 + p.per_split);
-    const int Hg = 2 * p.H, Wg = 2 * p.W;
+    const int Hg = p.Hg, Wg = p.Wg;
     f32x16 acc;
     static_for<16>([&](auto rc) { acc[decltype(rc)::value] = 0.f; });
     const int lq = tid & 15, lr = tid >> 4;
@@ -192,7 +194,7 @@ __global__ __launch_bounds__(256) void strided_wgrad_kernel(const StridedWgradAr
             if (pp < p1) {
                 const int x = pp % p.W, t = pp / p.W;
                 const int y = t % p.H, b = t / p.H;
-                const int gy = 2 * y + dyo, gx = 2 * x + dxo;
+                const int gy = p.stride * y + dyo, gx = p.stride * x + dxo;
                 if (cd_ok) ra[h2] = *reinterpret_cast<const f32x4*>(p.dense + (size_t)pp * p.Cd + cd);
                 if (cg_ok && (unsigned)gy < (unsigned)Hg && (unsigned)gx < (unsigned)Wg)
                     rb[h2] = *reinterpret_cast<const f32x4*>(p.gathered + (((size_t)b * Hg + gy) * Wg + gx) * p.Cg + cg);
@@ -432,6 +434,15 @@ __global__ __launch_bounds__(256) void conv_bias_grad_final_kernel(const float* 
 
 size_t conv_wgrad_workspace_floats(int B, int H, int W, int Cin, int Cout, int kh, int kw);
 
+size_t conv_bias_grad_workspace_floats(int Cout) { return (size_t)BIAS_PARTS * Cout; }
+
+hipError_t conv_bias_grad_launch(const float* dy, long long P, int Cout, float* dbias, float* workspace, hipStream_t s) {
+    const int parts = (int)std::min<long long>(BIAS_PARTS, (P + 63) / 64);
+    hipLaunchKernelGGL(conv_bias_grad_partial_kernel, dim3(parts), dim3(256), 0, s, dy, P, Cout, workspace);
+    hipLaunchKernelGGL(conv_bias_grad_final_kernel, dim3((Cout + 63) / 64), dim3(256), 0, s, workspace, parts, Cout, dbias);
+    return hipGetLastError();
+}
+
 hipError_t conv_wgrad_reduce_launch(const float* partial, int splits, int taps, int Mpad, int Npad, int Cout, int Cin, float* dw, hipStream_t s) {
     const size_t total = (size_t)Cout * Cin * taps;
     hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 65535)), dim3(256), 0, s, partial, splits,
@@ -470,7 +481,7 @@ StridedWgradPlan strided_wgrad_plan(int P, int rows, int cols, int taps) {
 size_t strided_wgrad_workspace_floats(int P, int rows, int cols, int ks) { return strided_wgrad_plan(P, rows, cols, ks * ks).floats; }
 
 hipError_t strided_wgrad_launch(const float* dense, const float* gathered, int B, int H, int W, int rows, int cols, int ks, int pad,
-                                float* dweight, float* workspace, hipStream_t s) {
+                                float* dweight, float* workspace, hipStream_t s, int stride, int Hg, int Wg) {
     const int taps = ks * ks;
     const StridedWgradPlan pl = strided_wgrad_plan(B * H * W, rows, cols, taps);
     StridedWgradArgs a{};
@@ -482,6 +493,9 @@ hipError_t strided_wgrad_launch(const float* dense, const float* gathered, int B
     a.Cg = cols;
     a.ks = ks;
     a.pad = pad;
+    a.stride = stride;
+    a.Hg = Hg > 0 ? Hg : 2 * H;
+    a.Wg = Wg > 0 ? Wg : 2 * W;
     a.P = B * H * W;
     a.per_split = pl.per_split;
     a.splits = pl.splits;
@@ -568,12 +582,7 @@ hipError_t conv_wgrad_launch(const float* x, const float* dy, int B, int H, int 
         else hipLaunchKernelGGL(conv_wgrad_kernel, grid, dim3(256), 0, s, a);
         if (hipError_t e = conv_wgrad_reduce_launch(workspace, a.splits, taps, a.mt * 64, a.nt * 64, Cout, Cin, dweight, s); e != hipSuccess) return e;
     }
-    if (dbias != nullptr) {
-        const long long P = (long long)B * H * W;
-        const int parts = (int)std::min<long long>(BIAS_PARTS, (P + 63) / 64);
-        hipLaunchKernelGGL(conv_bias_grad_partial_kernel, dim3(parts), dim3(256), 0, s, dy, P, Cout, bias_part);
-        hipLaunchKernelGGL(conv_bias_grad_final_kernel, dim3((Cout + 63) / 64), dim3(256), 0, s, bias_part, parts, Cout, dbias);
-    }
+    if (dbias != nullptr) return conv_bias_grad_launch(dy, (long long)B * H * W, Cout, dbias, bias_part, s);
     return hipGetLastError();
 }
 

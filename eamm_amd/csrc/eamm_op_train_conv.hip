@@ -15,7 +15,7 @@ struct ConvDevPlan {
 };
 bool conv_dev_plan(int B, int H, int W, int Cin, int Cout, int kh, int kw, ConvDevPlan* P) {
     if (B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || Cin % CONV_BK || (Cout & 3)) return false;
-    if (!((kh == 3 && kw == 3) || (kh == 7 && kw == 7))) return false;
+    if (!((kh == 3 && kw == 3) || (kh == 7 && kw == 7) || (kh == 1 && kw == 1))) return false;   // 1x1: the discriminator's prediction layer
     const long long Mq = (long long)B * (H / 4) * (W / 4);
     // F(4x4,3x3) where the bottleneck's kernel applies and the tile count fills the chip; else the register-staged implicit GEMM
     static const int wino_off = knob_int("EAMM_CONV_DEV_WINO4", 1) == 0;
@@ -102,7 +102,7 @@ int eamm_op_conv_dev(int device, const float* x, int B, int H, int W, int Cin, c
                      int kw, int transposed, float* out, float* workspace, size_t workspace_floats, void* stream_) {
     ConvDevPlan P;
     if (!x || !weight || !out || !workspace || !conv_dev_plan(B, H, W, Cin, Cout, kh, kw, &P))
-        return fail(nullptr, EAMM_ERR_ARG, "eamm_op_conv_dev: bad argument (3x3 or 7x7, Cin a multiple of 32, Cout of 4)");
+        return fail(nullptr, EAMM_ERR_ARG, "eamm_op_conv_dev: bad argument (1x1, 3x3 or 7x7, Cin a multiple of 32, Cout of 4)");
     const size_t need = P.packed + P.bias + P.aux + P.zbuf;
     if (!op_workspace_ok(workspace, workspace_floats, need, true))
         return fail(nullptr, EAMM_ERR_ARG, "eamm_op_conv_dev: workspace too small or misaligned (%zu floats needed)", need);

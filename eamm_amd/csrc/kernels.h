@@ -293,10 +293,37 @@ hipError_t conv_wgrad_reduce_launch(const float* partial, int splits, int taps, 
 // dense [B,H,W,rows] of dense[y, x][r] * gathered[2y + ky - pad, 2x + kx - pad][c], gathered [B,2H,2W,cols] (zeros outside), ks x ks taps;
 // one GEMM per tap, split over the pixels, the slabs summed in slice order into dweight [rows][cols][ks][ks].  workspace: the query's
 // floats (P = B*H*W), 16-byte aligned.  conv_s2_wgrad_launch: dense = dY, gathered = x, pad = ks / 2; deconv4s2_wgrad_launch: dense = x,
-// gathered = dY, ks = 4, pad = 1.
+// gathered = dY, ks = 4, pad = 1.  With `stride`, `Hg`, `Wg` given the gathered map is [B,Hg,Wg,cols] read at (stride y + ky - pad,
+// stride x + kx - pad): disc_conv4_wgrad_launch has stride 1, pad 0, Hg = H + 3, Wg = W + 3.
 size_t strided_wgrad_workspace_floats(int P, int rows, int cols, int ks);
 hipError_t strided_wgrad_launch(const float* dense, const float* gathered, int B, int H, int W, int rows, int cols, int ks, int pad,
-                                float* dweight, float* workspace, hipStream_t s);
+                                float* dweight, float* workspace, hipStream_t s, int stride = 2, int Hg = 0, int Wg = 0);
+// db[Cout] = sum over the P pixels of dy [P][Cout] (Cout a multiple of 4, <= 1024), two fixed-order stages; workspace: the query's floats
+size_t conv_bias_grad_workspace_floats(int Cout);
+hipError_t conv_bias_grad_launch(const float* dy, long long P, int Cout, float* dbias, float* workspace, hipStream_t s);
+
+// disc_conv4.hip: the discriminator's valid 4x4 convolution (NHWC, OIHW device filter packed into `workspace` on every call).
+// pad = 0, transposed = 0: the forward; pad = 3, transposed = 1: the data gradient (x = dY, weight = the forward filter).  thin = 4 | 8 |
+// 16: the side with few channels is [.,thin] floats per pixel (forward: the input, Cin = the filter's channels <= thin; data gradient:
+// the output, Cout = the filter's channels <= thin, zeros above).  *_refusal: null, or why the shape is refused.
+const char* disc_conv4_refusal(int B, int H, int W, int Cin, int Cout, int pad, int transposed, int thin);
+size_t disc_conv4_workspace_floats(int B, int H, int W, int Cin, int Cout, int pad, int transposed, int thin);
+hipError_t disc_conv4_launch(const float* x, int B, int H, int W, int Cin, const float* weight, const float* bias, int Cout, int pad,
+                             int transposed, int thin, float* out, float* workspace, hipStream_t s);
+// x [B,H,W,Cx] (Cx 4 | 8 | 16 | a multiple of 32), dy [B,H-3,W-3,Cout] -> dweight [Cout,Cx,4,4], dbias [Cout] or null
+const char* disc_conv4_wgrad_refusal(int B, int H, int W, int Cx, int Cout);
+size_t disc_conv4_wgrad_workspace_floats(int B, int H, int W, int Cx, int Cout);
+hipError_t disc_conv4_wgrad_launch(const float* x, const float* dy, int B, int H, int W, int Cx, int Cout, float* dweight, float* dbias,
+                                   float* workspace, hipStream_t s);
+// disc_norm.hip: InstanceNorm2d(affine) (norm = 1) + LeakyReLU(0.2) + AvgPool2d(2) (pool = 1, floor sizes) on x [B,H,W,C], and its
+// backward from the saved x and stats [B,C,2] doubles = (mean, rstd).  workspace: disc_norm_workspace_floats floats, 16-byte aligned.
+const char* disc_norm_refusal(int B, int H, int W, int C, int norm, int pool);
+size_t disc_norm_workspace_floats(int B, int H, int W, int C, int norm, int backward);
+hipError_t disc_norm_act_pool_launch(const float* x, const float* gamma, const float* beta, int B, int H, int W, int C, int norm, int pool,
+                                     float eps, double* stats, float* out, float* workspace, hipStream_t s);
+hipError_t disc_norm_act_pool_backward_launch(const float* x, const double* stats, const float* gamma, const float* beta, const float* dout,
+                                              int B, int H, int W, int C, int norm, int pool, float* dx, float* dgamma, float* dbeta,
+                                              float* workspace, hipStream_t s);
 
 // conv_pack_dev.hip: the packings of conv_pack_host (register-staged kernel) and wino4_pack_host from a DEVICE OIHW tensor;
 // transposed = 1 reads the forward filter [Cin][Cout][kh][kw] transposed and flipped (the data gradient's filter)

@@ -632,7 +632,7 @@ int eamm_op_warp_backward(int device, const float* feat, const float* deformatio
  * transformed input: a quarter of the multiplies), one GEMM per filter ROW for maps with W % 32 == 0, else one per tap.
  * Cin, Cout multiples of 4, Cout <= 1024; kh, kw odd and at most 7.  The DATA gradient of such a convolution is eamm_op_conv on grad_out with the filter transposed and
  * flipped (weight.permute(1,0,2,3).flip(2,3)), which eamm_amd/autograd_ops.py does. */
-/* Stride-1 "same" 3x3 / 7x7 convolution with DEVICE parameters (the training path: they change every optimiser step):
+/* Stride-1 "same" 1x1 / 3x3 / 7x7 convolution with DEVICE parameters (the training path: they change every optimiser step):
  * x NHWC [B,H,W,Cin], weight OIHW [Cout,Cin,kh,kw] and bias [Cout] (or NULL) in device memory, out NHWC [B,H,W,Cout].  The filter
  * is packed on the device into `workspace` (eamm_op_conv_dev_workspace_floats floats, 16-byte aligned) and the evaluation
  * path's kernels run on it: F(4x4,3x3) Winograd where the bottleneck's kernel applies (3x3, Cin % 64 == 0, H and W multiples of
@@ -931,6 +931,49 @@ size_t eamm_op_l1_pair_workspace_floats(long long n);
 int eamm_op_l1_pair(int device, const float* a, const float* b, long long n, float weight, float* value, float* grad, float* workspace,
                     size_t workspace_floats, void* stream);
 int eamm_op_l1_pair_backward(int device, const float* grad, long long n, const float* grad_value, float* out, void* stream);
+
+/*
+ * The discriminator (reference modules/discriminator.py) as DIFFERENTIABLE operators, a family of its own: eamm_disc_* (disc_conv4.hip,
+ * disc_norm.hip).  Device pointers, NHWC fp32 maps, 16-byte aligned; asynchronous on `stream`; the operator convention (device index
+ * first, workspace pair before the stream, errors through eamm_last_error(NULL)).  No float atomics anywhere: every sum has a fixed
+ * order, every result is the same bits from run to run.  The 512 -> 1 prediction layer is eamm_op_conv_dev / eamm_op_conv_wgrad (1x1).
+ *   eamm_disc_conv4              valid (unpadded) stride-1 4x4 convolution: x [B,H,W,Cin], weight OIHW [Cout,Cin,4,4] and bias [Cout]
+ *                                (or NULL) -> out [B,H+2pad-3,W+2pad-3,Cout] on the fp32 matrix cores (v_mfma_f32_32x32x2_f32); the
+ *                                filter is packed into `workspace` on every call.  pad = 0, transposed = 0: the forward.  pad = 3,
+ *                                transposed = 1: the DATA GRADIENT -- x is grad_out [B,H,W,Cin = the forward's Cout], weight the FORWARD
+ *                                filter [Cin,Cout,4,4], read transposed over (out, in) and flipped over (y, x) while packing.  Cin and
+ *                                Cout multiples of 32, H and W at least 4 (forward; the data gradient takes any grad_out).  thin = 4 | 8 | 16: the side with few channels (the image,
+ *                                or the image with the key-point heat maps) has `thin` floats per pixel.  Forward: x [B,H,W,thin]
+ *                                with exact zeros above the real channels, weight [Cout,Cin,4,4] with 1 <= Cin <= thin (K = 16 thin
+ *                                instead of 16 x 32: the kx taps of a filter row are contiguous in such a map).  Data gradient:
+ *                                weight [Cin,Cout,4,4] with 1 <= Cout <= thin, out [B,H+3,W+3,thin] with zeros above Cout (runs the
+ *                                ordinary form on a 32-column tile).
+ *   eamm_disc_conv4_wgrad        x [B,H,W,Cin] (Cin 4 | 8 | 16 for a thin input, else a multiple of 32), grad_out [B,H-3,W-3,Cout]
+ *                                -> grad_weight [Cout,Cin,4,4] (or NULL: the bias gradient alone), grad_bias [Cout] (or NULL): one GEMM per tap with K = the pixels split
+ *                                over workgroups, the slabs summed in slice order.  Cout a multiple of 32, at most 1024.
+ *   eamm_disc_norm_act_pool      out = AvgPool2d(2)?(LeakyReLU_0.2(InstanceNorm2d(x) * gamma + beta)): x [B,H,W,C]; norm = 1: affine
+ *                                InstanceNorm, eps 1e-5, biased variance, no running statistics, with stats [B,C,2] DOUBLES = (mean,
+ *                                1 / sqrt(var + eps)) written for the backward (sums in double, fixed order); norm = 0: no
+ *                                normalisation (gamma, beta, stats, workspace may be NULL).  pool = 1: out [B,H/2,W/2,C], sizes
+ *                                floored (an odd last row or column feeds no window); pool = 0: out [B,H,W,C].  C a multiple of 4, at
+ *                                most 1024; H * W >= 2 with norm (one value per channel has no variance: refused, as torch does).
+ *   eamm_disc_norm_act_pool_backward  from the saved x and stats: grad_out [B,H/2,W/2,C] (pool) or [B,H,W,C] -> grad_x [B,H,W,C],
+ *                                grad_gamma [C], grad_beta [C] (each may be NULL, not all; norm = 0: grad_x alone).
+ * Workspaces: the *_workspace_floats query of the entry for the same shape (0: the shape is refused, or -- norm = 0 -- none is needed).
+ */
+size_t eamm_disc_conv4_workspace_floats(int B, int H, int W, int Cin, int Cout, int pad, int transposed, int thin);
+int eamm_disc_conv4(int device, const float* x, int B, int H, int W, int Cin, const float* weight, const float* bias, int Cout, int pad,
+                    int transposed, int thin, float* out, float* workspace, size_t workspace_floats, void* stream);
+size_t eamm_disc_conv4_wgrad_workspace_floats(int B, int H, int W, int Cin, int Cout);
+int eamm_disc_conv4_wgrad(int device, const float* x, const float* grad_out, int B, int H, int W, int Cin, int Cout, float* grad_weight,
+                          float* grad_bias, float* workspace, size_t workspace_floats, void* stream);
+size_t eamm_disc_norm_act_pool_workspace_floats(int B, int H, int W, int C, int norm);
+int eamm_disc_norm_act_pool(int device, const float* x, const float* gamma, const float* beta, int B, int H, int W, int C, int norm, int pool,
+                            double* stats, float* out, float* workspace, size_t workspace_floats, void* stream);
+size_t eamm_disc_norm_act_pool_backward_workspace_floats(int B, int H, int W, int C, int norm);
+int eamm_disc_norm_act_pool_backward(int device, const float* x, const double* stats, const float* gamma, const float* beta,
+                                     const float* grad_out, int B, int H, int W, int C, int norm, int pool, float* grad_x, float* grad_gamma,
+                                     float* grad_beta, float* workspace, size_t workspace_floats, void* stream);
 
 #ifdef __cplusplus
 }
