@@ -13,7 +13,7 @@ LIB_PATH = os.path.join(_HERE, "libeamm_hip.so")
 
 ABI_VERSION = 6   # the emotion detector Emotion_k (eamm_emo_*); the audio network AT_net2 (eamm_audio_*) and the MFCC front end
                   # (eamm_op_mfcc*) and the emotion video's preprocessing (eamm_op_resize_aa, eamm_op_similarity_warp,
-                  # eamm_op_emotion_augment), the perceptual loss's and the discriminator's operators (eamm_disc_*) added symbols only
+                  # eamm_op_emotion_augment), the perceptual loss's, the discriminator's (eamm_disc_*) and the equivariance transform's (eamm_equi_*) operators added symbols only
 
 EAMM_OK = 0
 ERR_ARG, ERR_STATE, ERR_KEY, ERR_HIP, ERR_NUMERIC = -1, -2, -3, -4, -5
@@ -292,6 +292,13 @@ SIGNATURES = {
     "eamm_disc_norm_act_pool_backward": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                                    C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                    C.c_size_t, C.c_void_p]),
+    # the equivariance constraint's Transform, a family of its own (equivariance_ops.py); additive
+    "eamm_equi_tps_warp_frame": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                           C.c_void_p]),
+    "eamm_equi_tps_warp_points": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                            C.c_void_p, C.c_void_p]),
+    "eamm_equi_tps_warp_points_backward": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 for _prefix, _config in FAMILIES.items():
     SIGNATURES.update({

@@ -1,4 +1,4 @@
-"""The one way Python calls a handle-less operator entry (``eamm_op_*``, or ``eamm_disc_*`` with ``family="disc"``;
+"""The one way Python calls a handle-less operator entry (``eamm_op_*``, or ``eamm_disc_*`` / ``eamm_equi_*`` with ``family="disc"`` / ``"equi"``;
 include/eamm_hip.h): every entry takes the device index
 first and the stream last, a workspace-taking one its ``(workspace, workspace_floats)`` pair in front of the stream, and reports
 through ``eamm_last_error(NULL)``.  The handle families go through ``_handle.Handle`` instead."""

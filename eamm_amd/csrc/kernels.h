@@ -455,6 +455,16 @@ int l1_pair_partials(long long n);
 hipError_t l1_pair_launch(const float* a, const float* b, long long n, float weight, float* value, float* g, double* partial, hipStream_t s);
 hipError_t l1_pair_backward_launch(const float* g, long long n, const float* grad_value, float* out, hipStream_t s);
 
+// equivariance.hip: the equivariance constraint's Transform (affine theta [B,2,3] + thin-plate term, params [B,P*P], P = 0: none).
+// tps_warp_frame: out [B,C,H,W] = grid_sample(frame, warp(grid), reflection) without a grid tensor.  tps_warp_points: coords
+// [Bc,N,2] (Bc 1 or B) -> out [B,N,2], jac [B,N,2,2] (or null); its backward: gout / gjac (each nullable) -> gcoords [Bc,N,2].
+hipError_t tps_warp_frame_launch(const float* frame, const float* theta, const float* params, int P, int B, int C, int H, int W, float* out,
+                                 hipStream_t s);
+hipError_t tps_warp_points_launch(const float* coords, int Bc, const float* theta, const float* params, int P, int B, int N, float* out,
+                                  float* jac, hipStream_t s);
+hipError_t tps_warp_points_backward_launch(const float* coords, int Bc, const float* theta, const float* params, int P, int B, int N,
+                                           const float* gout, const float* gjac, float* gcoords, hipStream_t s);
+
 hipError_t one_euro_launch(const float* x, int T, int E, float mincutoff, float beta, float dcutoff, float freq, float scale,
                            float* out, hipStream_t stream, float* state = nullptr, int resume = 0);
 

@@ -1,6 +1,6 @@
 // What the operator translation units share (eamm_op_conv.hip, eamm_op_train_conv.hip, eamm_op_train.hip, eamm_op_infer.hip,
-// eamm_op_perceptual.hip, eamm_disc_api.hip; the
-// eamm_op_* and eamm_disc_* entries of include/eamm_hip.h): each entry runs ONE kernel family of the path -- or one operator of the differentiable
+// eamm_op_perceptual.hip, eamm_disc_api.hip, eamm_equi_api.hip; the
+// eamm_op_*, eamm_disc_* and eamm_equi_* entries of include/eamm_hip.h): each entry runs ONE kernel family of the path -- or one operator of the differentiable
 // training graph -- on caller-provided device buffers, without a handle.  Included by those files only.
 #pragma once
 #include "eamm_ctx.h"

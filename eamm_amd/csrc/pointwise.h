@@ -1,6 +1,7 @@
-// What the element-wise and gather kernels share (motion.hip, motion_backward.hip, warp.hip, kp_head.hip; the wave reduction also
-// batchnorm.hip): the coordinate grid, the sparse motion T_k, the ONE grid_sample sampling position that forward and backward
-// kernels both start from, the bilinear resize position, and the wave / workgroup reductions.  Device code only.
+// What the element-wise and gather kernels share (motion.hip, motion_backward.hip, warp.hip, kp_head.hip, equivariance.hip; the wave
+// reduction also batchnorm.hip): the coordinate grid, the sparse motion T_k, the ONE grid_sample sampling position that forward and
+// backward kernels both start from (zeros padding) and its reflection-padding form, the bilinear resize position, and the wave /
+// workgroup reductions.  Device code only.
 #pragma once
 #include "kernels.h"
 
@@ -42,6 +43,31 @@ __device__ __forceinline__ SamplePos sample_pos(float gx, float gy, int W, int H
     p.ax = ix - fx;
     p.ay = iy - fy;
     p.valid = ix > -2.f && ix < (float)W + 1.f && iy > -2.f && iy < (float)H + 1.f;   // false for NaN too
+    return p;
+}
+
+// F.grid_sample(mode='bilinear', padding_mode='reflection', align_corners=False): the same un-normalised position, reflected about
+// -0.5 and size - 0.5 as often as it takes (the distance from -0.5 modulo the size, counted back on an odd number of flips), then
+// clipped to [0, size - 1].  Always valid: x0 / y0 lie inside the map, and only a +1 corner can lie outside -- it weighs nothing
+// (the caller skips it).  A position that is not finite lands on pixel 0.
+__device__ __forceinline__ float reflect_clip(float i, int size) {
+    const float span = (float)size;
+    const float a = fabsf(i + 0.5f);
+    const float extra = fmodf(a, span);
+    const int flips = (int)fminf(floorf(a / span), 1073741824.f);
+    const float r = (flips & 1) ? span - extra - 0.5f : extra - 0.5f;
+    return fminf((float)(size - 1), fmaxf(r, 0.f));
+}
+__device__ __forceinline__ SamplePos sample_pos_reflect(float gx, float gy, int W, int H) {
+    const float ix = reflect_clip(((gx + 1.f) * (float)W - 1.f) * 0.5f, W);
+    const float iy = reflect_clip(((gy + 1.f) * (float)H - 1.f) * 0.5f, H);
+    const float fx = floorf(ix), fy = floorf(iy);
+    SamplePos p;
+    p.x0 = (int)fx;
+    p.y0 = (int)fy;
+    p.ax = ix - fx;
+    p.ay = iy - fy;
+    p.valid = true;
     return p;
 }
 

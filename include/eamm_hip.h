@@ -975,6 +975,36 @@ int eamm_disc_norm_act_pool_backward(int device, const float* x, const double* s
                                      const float* grad_out, int B, int H, int W, int C, int norm, int pool, float* grad_x, float* grad_gamma,
                                      float* grad_beta, float* workspace, size_t workspace_floats, void* stream);
 
+/*
+ * The equivariance constraint's random transform (reference modules/model.py:71-152, class Transform), a family of its own: eamm_equi_*
+ * (equivariance.hip).  Device pointers, fp32, 4-byte aligned; asynchronous on `stream`; the operator convention (device index first,
+ * stream last, errors through eamm_last_error(NULL)).  No atomics: every result is the same bits from run to run.
+ *   theta [B,2,3] the affine part, control_params [B,points^2] the thin-plate weights of the points x points coordinate grid (row-major,
+ *   x = 2 j / (points - 1) - 1); points = 0: affine only (control_params may be NULL), else 2..16.  For a point c = (x, y) of image b:
+ *       warp(c) = theta[b,:,:2] c + theta[b,:,2] + (r, r),  r = sum_p w[b,p] U(|x - cx_p| + |y - cy_p|),  U(d) = d^2 logf(d + 1e-6)
+ *   (the L1 distance, and one r for both components, are the reference's), summed over p ascending.
+ *   eamm_equi_tps_warp_frame     frame NCHW [B,C,H,W] -> out [B,C,H,W] = F.grid_sample(frame, warp(make_coordinate_grid(H, W)),
+ *                                mode='bilinear', padding_mode='reflection', align_corners=False): the sample is un-normalised as
+ *                                ((g + 1) size - 1) / 2, reflected about -0.5 and size - 0.5 any number of times, clipped to
+ *                                [0, size - 1]; a corner outside the map weighs nothing.  No grid tensor is written.  C 1..6, H and W
+ *                                at least 2, B at most 65535; out must not be the frame.
+ *   eamm_equi_tps_warp_points    coords [coords_batch,N,2] with coords_batch = 1 (one set for every image) or B -> out [B,N,2] and,
+ *                                where jac is not NULL, jac [B,N,2,2] = d out / d coords = theta[b,i,j] + g_j,
+ *                                g = sum_p w[b,p] U'(d_p) sign(c - c_p), sign(0) = 0 (autograd's abs).
+ *   eamm_equi_tps_warp_points_backward  grad_out [B,N,2] and grad_jac [B,N,2,2] (each may be NULL, not both) -> grad_coords
+ *                                [coords_batch,N,2], fully written: sum_i grad_out[i] jac[i][k] + sum_ij grad_jac[i][j] Hs[j][k],
+ *                                Hs = sum_p w[b,p] U''(d_p) s s^T (the jacobian differentiated once more).  coords_batch = 1: the
+ *                                images' terms are added in index order.
+ * There is no gradient to the frame, theta or control_params: the reference draws the parameters and trains none of them.
+ */
+int eamm_equi_tps_warp_frame(int device, const float* frame, const float* theta, const float* control_params, int points, int B, int C,
+                             int H, int W, float* out, void* stream);
+int eamm_equi_tps_warp_points(int device, const float* coords, int coords_batch, const float* theta, const float* control_params, int points,
+                              int B, int N, float* out, float* jac, void* stream);
+int eamm_equi_tps_warp_points_backward(int device, const float* coords, int coords_batch, const float* theta, const float* control_params,
+                                       int points, int B, int N, const float* grad_out, const float* grad_jac, float* grad_coords,
+                                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif
