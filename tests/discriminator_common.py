@@ -1,12 +1,12 @@
 """What the discriminator tests share: a plain-torch discriminator (nn.Conv2d, torch.nn.utils.spectral_norm, F.instance_norm /
 leaky_relu / avg_pool2d) as oracle -- run on the CPU in float64 and in float32 from identical fp32-rounded values -- and the seeded
-recipe of its parameters.  The tolerance rule is perceptual_common.close: no element beyond max(4 |ATen fp32 - fp64|_max,
+recipe of its parameters.  The tolerance rule is tests/closeness.py's: no element beyond max(4 |ATen fp32 - fp64|_max,
 OP_FLOOR x scale)."""
 import torch
 import torch.nn.functional as F
 from torch import nn
 
-from perceptual_common import GRAD_FLOOR, OP_FLOOR, close, grad_close  # noqa: F401
+from closeness import close, grad_close
 
 
 def heatmaps(value, size, variance):

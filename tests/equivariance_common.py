@@ -2,7 +2,7 @@
 ``F.grid_sample(mode='bilinear', padding_mode='reflection', align_corners=False)``, written from the formulas and differentiated by
 autograd -- twice for the jacobian's gradient, as the reference does -- on the CPU, in any dtype; the seeded parameters and planted
 cases; the fixture's loader.  The tests run it in float64 and in float32 from identical fp32-rounded inputs (the coordinate grids
-included: they are fp32 values in both runs, as the kernels build them) and compare with ``perceptual_common.close``:
+included: they are fp32 values in both runs, as the kernels build them) and compare with ``closeness.close``:
 no element beyond max(4 |fp32 - fp64|_max, OP_FLOOR x scale)."""
 import os
 
@@ -17,10 +17,6 @@ SHIPPED = (0.05, 0.005)      # sigma_affine, sigma_tps of every shipped configur
 WIDE = (0.3, 0.02)           # a third of the grid points leave the frame
 # every pixel takes several reflections, and the y axis is mirrored
 THETA_MANY_REFLECTIONS = [[3.2, 0.0, 2.7], [0.0, -3.2, -2.7]]
-
-# tests/test_gpu_kp_backward.py's floors, for the detector's parameter gradients in test_gpu_equivariance.py
-FP32_MIN_REL = 5e-3
-TIGHT_MIN_REL = 2e-5
 
 
 def coordinate_grid(h, w, dtype=torch.float32, grid_dtype=torch.float32):
@@ -161,27 +157,6 @@ def loss_reference(kp_driving, transformed_kp, theta, params, points, weight_val
         eye = torch.eye(2, dtype=value.dtype).view(1, 1, 2, 2)
         values["equivariance_jacobian"] = weight_jacobian * (eye - value).abs().mean()
     return values
-
-
-def kp_close(got, want, want32, what, floor, relu=False, gmax=None):
-    """tests/test_gpu_kp_backward.py's rule for a detector tensor: no element beyond max(4 x the oracle's fp32-vs-fp64 distance,
-    floor) of scale; behind ReLUs at most max(2, n // 200) elements (one if n < 400) beyond the bar, none beyond 20 bars."""
-    got, want, want32 = got.detach().cpu().double().reshape(-1), want.detach().double().reshape(-1), want32.detach().double().reshape(-1)
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    assert bool(torch.isfinite(got).all()), what
-    scale = float(want.abs().max())
-    if scale == 0.0 or (gmax is not None and scale < 1e-9 * gmax):
-        scale = gmax if gmax else 1.0
-    bar = max(4.0 * float((want32 - want).abs().max()) / scale, floor) * scale
-    diff = (got - want).abs()
-    print(f"  {what:60s} err/scale {float(diff.max()) / scale:.2e}  oracle fp32 {float((want32 - want).abs().max()) / scale:.2e}  "
-          f"bar/scale {bar / scale:.2e}")
-    if relu:
-        allowed = max(2, diff.numel() // 200) if diff.numel() >= 400 else 1
-        assert int((diff > bar).sum()) <= allowed, (what, int((diff > bar).sum()), allowed, float(diff.max()), bar)
-        assert float(diff.max()) <= 20 * bar, (what, float(diff.max()), bar)
-    else:
-        assert float(diff.max()) <= bar, (what, float(diff.max()), bar)
 
 
 def kp_leaves(sd, dtype):

@@ -13,7 +13,16 @@ that is 16 bytes off a 256-byte boundary.  Plain helper module: no pytest hooks,
 
 ``Plain(device)`` has the same call signature and does what the tests did before there was an arena (``.to(device)``,
 ``torch.full(nan)``); the case helpers take either as their ``place=`` argument.  Both remember the "out" and "inout" views they
-handed out, in order, so that two runs of one case can be compared bit for bit (``same_outputs``)."""
+handed out, in order, so that two runs of one case can be compared bit for bit (``same_outputs``).
+
+The registry: a guarded case is a function of ``place`` that calls entries on placed operands and makes its own comparison.  The
+test files that define such cases register them with ``case`` at import: ``CASES`` holds them by id, ``GUARDED`` maps an entry of
+``_lib.SIGNATURES`` to the ids of its cases, ``EXEMPT`` maps an entry without one to the reason.  ``run_three`` is the one driver.
+tests/test_gpu_guarded_ops.py imports every registering module and runs the whole registry; tests/test_guarded_host.py checks that
+every entry of ``OPERATOR_FAMILIES`` that takes a pointer is guarded or exempt.
+
+A new handle-less operator family joins by adding its prefix to ``OPERATOR_FAMILIES`` and registering its cases (a new module is
+added to the imports at the end of test_gpu_guarded_ops.py); tests/test_op_entries_host.py's all-zero refusal check then covers it too."""
 import torch
 
 GUARD_WORD = 0x7FC5A5A5          # a quiet NaN with a payload: poisons what reads it, and is recognisable in a dump
@@ -23,6 +32,16 @@ ALIGN = 256                      # a view starts at 0 mod ALIGN, plus the skew
 SKEWS = (0, 16)                  # 16 bytes is what the header documents; nothing below it is ever launched on
 ROLES = ("in", "out", "inout", "work")
 CHUNK = 64 << 20                 # the arena grows by buffers of at least this size; an operand and its bands lie in one of them
+
+# the handle-less operator families: every entry of theirs that takes a pointer is guarded or exempt
+OPERATOR_FAMILIES = ("eamm_op_", "eamm_bn_", "eamm_disc_", "eamm_equi_")
+CASES = {}        # id -> (function of place, names of outputs that may stay NaN, names of outputs exempt from bit-equality)
+GUARDED = {}      # entry -> [case ids]
+# entries that take a pointer argument but have no guarded case, with the reason
+EXEMPT = {
+    "eamm_op_lstm_check": "no tensor: its pointer argument is the stream",
+    "eamm_final_split_planes": "host pointers only: it packs the final layer's filter on the CPU",
+}
 
 
 def band_bytes(own_bytes):
@@ -190,3 +209,36 @@ def same_outputs(a, b):
     """Names of the "out" / "inout" operands of two placers' runs of one case that are not bit-identical."""
     assert [n for n, _ in a.outs] == [n for n, _ in b.outs], "the two runs placed different outputs"
     return [n for (n, x), (_, y) in zip(a.outs, b.outs) if not _same_bits(x, y)]
+
+
+def case(cid, entries, fn=None, nan_ok=(), unstable=()):
+    """Register ``fn(place)`` as case ``cid`` covering ``entries`` (full names).  Usable as a decorator when ``fn`` is None."""
+    def register(f):
+        from eamm_amd import _lib      # here, so that the placement helpers above need nothing but torch
+        assert cid not in CASES, cid
+        CASES[cid] = (f, tuple(nan_ok), tuple(unstable))
+        for e in entries:
+            assert e in _lib.SIGNATURES, e
+            GUARDED.setdefault(e, []).append(cid)
+        return f
+    return register if fn is None else register(fn)
+
+
+def run_three(cid, device="cuda:0"):
+    fn, nan_ok, unstable = CASES[cid]
+    sync = torch.cuda.synchronize if torch.device(device).type == "cuda" else lambda: None
+    plain = Plain(device)
+    fn(plain)
+    sync()
+    for skew in SKEWS:
+        arena = Arena(device, skew=skew)
+        fn(arena)
+        sync()
+        arena.check(nan_ok=nan_ok)
+        differ = [n for n in same_outputs(plain, arena) if n not in unstable]
+        if differ:      # tell an alignment / neighbourhood dependence from an entry that does not repeat itself
+            again = Plain(device)
+            fn(again)
+            sync()
+            assert not differ, (cid, f"skew {skew}: outputs differ from the plain call", differ,
+                                "two plain calls differ in", same_outputs(plain, again))

@@ -1,5 +1,5 @@
 """What the perceptual-loss tests share: the seeded inputs and weights of their recipe, the float64 / ATen-fp32 oracle on the CPU
-(plain torch: F.pad / F.conv2d / F.relu / F.max_pool2d), and the two tolerance rules (tests/test_gpu_emotion_backward.py).
+(plain torch: F.pad / F.conv2d / F.relu / F.max_pool2d).  The tolerance rules are tests/closeness.py's.
 
 Recipe: ``generated`` uniform [0,1), ``real = clamp(generated + 0.1 randn, 0, 1)``, He-normal filters (std = sqrt(2 / (9 Cin))),
 biases 0.05 randn, everything rounded to fp32 before the float64 oracle sees it -- both sides read identical values."""
@@ -10,10 +10,6 @@ import torch.nn.functional as F
 
 from eamm_amd.perceptual import _CONVS, _MEAN, _POOLS, _SLICES, _STD
 from eamm_amd.weights import antialias_kernel
-
-OP_FLOOR = 2e-5      # operators, forward taps, the loss value: two fp32 summation orders differ by this much
-GRAD_FLOOR = 5e-3    # the image gradient through the whole stack: one ReLU flipped by rounding moves it by about 1.6e-3 of scale
-
 
 def vgg_state(seed=7):
     """A Vgg19 state dict in the reference module's layout, fp32."""
@@ -71,36 +67,6 @@ def ref_loss(sd, generated, real, scales, weights):
             if weights[i]:
                 total = total + weights[i] * (fg[i] - fr[i]).abs().mean()
     return total
-
-
-def close(got, want, want32, what, floor=OP_FLOOR):
-    """One tensor against its float64 reference; ``want32`` = the same computation by ATen in fp32.  No element beyond the bar
-    ``max(4 |ATen fp32 - fp64|_max, floor * scale)``, scale = |fp64|_max.  Returns err / scale."""
-    got, want, want32 = (t.detach().cpu().double().reshape(-1) for t in (got, want, want32))
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    assert bool(torch.isfinite(got).all()), what
-    scale = float(want.abs().max()) or 1.0
-    aten = float((want32 - want).abs().max()) / scale
-    bar = max(4.0 * aten, floor) * scale
-    err = float((got - want).abs().max())
-    print(f"  {what:48s} err/scale {err / scale:.2e}  ATen fp32 {aten:.2e}  bar/scale {bar / scale:.2e}")
-    assert err <= bar, (what, err, bar)
-    return err / scale, aten
-
-
-def grad_close(got, want, want32, what, floor=GRAD_FLOOR):
-    """The whole-network gradient rule: at most max(2, numel // 200) elements beyond the bar, none beyond 20 bars."""
-    got, want, want32 = (t.detach().cpu().double().reshape(-1) for t in (got, want, want32))
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    assert bool(torch.isfinite(got).all()), what
-    scale = float(want.abs().max()) or 1.0
-    aten = float((want32 - want).abs().max()) / scale
-    bar = max(4.0 * aten, floor) * scale
-    diff = (got - want).abs()
-    beyond, allowed = int((diff > bar).sum()), max(2, diff.numel() // 200)
-    print(f"  {what:48s} err/scale {float(diff.max()) / scale:.2e}  ATen fp32 {aten:.2e}  bar/scale {bar / scale:.2e}  beyond {beyond}/{diff.numel()}")
-    assert beyond <= allowed, (what, beyond, allowed, float(diff.max()), bar)
-    assert float(diff.max()) <= 20 * bar, (what, float(diff.max()), bar)
 
 
 FRAGILE_REL = 1e-6   # about 8 fp32 ulps

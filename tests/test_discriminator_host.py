@@ -1,28 +1,14 @@
-"""CPU-side checks of the discriminator: the guarded table of tests/test_gpu_guarded_disc.py covers every eamm_disc_* entry that takes
-a pointer, the modules keep the reference's state-dict layout (that of the plain-torch module built with the same arguments) and
-load it strictly, unsupported widths are refused by name, and nothing computes without a GPU."""
-import ctypes as C
-
+"""CPU-side checks of the discriminator: the modules keep the reference's state-dict layout (that of the plain-torch module built
+with the same arguments) and load it strictly, unsupported widths are refused by name, and nothing computes without a GPU.  (The
+entries' guarded cases and all-zero refusals: tests/test_guarded_host.py, tests/test_op_entries_host.py.)"""
 import pytest
 import torch
 
-from eamm_amd import Discriminator, MultiScaleDiscriminator, _lib, conv4_valid, norm_act_pool
+from eamm_amd import Discriminator, MultiScaleDiscriminator, conv4_valid, norm_act_pool
 from eamm_amd.disc_ops import thin_channels
 from discriminator_common import TorchMultiScale, seeded_state
 
 SHIPPED = dict(scales=[1], block_expansion=32, max_features=512, num_blocks=4, sn=True)
-
-
-def test_every_disc_entry_with_a_pointer_has_a_guarded_case():
-    import test_gpu_disc_ops as ops
-    import test_gpu_guarded_disc as g
-    need = [name for name, (_, args) in _lib.SIGNATURES.items() if name.startswith("eamm_disc_") and any(a is C.c_void_p for a in args)]
-    assert len(need) == 4, need
-    assert [n for n in need if n not in g.GUARDED and n not in g.EXEMPT] == []
-    assert all(n in _lib.SIGNATURES for n in list(g.GUARDED) + list(g.EXEMPT))
-    assert all(ids and all(i in ops.CASES for i in ids) for ids in g.GUARDED.values())
-    # the size queries take no pointer; each entry with a workspace has one
-    assert all(n + "_workspace_floats" in _lib.SIGNATURES for n in need)
 
 
 @pytest.mark.parametrize("kwargs", [SHIPPED, dict(scales=[1, 0.5], block_expansion=32, num_blocks=3, sn=False),

@@ -139,21 +139,6 @@ def test_the_entries_are_bound_as_the_header_declares_them():
     assert _lib.ABI_VERSION == 6
 
 
-@pytest.mark.parametrize("name", ENTRIES)
-def test_an_all_zero_call_is_refused_under_the_entrys_own_name(name):
-    """tests/test_op_entries_host.py's check, for this family."""
-    L = _lib.lib()
-    zeros = [0 if t is ctypes.c_int else None for t in _lib.SIGNATURES[name][1]]
-    assert getattr(L, name)(*zeros) == _lib.ERR_ARG
-    assert L.eamm_last_error(None).decode().startswith(name + ":")
-
-
-def test_every_entry_has_guarded_cases():
-    import test_gpu_equivariance_ops as g
-    assert sorted(g.GUARDED) == sorted(ENTRIES)
-    assert all(ids and all(i in g.CASES for i in ids) for ids in g.GUARDED.values())
-
-
 # ---- the oracle -----------------------------------------------------------------------------------------------------------------
 def test_the_oracle_reproduces_the_references_recorded_results():
     fx = ec.load_fixture()

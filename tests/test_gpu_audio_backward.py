@@ -2,7 +2,7 @@
 audio_backward.hip) against ATen differentiated in float64 on the CPU, and the modules' differentiable forward against training
 steps of the reference itself (tests/golden/audio_eval_backward.npz, audio_train_backward.npz; tools/make_audio_train_golden.py).
 
-Operator bars, per tensor, relative to its largest float64 entry: 2e-5 (tests/test_gpu_backward.py), provided ATen's own CPU fp32
+Operator bars (tests/closeness.py), per tensor, relative to its largest float64 entry: 2e-5, provided ATen's own CPU fp32
 run stays under a quarter of it on the same inputs; otherwise 4 x that run's distance.  No element may lie beyond the bar.
 Module bars: tests/test_gpu_emotion_backward.py's rule, see ``check_module``.
 
@@ -31,26 +31,13 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from closeness import close
 from conftest import GOLDEN
 from eamm_amd import AudioFeatureNet, KPDetector_a, audio_ops, tiny_kp_config
 from eamm_amd.weights import audio_feature_state_dict_spec, kp_state_dict_spec, synthetic_audio_inputs, synthetic_state_dict
 
 DEV = "cuda:0"
-TIGHT_MIN_REL = 2e-5
 FP32_MIN_REL = 5e-3       # tests/test_train_backward.py
-
-
-def close(got, want, want32, what):
-    """One tensor against its float64 reference; ``want32`` = the same computation by ATen in fp32.  No element beyond the bar."""
-    got, want, want32 = (t.detach().cpu().double().reshape(-1) for t in (got, want, want32))
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    assert bool(torch.isfinite(got).all()), what
-    scale = float(want.abs().max()) or 1.0
-    aten = float((want32 - want).abs().max()) / scale
-    bar = (TIGHT_MIN_REL if aten <= TIGHT_MIN_REL / 4 else 4.0 * aten) * scale
-    err = float((got - want).abs().max())
-    print(f"  {what:48s} err/scale {err / scale:.2e}  ATen fp32 {aten:.2e}  bar/scale {bar / scale:.2e}")
-    assert err <= bar, (what, err, bar)
 
 
 def nhwc(t):

@@ -1,6 +1,8 @@
 """eamm_op_conv_dev with a 1x1 filter (the discriminator's prediction layer: pad 0, one tap in the packed image), forward and --
-``transposed = 1`` -- data gradient, against F.conv2d on the CPU in float64 at perceptual_common.close's bar, on plain tensors and
-between tests/guarded.py's poisoned bands at skew 0 and 16 (outputs bit-equal to the plain placement)."""
+``transposed = 1`` -- data gradient, against F.conv2d on the CPU in float64 at closeness.close's bar.  The cases are registered in
+tests/guarded.py as ``train-conv_dev_1x1_<name>``: tests/test_gpu_guarded_ops.py runs each on plain tensors and between poisoned
+bands at skew 0 and 16 (outputs bit-equal to the plain placement)."""
+import functools
 import math
 
 import pytest
@@ -8,8 +10,8 @@ import torch
 import torch.nn.functional as F
 
 from eamm_amd import _lib, _op
-from guarded import Arena, Plain, same_outputs
-from perceptual_common import close
+from closeness import close
+from guarded import case
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -37,17 +39,8 @@ def run_case(name, place):
     close(out, want[0], want[1], "conv_dev 1x1 " + name)
 
 
-@pytest.mark.parametrize("name", sorted(CASES))
-def test_conv_dev_1x1_plain_and_between_guard_bands(name):
-    plain = Plain(DEV)
-    run_case(name, plain)
-    torch.cuda.synchronize()
-    for skew in (0, 16):
-        arena = Arena(DEV, skew=skew)
-        run_case(name, arena)
-        torch.cuda.synchronize()
-        arena.check()
-        assert same_outputs(plain, arena) == [], (name, skew)
+for _n in sorted(CASES):
+    case("train-conv_dev_1x1_" + _n, ["eamm_op_conv_dev"], functools.partial(run_case, _n))
 
 
 def test_other_filter_sizes_stay_refused():

@@ -1,9 +1,10 @@
 """The discriminator's operator entries (eamm_disc_*) at the smallest shapes that can still go wrong, against F.conv2d /
-F.instance_norm / F.leaky_relu / F.avg_pool2d on the CPU in float64, at perceptual_common.close's bar: no element beyond
+F.instance_norm / F.leaky_relu / F.avg_pool2d on the CPU in float64, at closeness.close's bar: no element beyond
 max(4 |ATen fp32 - fp64|_max, 2e-5 x scale), ATen's distance measured in the same test.
 
-Every case is a function of ``place`` (tests/guarded.py), so that tests/test_gpu_guarded_disc.py runs the same cases between guard
-bands; here each runs twice on plain tensors and the two runs' outputs must be bit-equal (fixed-order sums, no atomics)."""
+Every case is a function of ``place`` (tests/guarded.py) and is registered there as ``disc-<name>`` under the entries it calls, so
+that tests/test_gpu_guarded_ops.py runs the same cases between guard bands; here each runs twice on plain tensors and the two
+runs' outputs must be bit-equal (fixed-order sums, no atomics)."""
 import functools
 import math
 
@@ -13,8 +14,8 @@ import torch.nn.functional as F
 
 from eamm_amd import _lib, _op
 from eamm_amd.disc_ops import thin_channels
-from discriminator_common import close
-from guarded import Plain, same_outputs
+from closeness import close
+from guarded import Plain, case, same_outputs
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -169,6 +170,16 @@ CASES = {
     "norm_two_values": functools.partial(norm_case, (2, 1, 2, 32), True, False),      # H * W = 2
     "norm_many_ranges": functools.partial(norm_case, (1, 19, 21, 8), True, True),     # 399 pixels: seven ranges, 32 row lanes
 }
+
+# between guard bands: every case but thin4_rubbish and thin8_rubbish
+_CONV = ["fwd_mtail", "fwd_one_pixel", "fwd_row_past_tile", "fwd_two_mtiles_n96", "dgrad", "dgrad_small_map", "dgrad_thin4", "dgrad_thin16", "thin4", "thin8",
+         "thin16", "thin16_rubbish"]
+_WGRAD = ["wgrad_ragged_split", "wgrad_one_pixel", "wgrad_row_past_tile", "wgrad_thin4", "wgrad_thin8", "wgrad_thin16"]
+_NORM = ["norm_pool_odd", "norm_nopool", "block0_pool", "block0_nopool", "norm_two_values", "norm_many_ranges"]
+for _names, _entries in ((_CONV, ["eamm_disc_conv4"]), (_WGRAD, ["eamm_disc_conv4_wgrad"]),
+                         (_NORM, ["eamm_disc_norm_act_pool", "eamm_disc_norm_act_pool_backward"])):
+    for _n in _names:
+        case("disc-" + _n, _entries, CASES[_n])
 
 
 @pytest.mark.parametrize("name", sorted(CASES))

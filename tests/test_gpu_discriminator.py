@@ -1,6 +1,6 @@
 """eamm_amd.Discriminator / MultiScaleDiscriminator and the GAN loss terms against the plain-torch oracle of
 tests/discriminator_common.py (CPU, float64, with ATen's fp32 distance measured beside it): forward maps, the image gradient, every
-parameter gradient and the spectral-norm vectors, at perceptual_common.close's bar -- no element beyond
+parameter gradient and the spectral-norm vectors, at closeness.close's bar -- no element beyond
 max(4 |ATen fp32 - fp64|_max, 2e-5 x scale).
 
 Network of the main test: block_expansion 32, four blocks, spectral norm, at [2,3,80,72]: 80 -> 77 -> 38 -> 35 -> 17 -> 14 -> 7 -> 4
@@ -11,7 +11,7 @@ Every tensor is held to ``close`` -- forward values, spectral-norm vectors, loss
 module_loss has a discrete decision per unit, sign(f) of |f|.mean(): where a feature value lies within rounding of zero two fp32
 evaluations choose differently, both subgradients are valid, and every gradient UPSTREAM of that unit moves with the choice.  The
 test counts the units of each feature map whose sign is not float64's (the forward itself is within ``close``); a gradient
-upstream of such a unit is held to the project's whole-network gradient rule ``perceptual_common.grad_close`` instead, every other
+upstream of such a unit is held to the project's whole-network gradient rule ``closeness.grad_close`` instead, every other
 gradient stays at ``close``.  Measured (profiles/discriminator_parity.txt): seeds 4 and 5 have no such unit and every gradient is
 within 1e-5 of scale; seed 3 has ONE, in feature map 1, and exactly the gradients upstream of it (image, blocks 0 and 1) are
 3e-5 .. 2.5e-4 of scale from float64 while blocks 2, 3 and the prediction layer stay below 9e-6; at seed 4 ATen's own fp32 run
@@ -23,9 +23,9 @@ import numpy as np
 import pytest
 import torch
 
+from closeness import GRAD_FLOOR, OP_FLOOR, close
 from eamm_amd import (Discriminator, ImagePyramide, MultiScaleDiscriminator, discriminator_gan_loss, generator_gan_loss, tiny_config)
-from discriminator_common import (OP_FLOOR, TorchMultiScale, close, decisions_differing, gradient_check, module_loss, oracle,
-                                  seeded_state)
+from discriminator_common import TorchMultiScale, decisions_differing, gradient_check, module_loss, oracle, seeded_state
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -292,7 +292,6 @@ def test_reference_fixture():
     rebuilt tensors: a changed torch generator stream fails HERE, by name, not as a kernel mismatch.  Bar: ``close``'s,
     max(4 ATen, 2e-5) of scale; the image gradient follows the main test's rule where a unit's sign differs from float64's."""
     from discriminator_common import SHIPPED, fixture_state, state_checksum
-    from perceptual_common import GRAD_FLOOR
     z = np.load(GOLDEN)
     sd = fixture_state(int(z["weight_seed"]))
     assert abs(state_checksum(sd) - float(z["state_checksum"])) <= 1e-9 * float(z["state_checksum"]), \

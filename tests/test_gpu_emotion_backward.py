@@ -3,8 +3,8 @@ emotion_backward.hip; ``eamm_amd.emo_ops``) against ATen differentiated in float
 forward against a training step of the reference itself (tests/golden/emotion_tiny128_train_backward.npz,
 tools/make_emotion_train_golden.py).
 
-Bars (tests/test_gpu_kp_backward.py), per tensor, relative to its largest reference entry: max(4 x the reference's own
-fp32-vs-fp64 distance for that tensor, a floor).  The floor is TIGHT_MIN_REL for the operators (no element may lie beyond the bar)
+Bars (tests/closeness.py), per tensor, relative to its largest reference entry: max(4 x the reference's own
+fp32-vs-fp64 distance for that tensor, a floor).  The floor is closeness.OP_FLOOR for the operators (no element may lie beyond the bar)
 and FP32_MIN_REL for the module's gradients, which all sit behind ReLUs: there at most max(2, n // 200) elements (one if n < 400) may
 lie beyond the bar, none beyond 20 bars.  A tensor whose reference gradient is below 1e-9 of the largest gradient (a convolution
 bias in front of batch statistics) is scaled by that largest one.  The reference's own fp32 run differs from its float64 run by at
@@ -19,6 +19,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from closeness import close
 from conftest import GOLDEN
 from eamm_amd import EmotionDetector, KPDetector_a, _lib, _op, emo_ops, tiny_kp_config
 from eamm_amd._handle import ptr as p, stream_ptr as stream   # (for the calls below that read an entry's return code themselves)
@@ -27,20 +28,7 @@ from eamm_amd.weights import (emotion_state_dict_spec, kp_state_dict_spec, synth
 
 DEV = "cuda:0"
 FP32_MIN_REL = 5e-3       # tests/test_train_backward.py
-TIGHT_MIN_REL = 2e-5
 UNUSED = ("fc.", "fc_n.", "final_4.", "final_10.")
-
-
-def close(got, want, want32, what, floor=TIGHT_MIN_REL):
-    """One tensor against its float64 reference; ``want32`` = the same computation by ATen in fp32.  No element beyond the bar."""
-    got, want, want32 = (t.detach().cpu().double().reshape(-1) for t in (got, want, want32))
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    assert bool(torch.isfinite(got).all()), what
-    scale = float(want.abs().max()) or 1.0
-    bar = max(4.0 * float((want32 - want).abs().max()) / scale, floor) * scale
-    err = float((got - want).abs().max())
-    print(f"  {what:48s} err/scale {err / scale:.2e}  ATen fp32 {float((want32 - want).abs().max()) / scale:.2e}  bar/scale {bar / scale:.2e}")
-    assert err <= bar, (what, err, bar)
 
 
 # ---- stride-2 convolution ------------------------------------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 """``eamm_amd.equivariance``: ``Transform`` against the reference's own recorded results (tests/golden/equivariance_tiny.npz,
 tools/record_equivariance_fixture.py), its inverse forms against the float64 oracle (the reference's cannot run without a GPU and
 are not recorded), and ``equivariance_loss`` through the tiny KPDetector against the float64 composition of the oracle detector
-(oracle/eamm_oracle.py) and tests/equivariance_common.py -- the loss values at ``perceptual_common.close``'s bar, the detector's
+(oracle/eamm_oracle.py) and tests/equivariance_common.py -- the loss values at ``closeness.close``'s bar, the detector's
 parameter gradients at tests/test_gpu_kp_backward.py's rule and floors."""
 import pytest
 import torch
@@ -9,8 +9,8 @@ import torch
 import equivariance_common as ec
 from eamm_amd import KPDetector, KPDetector_a, Transform, equivariance_loss, tiny_kp_config
 from eamm_amd.weights import kp_state_dict_spec, synthetic_source, synthetic_state_dict
+from closeness import GRAD_FLOOR, OP_FLOOR, close, kp_close
 from oracle import eamm_oracle as orc
-from perceptual_common import close
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -116,7 +116,7 @@ def test_equivariance_loss_values_and_detector_gradients(loss_case):
     for name, p in det.named_parameters():
         assert p.grad is not None, name
         head = name.startswith(("kp.", "jacobian."))
-        ec.kp_close(p.grad, g64[name], g32[name], "loss " + name, ec.TIGHT_MIN_REL if head else ec.FP32_MIN_REL, relu=not head, gmax=gmax)
+        kp_close(p.grad, g64[name], g32[name], "loss " + name, OP_FLOOR if head else GRAD_FLOOR, relu=not head, gmax=gmax)
 
 
 def test_both_sides_receive_their_gradient_and_a_zero_weight_leaves_its_key_out(loss_case):

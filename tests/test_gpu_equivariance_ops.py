@@ -1,10 +1,11 @@
 """The equivariance transform's entries (eamm_equi_*, csrc/equivariance.hip) against the plain-torch oracle of
-tests/equivariance_common.py, float64 on the CPU, at ``perceptual_common.close``'s bar: no element beyond
+tests/equivariance_common.py, float64 on the CPU, at ``closeness.close``'s bar: no element beyond
 max(4 |oracle fp32 - fp64|_max, OP_FLOOR x scale).
 
 A case is a function of ``place`` (tests/guarded.py): it calls the C entries on placed operands and compares.  Every case runs
-twice on plain tensors (identical bits); the cases listed in ``GUARDED`` -- every entry, shapes whose last workgroup is partial --
-run again between poisoned guard bands at skew 0 and 16, and must leave the bands intact and give the plain run's bits.
+twice on plain tensors (identical bits); the cases registered at the end of this file as ``equi-<name>`` -- every entry, shapes
+whose last workgroup is partial -- run again between poisoned guard bands at skew 0 and 16 (``guarded.run_three``: tests/test_gpu_guarded_ops.py),
+and must leave the bands intact and give the plain run's bits.
 
 The smallest shapes at which the kernels can go wrong: (16,24) non-square with a partial second workgroup, (33,17) odd sizes,
 (64,64) sixteen full workgroups per image; 1 / 10 / 257 points (257: a second, partial workgroup); P = 0 affine only, 2 the smallest
@@ -14,8 +15,8 @@ import torch
 
 import equivariance_common as ec
 from eamm_amd import _op, tps_warp_frame, tps_warp_points
-from guarded import Arena, Plain, same_outputs
-from perceptual_common import close
+from closeness import close
+from guarded import CASES, Plain, case, run_three, same_outputs
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -199,16 +200,6 @@ def test_tps_warp_frame_through_the_python_operator():
 
 
 # ---- between guard bands ---------------------------------------------------------------------------------------------------------
-CASES = {}
-GUARDED = {}
-
-
-def case(cid, entries, fn):
-    CASES[cid] = fn
-    for e in entries:
-        GUARDED.setdefault("eamm_equi_" + e, []).append(cid)
-
-
 def _frame_guarded(H, W, B, C, P, sigmas, seed):
     theta, params = ec.draw_params(B, P, sigmas, seed=seed)
     frame = _frame(B, C, H, W)
@@ -221,28 +212,21 @@ def _points_guarded(N, B, Bc, P):
     return lambda place: points_case(place, coords, theta, params, P, f"guarded points N{N} B{B} Bc{Bc} P{P}")
 
 
-case("frame-16x24", ["tps_warp_frame"], _frame_guarded(16, 24, 3, 3, 5, ec.WIDE, 1))        # 384 pixels: the second workgroup is half full
-case("frame-33x17-c6", ["tps_warp_frame"], _frame_guarded(33, 17, 1, 6, 2, ec.WIDE, 2))     # 561 pixels: three workgroups
-case("frame-33x17-affine", ["tps_warp_frame"], _frame_guarded(33, 17, 3, 1, 0, ec.WIDE, 3))
-case("frame-reflections", ["tps_warp_frame"],
+_FRAME, _POINTS = ["eamm_equi_tps_warp_frame"], ["eamm_equi_tps_warp_points", "eamm_equi_tps_warp_points_backward"]
+case("equi-frame-16x24", _FRAME, _frame_guarded(16, 24, 3, 3, 5, ec.WIDE, 1))        # 384 pixels: the second workgroup is half full
+case("equi-frame-33x17-c6", _FRAME, _frame_guarded(33, 17, 1, 6, 2, ec.WIDE, 2))     # 561 pixels: three workgroups
+case("equi-frame-33x17-affine", _FRAME, _frame_guarded(33, 17, 3, 1, 0, ec.WIDE, 3))
+case("equi-frame-reflections", _FRAME,
      lambda place: frame_case(place, _frame(2, 3, 33, 17), planted_reflections(2), ec.draw_params(2, 5, seed=9)[1], 5, "guarded reflections"))
-case("frame-edges", ["tps_warp_frame"],
+case("equi-frame-edges", _FRAME,
      lambda place: frame_case(place, _frame(3, 3, 16, 24), planted_translations(16, 24), None, 0, "guarded edges"))
-case("points-257", ["tps_warp_points", "tps_warp_points_backward"], _points_guarded(257, 4, 4, 5))      # 1028: five workgroups, the last of 4
-case("points-257-shared", ["tps_warp_points", "tps_warp_points_backward"], _points_guarded(257, 4, 1, 5))
-case("points-10-affine", ["tps_warp_points", "tps_warp_points_backward"], _points_guarded(10, 1, 1, 0))
-case("points-1", ["tps_warp_points", "tps_warp_points_backward"], _points_guarded(1, 4, 4, 2))
+case("equi-points-257", _POINTS, _points_guarded(257, 4, 4, 5))      # 1028: five workgroups, the last of 4
+case("equi-points-257-shared", _POINTS, _points_guarded(257, 4, 1, 5))
+case("equi-points-10-affine", _POINTS, _points_guarded(10, 1, 1, 0))
+case("equi-points-1", _POINTS, _points_guarded(1, 4, 4, 2))
 
 
-@pytest.mark.parametrize("cid", sorted(CASES))
+# the ids these nine runs have always had, kept beside tests/test_gpu_guarded_ops.py's test_guarded[equi-*], which makes the same call
+@pytest.mark.parametrize("cid", sorted(c[len("equi-"):] for c in CASES if c.startswith("equi-")))
 def test_case_between_guard_bands(cid):
-    fn = CASES[cid]
-    plain = Plain(DEV)
-    fn(plain)
-    torch.cuda.synchronize()
-    for skew in (0, 16):
-        arena = Arena(DEV, skew=skew)
-        fn(arena)
-        torch.cuda.synchronize()
-        arena.check()
-        assert same_outputs(plain, arena) == [], (cid, f"skew {skew}: outputs differ from the plain call")
+    run_three("equi-" + cid, DEV)

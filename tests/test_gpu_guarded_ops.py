@@ -6,11 +6,11 @@ existing bar (most are the other test files' own helpers, called with their ``pl
 ``Arena.check()`` must pass -- no guard word changed, no input written to, no NaN in an output -- and every output must be
 bit-equal to the plain run's: the library documents fixed-order sums and no float atomics outside the listed exceptions.
 
-``GUARDED`` maps an entry of ``_lib.SIGNATURES`` to the ids of the cases that cover it; ``EXEMPT`` maps the entries without a case
-to the reason.  tests/test_guarded_host.py checks that the two together are complete.
+The registry and the driver ``run_three`` live in tests/guarded.py.  This file registers the eamm_op_* and eamm_bn_* cases; the modules
+imported at its end register theirs, and ``test_guarded`` runs them all.  tests/test_guarded_host.py checks that none is missing.
 
 On a machine with a GPU run the file one family at a time (``-k conv-``, ``-k warp-``, ``-k infer-``, ``-k train-``, ``-k emo-``,
-``-k audio-``, ``-k kp-``, ``-k motion-``, ``-k perc-``, ``-k bn-``, ``-k modes-``, ``-k clip-``, ``-k "four_floats or boundary or refused"``):
+``-k audio-``, ``-k kp-``, ``-k motion-``, ``-k perc-``, ``-k bn-``, ``-k modes-``, ``-k clip-``, ``-k disc-``, ``-k equi-``, ``-k "four_floats or boundary or refused"``):
 a stray store is the failure this file exists to find, and a family that has one should not be followed by another."""
 import ctypes as C
 import functools
@@ -21,50 +21,11 @@ import torch
 import torch.nn.functional as F
 
 from eamm_amd import _lib, _op
-from guarded import Arena, Plain, same_outputs
+from closeness import close
+from guarded import CASES, EXEMPT, GUARDED, Arena, Plain, case, run_three  # noqa: F401  (tests/test_guarded_host.py reads the registry here)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-CASES = {}        # id -> (function of place, names of outputs that may stay NaN, names of outputs exempt from bit-equality)
-GUARDED = {}      # entry -> [case ids]
-# entries that take a pointer argument but have no guarded case, with the reason
-EXEMPT = {
-    "eamm_op_lstm_check": "no tensor: its pointer argument is the stream",
-    "eamm_final_split_planes": "host pointers only: it packs the final layer's filter on the CPU",
-}
-
-
-def case(cid, entries, fn=None, nan_ok=(), unstable=()):
-    """Register ``fn(place)`` as case ``cid`` covering ``entries`` (full names).  Usable as a decorator when ``fn`` is None."""
-    def register(f):
-        assert cid not in CASES, cid
-        CASES[cid] = (f, tuple(nan_ok), tuple(unstable))
-        for e in entries:
-            assert e in _lib.SIGNATURES, e
-            GUARDED.setdefault(e, []).append(cid)
-        return f
-    return register if fn is None else register(fn)
-
-
-def run_three(cid):
-    fn, nan_ok, unstable = CASES[cid]
-    plain = Plain(DEV)
-    fn(plain)
-    torch.cuda.synchronize()
-    for skew in (0, 16):
-        arena = Arena(DEV, skew=skew)
-        fn(arena)
-        torch.cuda.synchronize()
-        arena.check(nan_ok=nan_ok)
-        differ = [n for n in same_outputs(plain, arena) if n not in unstable]
-        if differ:      # tell an alignment / neighbourhood dependence from an entry that does not repeat itself
-            again = Plain(DEV)
-            fn(again)
-            torch.cuda.synchronize()
-            assert not differ, (cid, f"skew {skew}: outputs differ from the plain call", differ,
-                                "two plain calls differ in", same_outputs(plain, again))
-
 
 def _call(name, *args, work=None):
     _op.call(name[len("eamm_op_"):], torch.device(DEV), *args, work=work)
@@ -323,9 +284,9 @@ def _conv_s2_case(k, shape, place):
     _call("eamm_op_conv_s2_wgrad", xd, gd, b, h, w, cin, cout, k, dw,
           work=_work(place, "eamm_op_conv_s2_wgrad_workspace_floats", b, h, w, cin, cout, k, name="wgrad workspace"))
     torch.cuda.synchronize()
-    emo.close(y, emo.nhwc(y64), emo.nhwc(y32), f"k{k} {shape} forward")
-    emo.close(dx, emo.nhwc(dx64), emo.nhwc(dx32), f"k{k} {shape} data gradient")
-    emo.close(dw, dw64, dw32, f"k{k} {shape} weight gradient")
+    close(y, emo.nhwc(y64), emo.nhwc(y32), f"k{k} {shape} forward")
+    close(dx, emo.nhwc(dx64), emo.nhwc(dx32), f"k{k} {shape} data gradient")
+    close(dw, dw64, dw32, f"k{k} {shape} weight gradient")
 
 
 for _k in (1, 3):
@@ -346,7 +307,7 @@ def _emo_maxpool_case(place, shape=(1, 2, 2, 64)):
     assert torch.equal(y.cpu(), emo.nhwc(ref[torch.float32][0]))
     want = emo.nhwc(ref[torch.float64][1])
     assert bool(((dx.cpu() != 0) == (want != 0)).all())
-    emo.close(dx, want, emo.nhwc(ref[torch.float32][1]), f"maxpool {shape}")
+    close(dx, want, emo.nhwc(ref[torch.float32][1]), f"maxpool {shape}")
 
 
 case("emo-maxpool_2_6_10_64", ["eamm_op_emo_maxpool", "eamm_op_emo_maxpool_backward"], functools.partial(_emo_maxpool_case, shape=(2, 6, 10, 64)))
@@ -374,7 +335,7 @@ def _emo_final_case(B, place):
     _call("eamm_op_emo_final_backward", ad, wd, gvd, gjd, B, ga, gw, work=_work(place, "eamm_op_emo_final_workspace_floats", B))
     torch.cuda.synchronize()
     for name, got, i in (("value", value, 0), ("jacobian", jac, 1), ("grad input", ga, 2), ("grad weights", gw, 3)):
-        emo.close(got, ref[torch.float64][i], ref[torch.float32][i], f"emo_final B={B} {name}")
+        close(got, ref[torch.float64][i], ref[torch.float32][i], f"emo_final B={B} {name}")
 
 
 for _b in (1, 9):
@@ -401,9 +362,9 @@ def _lstm_case(shape, place):
     _call("eamm_op_lstm_backward", gates, c, wd, gd, n, t, gx, work=_work(place, "eamm_op_lstm_backward_workspace_floats", n, t, name="backward workspace"))
     _call("eamm_op_lstm_check")
     gw = torch.matmul(gx.reshape(n * t, 1024).t(), h_prev)
-    aud.close(y, y64, y32, f"lstm {shape} y")
-    aud.close(gx, dx64, dx32, f"lstm {shape} dxproj")
-    aud.close(gw, dw64, dw32, f"lstm {shape} dW_hh")
+    close(y, y64, y32, f"lstm {shape} y")
+    close(gx, dx64, dx32, f"lstm {shape} dxproj")
+    close(gw, dw64, dw32, f"lstm {shape} dW_hh")
 
 
 for _s in [(1, 1), (3, 5), (8, 5)]:
@@ -429,10 +390,10 @@ def _deconv_case(shape, place):
     _call("eamm_op_deconv4s2_wgrad", xd, gd, b, h, w, cin, cp, dw, db,
           work=_work(place, "eamm_op_deconv4s2_wgrad_workspace_floats", b, h, w, cin, cp, name="wgrad workspace"))
     torch.cuda.synchronize()
-    aud.close(y[..., :cout], aud.nhwc(y64), aud.nhwc(y32), f"deconv {shape} forward")
-    aud.close(dx, aud.nhwc(dx64), aud.nhwc(dx32), f"deconv {shape} data gradient")
-    aud.close(dw[:, :cout], dw64, dw32, f"deconv {shape} weight gradient")
-    aud.close(db[:cout], db64, db32, f"deconv {shape} bias gradient")
+    close(y[..., :cout], aud.nhwc(y64), aud.nhwc(y32), f"deconv {shape} forward")
+    close(dx, aud.nhwc(dx64), aud.nhwc(dx32), f"deconv {shape} data gradient")
+    close(dw[:, :cout], dw64, dw32, f"deconv {shape} weight gradient")
+    close(db[:cout], db64, db32, f"deconv {shape} bias gradient")
 
 
 for _s in [(1, 1, 1, 32, 32), (3, 4, 4, 64, 35), (2, 5, 3, 256, 128)]:
@@ -614,9 +575,9 @@ for _a in [(1, 20, 12, 4), (1, 8, 8, 4), (2, 12, 20, 1)]:
     case("motion-antialias_%d_%d_%d_inv%d" % _a, ["eamm_op_antialias_down", "eamm_op_antialias_down_backward"], functools.partial(_antialias_case, *_a))
 
 
-# ---- the perceptual loss's small kernels: test_gpu_perceptual_ops.py's references, perceptual_common.close ---------------------------------
+# ---- the perceptual loss's small kernels: test_gpu_perceptual_ops.py's references, closeness.close ----------------------------------------
 import test_gpu_perceptual_ops as perc
-from perceptual_common import _MEAN, _STD, close as perc_close, ref_level
+from perceptual_common import _MEAN, _STD, ref_level
 
 
 def _vgg_input_case(inv, place, shape=(2, 3, 40, 24)):
@@ -639,9 +600,9 @@ def _vgg_input_case(inv, place, shape=(2, 3, 40, 24)):
     _call("eamm_op_vgg_input_backward", gd, 32, None, kd, sd, b, hh, ww, inv, grad)
     torch.cuda.synchronize()
     assert int(torch.count_nonzero(out[..., 3:])) == 0
-    perc_close(out[..., :3], want[torch.float64][0], want[torch.float32][0], f"vgg_input {shape} 1/{inv}")
-    perc_close(grad, want[torch.float64][1], want[torch.float32][1], f"vgg_input backward {shape} 1/{inv}")
-    perc_close(level, ref_level(x.double(), inv), ref_level(x, inv), f"level {shape} 1/{inv}")
+    close(out[..., :3], want[torch.float64][0], want[torch.float32][0], f"vgg_input {shape} 1/{inv}")
+    close(grad, want[torch.float64][1], want[torch.float32][1], f"vgg_input backward {shape} 1/{inv}")
+    close(level, ref_level(x.double(), inv), ref_level(x, inv), f"level {shape} 1/{inv}")
 
 
 for _i in (1, 8):
@@ -667,7 +628,7 @@ def _relu_pool_case(place, shape=(1, 7, 5, 32)):
     _call("eamm_op_relu_pool_backward", xd, dy, dp, b, h, w, c, dx)
     torch.cuda.synchronize()
     assert torch.equal(xd.cpu(), want[torch.float32][0]) and torch.equal(pooled.cpu(), want[torch.float32][1])
-    perc_close(dx, want[torch.float64][2], want[torch.float32][2], f"relu_pool backward {shape}")
+    close(dx, want[torch.float64][2], want[torch.float32][2], f"relu_pool backward {shape}")
 
 
 @case("perc-l1_pair_1155", ["eamm_op_l1_pair", "eamm_op_l1_pair_backward"])
@@ -686,7 +647,7 @@ def _l1_pair_case(place, shape=(3, 5, 7, 11)):
     torch.cuda.synchronize()
     err, bar = abs(float(value) - float(want64)), max(4 * abs(float(want32) - float(want64)), 2e-5 * abs(float(want64)))
     assert err <= bar, (err, bar)
-    perc_close(ga, 3.0 * g64, (3.0 * g64).float(), f"l1_pair gradient {shape}")
+    close(ga, 3.0 * g64, (3.0 * g64).float(), f"l1_pair gradient {shape}")
     assert int(torch.count_nonzero(ga.reshape(-1)[::7])) == 0
 
 
@@ -1188,6 +1149,10 @@ def test_audio_lstm_features_on_skewed_boundary_tensors():
     assert torch.equal(first, run(Plain(DEV))["lstm_out"])
 
 
+# ---- every guarded case, of this file and of the other modules that register some ------------------------------------------------------------
+import test_gpu_conv_dev_1x1, test_gpu_disc_ops, test_gpu_equivariance_ops  # noqa: E401,F401  (the modules that register cases: this list)
+
+
 @pytest.mark.parametrize("cid", list(CASES))
 def test_guarded(cid):
-    run_three(cid)
+    run_three(cid, DEV)

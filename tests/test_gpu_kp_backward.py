@@ -2,7 +2,7 @@
 ``eamm_amd.kp_ops.kp_head``) and the detectors' differentiable forward, against the oracle differentiated by autograd in float64
 on the CPU (``oracle/eamm_oracle.py``: kp_head, kp_detector_forward, kp_detector_a_forward, generator_forward).
 
-Bars (tests/test_train_backward.py), per tensor, relative to its largest reference entry: max(4 x the oracle's own fp32-vs-fp64
+Bars (tests/closeness.py), per tensor, relative to its largest reference entry: max(4 x the oracle's own fp32-vs-fp64
 distance for that tensor, a floor).  The floor is TIGHT_MIN_REL where no ReLU lies between the tensor and the loss (the
 operator, the heads' parameters, KPDetector_a's feature map) and FP32_MIN_REL behind ReLUs (the hourglass's parameters and the
 image: every path from them to the loss crosses the hourglass's ReLUs; in the chain test every detector tensor, since the
@@ -15,6 +15,7 @@ room to spare (no tensor's fp32-vs-fp64 distance above a fifth of FP32_MIN_REL: 
 import pytest
 import torch
 
+from closeness import kp_close
 from eamm_amd import KPDetector, KPDetector_a, OcclusionAwareGenerator, tiny_config, tiny_kp_config
 from eamm_amd.weights import kp_state_dict_spec, synthetic_keypoints, synthetic_source, synthetic_state_dict
 from oracle import eamm_oracle as orc
@@ -27,30 +28,7 @@ T = 0.1                   # the shipped configurations' temperature
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-def close(got, want, want32, what, floor, relu=False, gmax=None):
-    """One tensor against its float64 reference ``want``; ``want32`` = the oracle's fp32 run of the same computation.  Entries that
-    are not finite in the reference (a window of one pixel has the grid 0 / 0) must be not finite here too."""
-    got, want, want32 = got.detach().cpu().double().reshape(-1), want.detach().double().reshape(-1), want32.detach().double().reshape(-1)
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    fin = torch.isfinite(want)
-    assert bool((torch.isfinite(got) == fin).all()), (what, "finite entries differ")
-    if not bool(fin.any()):
-        return 0.0
-    got, want, want32 = got[fin], want[fin], want32[fin]
-    scale = float(want.abs().max())
-    if scale == 0.0 or (gmax is not None and scale < 1e-9 * gmax):   # a gradient that is zero by construction: the largest tensor's scale
-        scale = gmax if gmax else 1.0
-    bar = max(4.0 * float((want32 - want).abs().max()) / scale, floor) * scale
-    diff = (got - want).abs()
-    print(f"  {what:60s} err/scale {float(diff.max()) / scale:.2e}  oracle fp32 {float((want32 - want).abs().max()) / scale:.2e}  "
-          f"bar/scale {bar / scale:.2e}")
-    if relu:
-        allowed = max(2, diff.numel() // 200) if diff.numel() >= 400 else 1
-        assert int((diff > bar).sum()) <= allowed, (what, int((diff > bar).sum()), allowed, float(diff.max()), bar)
-        assert float(diff.max()) <= 20 * bar, (what, float(diff.max()), bar)
-    else:
-        assert float(diff.max()) <= bar, (what, float(diff.max()), bar)
-    return float(diff.max()) / bar
+close = lambda *a, **k: kp_close(*a, nonfinite="match", **k)      # a window of one pixel has the grid 0 / 0: not finite in the reference and here
 
 
 def head_expression(logits, K, njm, pad, temperature):

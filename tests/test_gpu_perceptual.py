@@ -12,7 +12,8 @@ import pytest
 import torch
 
 from eamm_amd import ImagePyramide, PerceptualLoss, Vgg19, l1_pair, tiny_config
-from perceptual_common import OP_FLOOR, close, fragile_decisions, grad_close, image_pair, ref_level, ref_loss, ref_vgg, vgg_state
+from closeness import OP_FLOOR, close, grad_close
+from perceptual_common import fragile_decisions, image_pair, ref_level, ref_loss, ref_vgg, vgg_state
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"

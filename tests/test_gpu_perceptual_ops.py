@@ -1,6 +1,6 @@
 """The perceptual loss's operators one by one (eamm_amd/perceptual_ops.py; csrc/perceptual.hip) against float64 torch on the CPU:
 ``vgg_input`` (pyramid level + normalisation + conv1_1's layout), ``relu_pool``, ``l1_pair``, the frozen convolution on the tiny deep
-maps VGG19 ends in, and conv1_1's four-channel data gradient.  Bars: ``perceptual_common.close`` -- 4 x ATen's own fp32 distance from
+maps VGG19 ends in, and conv1_1's four-channel data gradient.  Bars: ``closeness.close`` -- 4 x ATen's own fp32 distance from
 float64, at least 2e-5 of the tensor's largest value."""
 import pytest
 import torch
@@ -8,7 +8,8 @@ import torch.nn.functional as F
 
 from eamm_amd import perceptual_ops as P
 from eamm_amd.weights import antialias_kernel
-from perceptual_common import _MEAN, _STD, close, ref_level
+from closeness import close
+from perceptual_common import _MEAN, _STD, ref_level
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"

@@ -1,6 +1,6 @@
 """tests/guarded.py on CPU tensors (placement arithmetic, both skews, the band-width rule, what check() reports) and the
-completeness of tests/test_gpu_guarded_ops.py's table: every operator entry that takes a pointer has a guarded case or a stated
-reason for having none.  No GPU."""
+completeness of its registry once every registering module is imported: every entry of ``guarded.OPERATOR_FAMILIES`` that takes a
+pointer has a guarded case or a stated reason for having none.  No GPU."""
 import ctypes as C
 
 import pytest
@@ -124,17 +124,21 @@ def test_plain_placement_is_what_the_tests_did_and_outputs_compare_bit_for_bit()
     assert same_outputs(plain, arena) == ["o"]
 
 
-# ---- completeness of the guarded table -----------------------------------------------------------------------------------------
+# ---- completeness of the guarded registry ----------------------------------------------------------------------------------------
 def test_every_operator_entry_with_a_pointer_has_a_guarded_case_or_a_reason():
     from eamm_amd import _lib
-    import test_gpu_guarded_ops as g
+    import test_gpu_guarded_ops as g            # imports every module that registers cases, and shows the registry
     need = [name for name, (_, args) in _lib.SIGNATURES.items()
-            if name.startswith(("eamm_op_", "eamm_bn_")) and any(a is C.c_void_p for a in args)]
-    assert len(need) > 70
+            if name.startswith(guarded.OPERATOR_FAMILIES) and any(a is C.c_void_p for a in args)]
+    count = lambda *prefixes: sum(n.startswith(prefixes) for n in need)
+    assert (count("eamm_op_", "eamm_bn_"), count("eamm_disc_"), count("eamm_equi_")) == (75, 4, 3) and len(need) == 82, need
+    assert sum(n in g.GUARDED for n in need) == 81 and "eamm_op_lstm_check" in g.EXEMPT and "eamm_final_split_planes" in g.EXEMPT
     missing = [n for n in need if n not in g.GUARDED and n not in g.EXEMPT]
-    assert not missing, ("entries with neither a guarded case in tests/test_gpu_guarded_ops.py nor a reason in its EXEMPT", missing)
+    assert not missing, ("entries with neither a guarded case registered in tests/guarded.py nor a reason in its EXEMPT", missing)
     assert not [n for n in g.EXEMPT if n in g.GUARDED], "an entry is either guarded or exempt"
     assert all(n in _lib.SIGNATURES and isinstance(why, str) and len(why) > 10 for n, why in g.EXEMPT.items())
     assert all(ids and all(i in g.CASES for i in ids) for ids in g.GUARDED.values())
-    # every case runs: the GPU test is parametrised over the whole table
+    # every case runs: the GPU test is parametrised over the whole registry
     assert sorted(g.CASES) == sorted({i for ids in g.GUARDED.values() for i in ids})
+    # the size queries take no pointer; each discriminator entry with a workspace has one
+    assert all(n + "_workspace_floats" in _lib.SIGNATURES for n in need if n.startswith("eamm_disc_"))

@@ -1,18 +1,21 @@
-"""Every operator entry (eamm_op_*, include/eamm_hip.h) refuses an all-NULL, all-zero call with EAMM_ERR_ARG and a message that
-starts with its own name, before it touches a device -- the argument check comes first in each entry, so this runs without a GPU.
-It pins which entry says what: an entry that lost its check, or two entries whose messages were swapped, fail here."""
+"""Every operator entry (eamm_op_*, eamm_disc_*, eamm_equi_*, include/eamm_hip.h) refuses an all-NULL, all-zero call with
+EAMM_ERR_ARG and a message that starts with its own name, before it touches a device -- the argument check comes first in each
+entry, so this runs without a GPU.  An entry that lost its check, or two entries whose messages were swapped, fail here."""
 import ctypes
 
 import pytest
 
 from eamm_amd import _lib
+from guarded import OPERATOR_FAMILIES
 
+# not eamm_bn_*: that family takes no device argument and reports through eamm_bn_last_error, with messages that carry no entry name
+FAMILIES = tuple(f for f in OPERATOR_FAMILIES if f != "eamm_bn_")
 # takes no refusable argument (a device and a stream): an all-zero call would open device 0 and wait for its NULL stream
 NO_ARGUMENT_CHECK = {"eamm_op_lstm_check"}
 
 OP_ENTRIES = sorted(n for n, (res, _) in _lib.SIGNATURES.items()
-                    if n.startswith("eamm_op_") and res is ctypes.c_int and n not in NO_ARGUMENT_CHECK)
-WORKSPACE_QUERIES = sorted(n for n in _lib.SIGNATURES if n.startswith("eamm_op_") and n.endswith("_workspace_floats"))
+                    if n.startswith(FAMILIES) and res is ctypes.c_int and n not in NO_ARGUMENT_CHECK)
+WORKSPACE_QUERIES = sorted(n for n in _lib.SIGNATURES if n.startswith(FAMILIES) and n.endswith("_workspace_floats"))
 
 
 def zeros(name):
@@ -22,7 +25,7 @@ def zeros(name):
 
 
 def test_the_lists_are_not_empty():
-    assert len(OP_ENTRIES) >= 53 and len(WORKSPACE_QUERIES) >= 13
+    assert len(OP_ENTRIES) >= 53 + 4 + 3 and len(WORKSPACE_QUERIES) >= 13 + 4         # + eamm_disc_*, eamm_equi_*
     assert all(_lib.SIGNATURES[n][0] is ctypes.c_size_t for n in WORKSPACE_QUERIES)
 
 
