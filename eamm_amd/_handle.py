@@ -14,8 +14,12 @@ import torch
 from . import _lib
 
 
-def ptr(t: Optional[torch.Tensor]):
-    """Tensor or None -> its address as a ``c_void_p``, or None (a NULL argument)."""
+def ptr(t: Optional[torch.Tensor], entry: Optional[str] = None, operand: Optional[int] = None):
+    """Tensor or None -> its address as a ``c_void_p``, or None (a NULL argument).  The ONE place where the binding turns a tensor
+    into an address: ``_op.call`` and the BatchNorm calls convert here and say which ``entry`` and which of its C arguments
+    (``operand``, counted from 0) the address is for.  Nothing is checked here -- the public wrappers refuse a wrong dtype or device
+    and copy what is strided or off a 16-byte boundary (``_op.operands``, ``_op.dense``) -- but tests/calling.py replaces this
+    function to look at every tensor before the library does."""
     return None if t is None else C.c_void_p(t.data_ptr())
 
 

@@ -49,7 +49,7 @@ class _LstmLayerFunction(torch.autograd.Function):
         dev = xproj.device
         y = torch.empty(n, t, HIDDEN, dtype=torch.float32, device=dev)
         work = _op.workspace("lstm", dev, n, t)     # the call's own W_hh image, state and hand-off words
-        w = w_hh.detach().contiguous()
+        w = _op.dense(w_hh.detach())
         _op.call("lstm_forward", dev, xproj, w, n, t, y, work=work)
         ctx.save_for_backward(xproj, w_hh, y)
         return y
@@ -59,8 +59,8 @@ class _LstmLayerFunction(torch.autograd.Function):
         xproj, w_hh, y = ctx.saved_tensors
         n, t, _ = xproj.shape
         dev = xproj.device
-        w = w_hh.detach().contiguous()
-        grad_y = grad_y.contiguous()
+        w = _op.dense(w_hh.detach())
+        grad_y = _op.dense(grad_y)
         h_prev = torch.cat([y.new_zeros(n, 1, HIDDEN), y[:, :-1]], dim=1).reshape(n * t, HIDDEN)          # h_{t-1}, zero state first
         gates = torch.addmm(xproj.detach().reshape(n * t, 4 * HIDDEN), h_prev, w.t()).view(n, t, 4 * HIDDEN).contiguous()
         c = torch.empty(n, t, HIDDEN, dtype=torch.float32, device=dev)
@@ -82,8 +82,8 @@ class _Deconv4s2Function(torch.autograd.Function):
         dev = x.device
         out = torch.empty(b, 2 * h, 2 * w, cout, dtype=torch.float32, device=dev)
         work = _op.workspace("deconv4s2", dev, b, h, w, cin, cout)
-        wt = weight.detach().contiguous()
-        bs = bias.detach().contiguous() if bias is not None else None
+        wt = _op.dense(weight.detach())
+        bs = _op.dense(bias.detach()) if bias is not None else None
         _op.call("deconv4s2", dev, x, b, h, w, cin, wt, bs, cout, out, work=work)
         ctx.save_for_backward(x, weight)
         ctx.has_bias = bias is not None
@@ -96,13 +96,13 @@ class _Deconv4s2Function(torch.autograd.Function):
         b, h, w, cin = x.shape
         cout = weight.shape[1]
         dev = x.device
-        grad_out = grad_out.contiguous()
+        grad_out = _op.dense(grad_out)
         gx = gw = gb = None
         want_b = ctx.has_bias and ctx.needs_input_grad[2]
         if ctx.needs_input_grad[0]:
             gx = torch.empty_like(x)
             work = _op.workspace("deconv4s2_dgrad", dev, b, h, w, cin, cout)
-            wt = weight.detach().contiguous()
+            wt = _op.dense(weight.detach())
             _op.call("deconv4s2_dgrad", dev, grad_out, b, h, w, cin, wt, cout, gx, work=work)
         if ctx.needs_input_grad[1] or want_b:
             gw = torch.empty_like(weight, memory_format=torch.contiguous_format)
@@ -133,7 +133,7 @@ class _MaxPool3Function(torch.autograd.Function):
         x, = ctx.saved_tensors
         b, h, w, c = x.shape
         sy, sx = ctx.strides
-        grad_out = grad_out.contiguous()
+        grad_out = _op.dense(grad_out)
         gx = torch.empty_like(x)
         _op.call("audio_maxpool_backward", x.device, x, grad_out, b, h, w, c, sy, sx, gx)
         return gx, None, None
@@ -155,10 +155,8 @@ def lstm_layer(xproj: torch.Tensor, w_hh: torch.Tensor) -> torch.Tensor:
         raise ValueError(f"lstm_layer: w_hh must be [{4 * HIDDEN},{HIDDEN}], got {tuple(getattr(w_hh, 'shape', ()))}")
     if n * t * 4 * HIDDEN >= 2 ** 31:
         raise ValueError("lstm_layer: fewer than 2^31 gate values")
-    _op.need_gpu(xproj, "audio_ops", "lstm_layer")
-    if w_hh.device != xproj.device or w_hh.dtype != torch.float32:
-        raise RuntimeError("lstm_layer: w_hh must be float32 on the input's device")
-    return _LstmLayerFunction.apply(xproj.contiguous(), w_hh)
+    _op.operands("audio_ops", "lstm_layer", xproj, w_hh)
+    return _LstmLayerFunction.apply(_op.dense(xproj), w_hh)
 
 
 def conv_transpose4s2_nhwc(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None,
@@ -184,9 +182,7 @@ def conv_transpose4s2_nhwc(x: torch.Tensor, weight: torch.Tensor, bias: Optional
     cin_p, cout_p = round_up(cin, CHANNEL_GRANULE), round_up(cout, CHANNEL_GRANULE)
     if max(b * h * w * cin_p, 4 * b * h * w * cout_p) * 4 >= 2 ** 32 - 16:
         raise ValueError(f"conv_transpose4s2_nhwc: input {tuple(x.shape)} / output beyond the kernels' 32-bit byte offsets")
-    _op.need_gpu(x, "audio_ops", "conv_transpose4s2_nhwc")
-    if weight.device != x.device or (bias is not None and bias.device != x.device):
-        raise RuntimeError("conv_transpose4s2_nhwc: weight, bias and input are on different devices")
+    _op.operands("audio_ops", "conv_transpose4s2_nhwc", x, weight, bias)
     if cin_p != cin:
         x = F.pad(x, (0, cin_p - cin))
         weight = F.pad(weight, (0, 0, 0, 0, 0, 0, 0, cin_p - cin))
@@ -195,7 +191,7 @@ def conv_transpose4s2_nhwc(x: torch.Tensor, weight: torch.Tensor, bias: Optional
         bias = F.pad(bias, (0, cout_p - cout)) if bias is not None else None
     if _lib.lib().eamm_op_deconv4s2_workspace_floats(b, h, w, cin_p, cout_p) == 0:
         raise ValueError(f"conv_transpose4s2_nhwc: unsupported shape {tuple(x.shape)} x {tuple(weight.shape)}")
-    y = _Deconv4s2Function.apply(x.contiguous(), weight, bias, bias_grad_is_zero)
+    y = _Deconv4s2Function.apply(_op.dense(x), weight, bias, bias_grad_is_zero)
     return y[..., :cout] if cout_p != cout else y
 
 
@@ -214,4 +210,4 @@ def maxpool3_nhwc(x: torch.Tensor, sy: int, sx: int) -> torch.Tensor:
     if x.numel() >= 2 ** 31:
         raise ValueError("maxpool3_nhwc: fewer than 2^31 elements")
     _op.need_gpu(x, "audio_ops", "maxpool3_nhwc")
-    return _MaxPool3Function.apply(x.contiguous(), int(sy), int(sx))
+    return _MaxPool3Function.apply(_op.dense(x), int(sy), int(sx))

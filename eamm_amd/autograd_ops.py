@@ -67,7 +67,7 @@ class _WarpFunction(torch.autograd.Function):
         feat, deformation, occlusion = ctx.saved_tensors
         n, h, w = deformation.shape[:3]
         ns, c = feat.shape[0], feat.shape[3]
-        grad_out = grad_out.contiguous()
+        grad_out = _op.dense(grad_out)
         need = ctx.needs_input_grad
         gf = torch.empty_like(feat) if need[0] else None
         gd = torch.empty_like(deformation) if need[1] else None
@@ -84,7 +84,7 @@ def warp(features: torch.Tensor, deformation: torch.Tensor, occlusion: Optional[
     features NCHW [n,C,h,w] or [1,C,h,w] (one source for all frames); deformation [n,h,w,2]; occlusion [n,1,h,w] or None;
     flow and occlusion at the features' resolution (the reference's bilinear resize of a coarser flow stays a torch op in
     front of this one).  Returns NCHW [n,C,h,w]."""
-    _op.need_gpu(features, "autograd_ops", "warp")
+    _op.operands("autograd_ops", "warp", features, deformation, occlusion)
     n, h, w, two = deformation.shape
     if two != 2 or features.shape[2:] != (h, w) or features.shape[0] not in (1, n) or features.shape[1] % 8:
         raise ValueError(f"warp: features {tuple(features.shape)} / deformation {tuple(deformation.shape)} mismatch "
@@ -93,8 +93,8 @@ def warp(features: torch.Tensor, deformation: torch.Tensor, occlusion: Optional[
     if occlusion is not None:
         if tuple(occlusion.shape) != (n, 1, h, w):
             raise ValueError(f"warp: occlusion must be [{n},1,{h},{w}], got {tuple(occlusion.shape)}")
-        occ = occlusion.reshape(n, h, w).contiguous()
-    out = _WarpFunction.apply(features.permute(0, 2, 3, 1).contiguous(), deformation.contiguous(), occ)
+        occ = _op.dense(occlusion.reshape(n, h, w))
+    out = _WarpFunction.apply(_op.dense(features.permute(0, 2, 3, 1)), _op.dense(deformation), occ)
     return out.permute(0, 3, 1, 2)
 
 
@@ -114,8 +114,8 @@ class _Conv2dSameFunction(torch.autograd.Function):
         if nwork == 0:
             raise ValueError(f"conv2d_same: unsupported convolution {tuple(x.shape)} x {tuple(weight.shape)}")
         work = torch.empty(nwork, dtype=torch.float32, device=x.device)
-        wt = weight.detach().contiguous()
-        bt = bias.detach().contiguous() if bias is not None else None
+        wt = _op.dense(weight.detach())
+        bt = _op.dense(bias.detach()) if bias is not None else None
         _op.call("conv_dev", x.device, x, b, h, w, cin, wt, bt, cout, kh, kw, int(transposed), out, work=work)
         return (out, work) if keep_work else out
 
@@ -140,7 +140,7 @@ class _Conv2dSameFunction(torch.autograd.Function):
     def backward(ctx, grad_out):
         x, weight = ctx.saved_tensors[:2]
         saved_work = ctx.saved_tensors[2] if ctx.v_offset != _NO_OFFSET else None
-        grad_out = grad_out.contiguous()
+        grad_out = _op.dense(grad_out)
         b, h, w, cin = x.shape
         cout, _, kh, kw = weight.shape
         gx = gw = gb = side = None
@@ -184,7 +184,7 @@ class _FirstConv7Function(torch.autograd.Function):
         n = weight.shape[0]
         out = torch.empty(b, h, w, n, dtype=torch.float32, device=x4.device)
         work = _op.workspace("conv7_thin", x4.device, b, h, w, n)
-        wt, bt = weight.detach().contiguous(), bias.detach().contiguous()
+        wt, bt = _op.dense(weight.detach()), _op.dense(bias.detach())
         _op.call("conv7_thin", x4.device, x4, wt, bt, b, h, w, n, 0, out, work=work)
         ctx.save_for_backward(x4, weight)
         return out
@@ -192,7 +192,7 @@ class _FirstConv7Function(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         x4, weight = ctx.saved_tensors
-        grad_out = grad_out.contiguous()
+        grad_out = _op.dense(grad_out)
         b, h, w, _ = x4.shape
         n = weight.shape[0]
         gx = gw = gb = None
@@ -219,7 +219,7 @@ class _FinalConvSigmoidFunction(torch.autograd.Function):
         b, h, w, n = x.shape
         y = torch.empty(b, 3, h, w, dtype=torch.float32, device=x.device)
         work = torch.empty(7 * n * 32, dtype=torch.float32, device=x.device)
-        wt, bt = weight.detach().contiguous(), bias.detach().contiguous()
+        wt, bt = _op.dense(weight.detach()), _op.dense(bias.detach())
         _op.call("final_conv_sigmoid", x.device, x, wt, bt, b, h, w, n, y, work=work)
         ctx.save_for_backward(x, weight, y)
         return y
@@ -228,13 +228,14 @@ class _FinalConvSigmoidFunction(torch.autograd.Function):
     def backward(ctx, grad_y):
         x, weight, y = ctx.saved_tensors
         b, h, w, n = x.shape
+        grad_y = _op.dense(grad_y)                                                          # (the sums below keep one order whatever layout the gradient arrives in)
         g = grad_y * y * (1.0 - y)                                                          # through the sigmoid, NCHW [B,3,H,W]
         g4 = torch.nn.functional.pad(g.permute(0, 2, 3, 1), (0, 1)).contiguous()             # NHWC, four floats per pixel
         work = _op.workspace("conv7_thin", x.device, b, h, w, n)
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:
             gx = torch.empty_like(x)
-            wt = weight.detach().contiguous()
+            wt = _op.dense(weight.detach())
             _op.call("conv7_thin", x.device, g4, wt, None, b, h, w, n, 1, gx, work=work)
         if ctx.needs_input_grad[1]:
             gw = torch.empty_like(weight, memory_format=torch.contiguous_format)
@@ -247,18 +248,18 @@ class _FinalConvSigmoidFunction(torch.autograd.Function):
 
 def first_conv7(x4: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, bias_grad_is_zero: bool = False) -> torch.Tensor:
     """7x7 "same" convolution of a three-channel image (NHWC [B,H,W,4], fourth channel zero) to N = 32 | 64 channels."""
-    _op.need_gpu(x4, "autograd_ops", "first_conv7")
+    _op.operands("autograd_ops", "first_conv7", x4, weight, bias)
     if x4.shape[3] != 4 or tuple(weight.shape[1:]) != (3, 7, 7) or weight.shape[0] not in (32, 64) or bias is None:
         raise ValueError(f"first_conv7: input {tuple(x4.shape)} / weight {tuple(weight.shape)} unsupported")
-    return _FirstConv7Function.apply(x4.contiguous(), weight, bias, bias_grad_is_zero)
+    return _FirstConv7Function.apply(_op.dense(x4), weight, bias, bias_grad_is_zero)
 
 
 def final_conv7_sigmoid(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
     """sigmoid(7x7 "same" convolution of NHWC [B,H,W,N], N = 32 | 64, to three channels + bias) -> NCHW [B,3,H,W]."""
-    _op.need_gpu(x, "autograd_ops", "final_conv7_sigmoid")
+    _op.operands("autograd_ops", "final_conv7_sigmoid", x, weight, bias)
     if tuple(weight.shape) != (3, x.shape[3], 7, 7) or x.shape[3] not in (32, 64) or bias is None:
         raise ValueError(f"final_conv7_sigmoid: input {tuple(x.shape)} / weight {tuple(weight.shape)} unsupported")
-    return _FinalConvSigmoidFunction.apply(x.contiguous(), weight, bias)
+    return _FinalConvSigmoidFunction.apply(_op.dense(x), weight, bias)
 
 
 def conv2d_same_nhwc(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None,
@@ -266,37 +267,33 @@ def conv2d_same_nhwc(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch
     """``conv2d_same`` on the kernels' own layout: x NHWC [B,H,W,Cin] -> NHWC [B,H,W,Cout] (no layout copies).
     ``bias_grad_is_zero``: the output feeds a batch-statistics BatchNorm directly, so the bias gradient is exactly zero and is
     returned as zeros without being computed."""
-    _op.need_gpu(x, "autograd_ops", "conv2d_same_nhwc")
+    _op.operands("autograd_ops", "conv2d_same_nhwc", x, weight, bias)
     cout, cin, kh, kw = weight.shape
     if (kh, kw) not in ((3, 3), (7, 7)) or x.shape[3] != cin or cin % CHANNEL_GRANULE or cout % CHANNEL_GRANULE:
         raise ValueError(f"conv2d_same_nhwc: weight {tuple(weight.shape)} / input {tuple(x.shape)} unsupported "
                          f"(3x3 or 7x7, channels multiples of {CHANNEL_GRANULE})")
-    if weight.device != x.device or (bias is not None and bias.device != x.device):
-        raise RuntimeError("conv2d_same_nhwc: parameters and input are on different devices")
-    return _Conv2dSameFunction.apply(x.contiguous(), weight, bias, bias_grad_is_zero)
+    return _Conv2dSameFunction.apply(_op.dense(x), weight, bias, bias_grad_is_zero)
 
 
 def warp_nhwc(features: torch.Tensor, deformation: torch.Tensor, occlusion: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``warp`` on NHWC features [n|1,h,w,C] (C a multiple of 8), flow [n,h,w,2], occlusion [n,h,w] or None -> NHWC [n,h,w,C]."""
-    _op.need_gpu(features, "autograd_ops", "warp_nhwc")
+    _op.operands("autograd_ops", "warp_nhwc", features, deformation, occlusion)
     n, h, w, two = deformation.shape
     if two != 2 or features.shape[1:3] != (h, w) or features.shape[0] not in (1, n) or features.shape[3] % 8:
         raise ValueError(f"warp_nhwc: features {tuple(features.shape)} / deformation {tuple(deformation.shape)} mismatch")
     if occlusion is not None and tuple(occlusion.shape) != (n, h, w):
         raise ValueError(f"warp_nhwc: occlusion must be [{n},{h},{w}], got {tuple(occlusion.shape)}")
-    return _WarpFunction.apply(features.contiguous(), deformation.contiguous(), None if occlusion is None else occlusion.contiguous())
+    return _WarpFunction.apply(_op.dense(features), _op.dense(deformation), None if occlusion is None else _op.dense(occlusion))
 
 
 def conv2d_same(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``F.conv2d(x, weight, bias, padding=k // 2)`` for the path's square 3x3 / 7x7 filters (reference modules/util.py:858-938),
     differentiable in x, weight and bias.  x NCHW [B,Cin,H,W], weight [Cout,Cin,k,k] on the GPU; Cin and Cout multiples of 32
     (the granule of the forward kernels, which also compute the data gradient).  Returns NCHW."""
-    _op.need_gpu(x, "autograd_ops", "conv2d_same")
+    _op.operands("autograd_ops", "conv2d_same", x, weight, bias)
     cout, cin, kh, kw = weight.shape
     if (kh, kw) not in ((3, 3), (7, 7)) or x.shape[1] != cin or cin % CHANNEL_GRANULE or cout % CHANNEL_GRANULE:
         raise ValueError(f"conv2d_same: weight {tuple(weight.shape)} / input {tuple(x.shape)} unsupported "
                          f"(3x3 or 7x7, channels multiples of {CHANNEL_GRANULE})")
-    if weight.device != x.device or (bias is not None and bias.device != x.device):
-        raise RuntimeError("conv2d_same: parameters and input are on different devices")
-    out = _Conv2dSameFunction.apply(x.permute(0, 2, 3, 1).contiguous(), weight, bias, False)
+    out = _Conv2dSameFunction.apply(_op.dense(x.permute(0, 2, 3, 1)), weight, bias, False)
     return out.permute(0, 3, 1, 2)

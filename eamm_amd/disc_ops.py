@@ -43,7 +43,7 @@ class _Conv4Function(torch.autograd.Function):
         cout, cw = weight.shape[:2]
         out = torch.empty(b, h - 3, w - 3, cout, dtype=torch.float32, device=x.device)
         work = _op.workspace("conv4", x.device, b, h, w, cw, cout, 0, 0, thin, family="disc")
-        _op.call("conv4", x.device, x, b, h, w, cw, weight.detach().contiguous(), None if bias is None else bias.detach().contiguous(),
+        _op.call("conv4", x.device, x, b, h, w, cw, _op.dense(weight.detach()), None if bias is None else _op.dense(bias.detach()),
                  cout, 0, 0, thin, out, work=work, family="disc")
         ctx.save_for_backward(x, weight)
         ctx.thin, ctx.has_bias = thin, bias is not None
@@ -53,7 +53,7 @@ class _Conv4Function(torch.autograd.Function):
     def backward(ctx, grad_out):
         x, weight = ctx.saved_tensors
         thin = ctx.thin
-        grad_out = grad_out.contiguous()
+        grad_out = _op.dense(grad_out)
         b, h, w, cx = x.shape
         cout, cw = weight.shape[:2]
         gx = gw = gb = None
@@ -61,7 +61,7 @@ class _Conv4Function(torch.autograd.Function):
             # dX = valid 4x4 correlation of dY zero-padded by 3 with the filter transposed over (out, in) and flipped over (y, x)
             gx = torch.empty_like(x)
             work = _op.workspace("conv4", x.device, b, h - 3, w - 3, cout, cw, 3, 1, thin, family="disc")
-            _op.call("conv4", x.device, grad_out, b, h - 3, w - 3, cout, weight.detach().contiguous(), None, cw, 3, 1, thin, gx,
+            _op.call("conv4", x.device, grad_out, b, h - 3, w - 3, cout, _op.dense(weight.detach()), None, cw, 3, 1, thin, gx,
                      work=work, family="disc")
         want_b = ctx.has_bias and ctx.needs_input_grad[2]
         if ctx.needs_input_grad[1] or want_b:
@@ -78,7 +78,7 @@ def conv4_valid(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tens
     """``F.conv2d`` with a 4x4 filter, no padding, stride 1, on NHWC x [B,H,W,Cx] -> [B,H-3,W-3,Cout]; weight OIHW [Cout,Cw,4,4].
     ``Cw`` and ``Cout`` multiples of 32 with ``Cx == Cw`` -- or ``Cw <= 16`` with ``Cx == thin_channels(Cw)`` and exact zeros in x's
     channels ``Cw .. Cx-1`` (the thin first layer: K = 16 Cx instead of 16 x 32).  Differentiable in x, weight and bias."""
-    _op.need_gpu(x, _MODULE, "conv4_valid")
+    _op.operands(_MODULE, "conv4_valid", x, weight, bias)
     if weight.dim() != 4 or tuple(weight.shape[2:]) != (4, 4) or x.dim() != 4:
         raise ValueError(f"conv4_valid: a [Cout,Cin,4,4] filter and an NHWC input are required, got {tuple(weight.shape)} / {tuple(x.shape)}")
     cout, cw = weight.shape[:2]
@@ -90,9 +90,7 @@ def conv4_valid(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tens
                          f"thin_channels(Cin) floats per input pixel)")
     if x.shape[1] < 4 or x.shape[2] < 4:
         raise ValueError(f"conv4_valid: a {x.shape[1]} x {x.shape[2]} map is smaller than the 4 x 4 filter")
-    if weight.device != x.device or (bias is not None and bias.device != x.device):
-        raise RuntimeError("conv4_valid: parameters and input are on different devices")
-    return _Conv4Function.apply(x.contiguous(), weight, bias, thin)
+    return _Conv4Function.apply(_op.dense(x), weight, bias, thin)
 
 
 class _NormActPoolFunction(torch.autograd.Function):
@@ -103,8 +101,8 @@ class _NormActPoolFunction(torch.autograd.Function):
         out = torch.empty((b, h // 2, w // 2, c) if pool else (b, h, w, c), dtype=torch.float32, device=x.device)
         stats = torch.empty(b, c, 2, dtype=torch.float64, device=x.device) if norm else None
         work = _op.workspace("norm_act_pool", x.device, b, h, w, c, norm, family="disc") if norm else None
-        g = gamma.detach().contiguous() if norm else None
-        be = beta.detach().contiguous() if norm else None
+        g = _op.dense(gamma.detach()) if norm else None
+        be = _op.dense(beta.detach()) if norm else None
         _op.call("norm_act_pool", x.device, x, g, be, b, h, w, c, norm, int(pool), stats, out, work, 0 if work is None else work.numel(),
                  family="disc")
         ctx.save_for_backward(x, stats, gamma, beta)
@@ -119,13 +117,13 @@ class _NormActPoolFunction(torch.autograd.Function):
         if not (need_x or need_g or need_b):
             return None, None, None, None
         b, h, w, c = x.shape
-        grad_out = grad_out.contiguous()
+        grad_out = _op.dense(grad_out)
         gx = torch.empty_like(x) if need_x else None
         gg = torch.empty(c, dtype=torch.float32, device=x.device) if need_g else None
         gb = torch.empty(c, dtype=torch.float32, device=x.device) if need_b else None
         work = _op.workspace("norm_act_pool_backward", x.device, b, h, w, c, norm, family="disc") if norm else None
-        g = gamma.detach().contiguous() if norm else None
-        be = beta.detach().contiguous() if norm else None
+        g = _op.dense(gamma.detach()) if norm else None
+        be = _op.dense(beta.detach()) if norm else None
         _op.call("norm_act_pool_backward", x.device, x, stats, g, be, grad_out, b, h, w, c, norm, pool, gx, gg, gb, work,
                  0 if work is None else work.numel(), family="disc")
         return gx, gg, gb, None
@@ -136,7 +134,7 @@ def norm_act_pool(x: torch.Tensor, gamma: Optional[torch.Tensor], beta: Optional
     statistics; ``gamma = beta = None``: no normalisation), then with ``pool`` ``avg_pool2d(., 2)`` -> [B,H//2,W//2,C] (an odd last row
     or column feeds no window).  One apply pass over x; differentiable in x, gamma and beta (recomputed from x and the saved
     statistics).  C a multiple of 4."""
-    _op.need_gpu(x, _MODULE, "norm_act_pool")
+    _op.operands(_MODULE, "norm_act_pool", x, gamma, beta)
     if (gamma is None) != (beta is None):
         raise ValueError("norm_act_pool: gamma and beta come together")
     if x.dim() != 4 or x.shape[3] % 4 or (gamma is not None and (tuple(gamma.shape) != (x.shape[3],) or tuple(beta.shape) != (x.shape[3],))):
@@ -145,6 +143,4 @@ def norm_act_pool(x: torch.Tensor, gamma: Optional[torch.Tensor], beta: Optional
         raise ValueError("norm_act_pool: InstanceNorm needs more than one value per channel")
     if pool and (x.shape[1] < 2 or x.shape[2] < 2):
         raise ValueError(f"norm_act_pool: a {x.shape[1]} x {x.shape[2]} map has no 2 x 2 pooling window")
-    if gamma is not None and (gamma.device != x.device or beta.device != x.device):
-        raise RuntimeError("norm_act_pool: parameters and input are on different devices")
-    return _NormActPoolFunction.apply(x.contiguous(), gamma, beta, bool(pool))
+    return _NormActPoolFunction.apply(_op.dense(x), gamma, beta, bool(pool))

@@ -33,7 +33,7 @@ class _ConvS2Function(torch.autograd.Function):
         dev = x.device
         out = torch.empty(b, h // 2, w // 2, cout, dtype=torch.float32, device=dev)
         work = _op.workspace("conv_s2", dev, b, h, w, cin, cout, k)
-        wt = weight.detach().contiguous()
+        wt = _op.dense(weight.detach())
         _op.call("conv_s2", dev, x, b, h, w, cin, wt, cout, k, out, work=work)
         ctx.save_for_backward(x, weight)
         return out
@@ -44,12 +44,12 @@ class _ConvS2Function(torch.autograd.Function):
         b, h, w, cin = x.shape
         cout, _, k, _ = weight.shape
         dev = x.device
-        grad_out = grad_out.contiguous()
+        grad_out = _op.dense(grad_out)
         gx = gw = None
         if ctx.needs_input_grad[0]:
             gx = torch.empty_like(x)
             work = _op.workspace("conv_s2_dgrad", dev, b, h, w, cin, cout, k)
-            wt = weight.detach().contiguous()
+            wt = _op.dense(weight.detach())
             _op.call("conv_s2_dgrad", dev, grad_out, b, h, w, cin, wt, cout, k, gx, work=work)
         if ctx.needs_input_grad[1]:
             gw = torch.empty_like(weight, memory_format=torch.contiguous_format)
@@ -73,7 +73,7 @@ class _MaxPoolFunction(torch.autograd.Function):
     def backward(ctx, grad_out):
         x, = ctx.saved_tensors
         b, h, w, c = x.shape
-        grad_out = grad_out.contiguous()
+        grad_out = _op.dense(grad_out)
         gx = torch.empty_like(x)
         _op.call("emo_maxpool_backward", x.device, x, grad_out, b, h, w, c, gx)
         return gx
@@ -100,8 +100,8 @@ class _EmoFinalFunction(torch.autograd.Function):
             return None, None
         b = a.shape[0]
         dev = a.device
-        g_value = None if g_value is None else g_value.contiguous()
-        g_jac = None if g_jac is None else g_jac.contiguous()
+        g_value = None if g_value is None else _op.dense(g_value)
+        g_jac = None if g_jac is None else _op.dense(g_jac)
         ga, gw = torch.empty_like(a), torch.empty_like(w98)
         work = _op.workspace("emo_final", dev, b)
         _op.call("emo_final_backward", dev, a, w98, g_value, g_jac, b, ga, gw, work=work)
@@ -122,12 +122,10 @@ def conv2d_s2_nhwc(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
         raise ValueError(f"conv2d_s2_nhwc: even map sides only (odd sizes are out of scope), got {h} x {w}")
     if c != cin or cin % CHANNEL_GRANULE or cout % CHANNEL_GRANULE:
         raise ValueError(f"conv2d_s2_nhwc: weight {tuple(weight.shape)} / input {tuple(x.shape)} unsupported (channels multiples of {CHANNEL_GRANULE})")
-    _op.need_gpu(x, "emo_ops", "conv2d_s2_nhwc")
-    if weight.device != x.device:
-        raise RuntimeError("conv2d_s2_nhwc: weight and input are on different devices")
+    _op.operands("emo_ops", "conv2d_s2_nhwc", x, weight)
     if _lib.lib().eamm_op_conv_s2_workspace_floats(b, h, w, cin, cout, kh) == 0:
         raise ValueError(f"conv2d_s2_nhwc: unsupported convolution {tuple(x.shape)} x {tuple(weight.shape)}")
-    return _ConvS2Function.apply(x.contiguous(), weight)
+    return _ConvS2Function.apply(_op.dense(x), weight)
 
 
 def maxpool3s2_nhwc(x: torch.Tensor) -> torch.Tensor:
@@ -140,7 +138,7 @@ def maxpool3s2_nhwc(x: torch.Tensor) -> torch.Tensor:
     if x.numel() >= 2 ** 31:
         raise ValueError("maxpool3s2_nhwc: fewer than 2^31 elements")
     _op.need_gpu(x, "emo_ops", "maxpool3s2_nhwc")
-    return _MaxPoolFunction.apply(x.contiguous())
+    return _MaxPoolFunction.apply(_op.dense(x))
 
 
 def final_weights(final: Sequence[torch.nn.Module]) -> torch.Tensor:
@@ -156,7 +154,5 @@ def emo_final(a: torch.Tensor, w98: torch.Tensor) -> Tuple[torch.Tensor, torch.T
         raise ValueError(f"emo_final: input [B,64], got {tuple(a.shape)}")
     if w98.dim() != 1 or w98.numel() != 98:
         raise ValueError(f"emo_final: 98 weights (final_weights), got {tuple(w98.shape)}")
-    _op.need_gpu(a, "emo_ops", "emo_final")
-    if w98.device != a.device or w98.dtype != torch.float32:
-        raise RuntimeError("emo_final: weights must be float32 on the input's device")
-    return _EmoFinalFunction.apply(a.contiguous(), w98.contiguous())
+    _op.operands("emo_ops", "emo_final", a, w98)
+    return _EmoFinalFunction.apply(_op.dense(a), _op.dense(w98))

@@ -31,14 +31,14 @@ def _check_params(theta: torch.Tensor, control_params: Optional[torch.Tensor], p
         raise ValueError(f"{what}: points must be 0 (affine only) or 2..{MAX_POINTS}, got {points}")
     _op.need_gpu(theta, _MODULE, what)
     if points == 0:
-        return theta.detach().contiguous(), None, 0
+        return _op.dense(theta.detach()), None, 0
     if control_params is None or control_params.numel() != theta.shape[0] * points * points:
         raise ValueError(f"{what}: control_params must hold {theta.shape[0]} x {points * points} weights, got "
                          f"{None if control_params is None else tuple(control_params.shape)}")
     _op.need_gpu(control_params, _MODULE, what)
     if control_params.device != theta.device:
         raise RuntimeError(f"{what}: theta and control_params are on different devices")
-    return theta.detach().contiguous(), control_params.detach().reshape(theta.shape[0], points * points).contiguous(), points
+    return _op.dense(theta.detach()), _op.dense(control_params.detach().reshape(theta.shape[0], points * points)), points
 
 
 def tps_warp_frame(frame: torch.Tensor, theta: torch.Tensor, control_params: Optional[torch.Tensor], points: int) -> torch.Tensor:
@@ -54,7 +54,7 @@ def tps_warp_frame(frame: torch.Tensor, theta: torch.Tensor, control_params: Opt
         raise ValueError(f"tps_warp_frame: the frame batch {frame.shape[0]} is not the transform's {theta.shape[0]}")
     if theta.device != frame.device:
         raise RuntimeError("tps_warp_frame: frame and theta are on different devices")
-    frame = frame.detach().contiguous()
+    frame = _op.dense(frame.detach())
     b, c, h, w = frame.shape
     out = torch.empty_like(frame)
     _op.call("tps_warp_frame", frame.device, frame, theta, params, points, b, c, h, w, out, family=_FAMILY)
@@ -82,8 +82,8 @@ class _TpsWarpPointsFunction(torch.autograd.Function):
             return (None,) * 5
         coords, theta, params = ctx.saved_tensors
         bc, n, _ = coords.shape
-        grad_out = None if grad_out is None else grad_out.contiguous()
-        grad_jac = None if grad_jac is None else grad_jac.contiguous()
+        grad_out = None if grad_out is None else _op.dense(grad_out)
+        grad_jac = None if grad_jac is None else _op.dense(grad_jac)
         grad = torch.empty_like(coords)
         _op.call("tps_warp_points_backward", coords.device, coords, bc, theta, params, ctx.points, theta.shape[0], n, grad_out, grad_jac,
                  grad, family=_FAMILY)
@@ -103,4 +103,4 @@ def tps_warp_points(coords: torch.Tensor, theta: torch.Tensor, control_params: O
         raise ValueError(f"tps_warp_points: the coordinate batch {coords.shape[0]} is neither 1 nor the transform's {theta.shape[0]}")
     if theta.device != coords.device:
         raise RuntimeError("tps_warp_points: coordinates and theta are on different devices")
-    return _TpsWarpPointsFunction.apply(coords.contiguous(), theta, params, points, bool(want_jacobian))
+    return _TpsWarpPointsFunction.apply(_op.dense(coords), theta, params, points, bool(want_jacobian))

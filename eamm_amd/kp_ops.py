@@ -43,7 +43,7 @@ class _KpHeadFunction(torch.autograd.Function):
         k, njm, pad, temperature = ctx.cfg
         b, h, w, cs = logits.shape
         dev = logits.device
-        cont = lambda t: None if t is None else t.contiguous()
+        cont = lambda t: None if t is None else _op.dense(t)
         g_value, g_jac, g_heat = cont(g_value), cont(g_jac), cont(g_heat)
         grad = torch.empty_like(logits)
         ws = _op.workspace("kp_head", dev, b, k)
@@ -70,7 +70,7 @@ def kp_head(logits_nhwc: torch.Tensor, K: int, njm: int, pad: int, temperature: 
     if not temperature > 0:
         raise ValueError(f"kp_head: temperature must be positive, got {temperature}")
     _op.need_gpu(logits_nhwc, "autograd_ops", "kp_head")   # (the module name this message has always carried)
-    value, jac, heat = _KpHeadFunction.apply(logits_nhwc.contiguous(), K, njm, pad, float(temperature), bool(want_heatmap))
+    value, jac, heat = _KpHeadFunction.apply(_op.dense(logits_nhwc), K, njm, pad, float(temperature), bool(want_heatmap))
     out = {"value": value}
     if heat is not None:
         out["heatmap"] = heat

@@ -37,7 +37,7 @@ class _AntiAliasDownFunction(torch.autograd.Function):
             return None, None, None
         (weight,) = ctx.saved_tensors
         b, hh, ww = ctx.shape
-        grad_small = grad_small.contiguous()
+        grad_small = _op.dense(grad_small)
         grad = torch.empty(b, 3, hh, ww, dtype=torch.float32, device=grad_small.device)
         _op.call("antialias_down_backward", grad.device, grad_small, weight, b, hh, ww, ctx.inv_scale, grad)
         return grad, None, None
@@ -46,14 +46,14 @@ class _AntiAliasDownFunction(torch.autograd.Function):
 def antialias_down(source: torch.Tensor, weight: Optional[torch.Tensor], scale_factor: float) -> torch.Tensor:
     """AntiAliasInterpolation2d (reference modules/util.py:1005-1052) on an RGB batch -> NHWC [B,h,w,4]; ``scale_factor`` 0.25 (the
     13x13 Gaussian of every shipped configuration) or 1 (util.py:1047-1048 returns the input)."""
-    _op.need_gpu(source, _MODULE, "antialias_down")
+    _op.operands(_MODULE, "antialias_down", source, weight)
     inv = int(round(1.0 / scale_factor))
     if source.dim() != 4 or source.shape[1] != 3 or inv not in (1, 4) or source.shape[2] % inv or source.shape[3] % inv:
         raise ValueError(f"antialias_down: RGB NCHW input with sides multiples of 1/scale_factor, scale_factor 0.25 or 1; got "
                          f"{tuple(source.shape)}, {scale_factor}")
     if inv == 4 and (weight is None or tuple(weight.shape) != (3, 1, 13, 13)):
         raise ValueError("antialias_down: the module's [3,1,13,13] Gaussian buffer is required")
-    return _AntiAliasDownFunction.apply(source.contiguous(), None if weight is None else weight.contiguous(), inv)
+    return _AntiAliasDownFunction.apply(_op.dense(source), None if weight is None else _op.dense(weight), inv)
 
 
 _SINGULAR = "kp_records: a driving jacobian is singular (torch.inverse would raise, dense_motion.py:56)"
@@ -85,7 +85,7 @@ class _KpRecordsFunction(torch.autograd.Function):
         if ctx.flag is not None and not torch.cuda.is_current_stream_capturing() and int(ctx.flag.item()):
             raise RuntimeError(_SINGULAR)
         n, k = grad_rec.shape[:2]
-        grad_rec = grad_rec.contiguous()
+        grad_rec = _op.dense(grad_rec)
         need = ctx.needs_input_grad
         dev = grad_rec.device
         new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
@@ -102,12 +102,12 @@ class _KpRecordsFunction(torch.autograd.Function):
 def kp_records(kp_driving: dict, kp_source: dict) -> torch.Tensor:
     """dense_motion.py:47-67: the per key point affine map T_k(z) = J_k (z - kp_driving_k) + kp_source_k as records [n,K,8]."""
     kd_val, ks_val = kp_driving["value"], kp_source["value"]
-    _op.need_gpu(kd_val, _MODULE, "kp_records")
     kd_jac = kp_driving.get("jacobian") if "jacobian" in kp_driving else None
     ks_jac = kp_source.get("jacobian") if kd_jac is not None else None
+    _op.operands(_MODULE, "kp_records", kd_val, kd_jac, ks_val, ks_jac)
     if kd_val.shape != ks_val.shape or kd_val.dim() != 3 or kd_val.shape[2] != 2:
         raise ValueError(f"kp_records: key-point values must both be [n,K,2], got {tuple(kd_val.shape)} / {tuple(ks_val.shape)}")
-    cont = lambda t: None if t is None else t.contiguous()
+    cont = lambda t: None if t is None else _op.dense(t)
     return _KpRecordsFunction.apply(cont(kd_val), cont(kd_jac), cont(ks_val), cont(ks_jac))
 
 
@@ -134,8 +134,8 @@ class _MotionFrontFunction(torch.autograd.Function):
         dev = rec.device
         if grad_hg is None and grad_sd is None:
             return None, None, None, None
-        grad_hg = None if grad_hg is None else grad_hg.contiguous()
-        grad_sd = None if grad_sd is None else grad_sd.contiguous()
+        grad_hg = None if grad_hg is None else _op.dense(grad_hg)
+        grad_sd = None if grad_sd is None else _op.dense(grad_sd)
         g_rec = torch.empty_like(rec)
         g_small = torch.empty_like(small) if ctx.needs_input_grad[1] else None
         ws = _op.workspace("motion", dev, n, k, h, w)
@@ -146,11 +146,11 @@ class _MotionFrontFunction(torch.autograd.Function):
 def motion_front(records: torch.Tensor, small: torch.Tensor, kp_variance: float, cpad: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """dense_motion.py:32-45, 47-79, 93-94: heat-maps, sparse motions and the K+1 warps of the down-sampled source, laid out as the
     hourglass input (channel 4k = heat-map k, 4k+1..3 = RGB warped by motion k; zero padded to ``cpad``) + ``sparse_deformed``."""
-    _op.need_gpu(records, _MODULE, "motion_front")
+    _op.operands(_MODULE, "motion_front", records, small)
     n, k = records.shape[:2]
     if tuple(small.shape[:1]) != (n,) or small.dim() != 4 or small.shape[3] != 4 or cpad < 4 * (k + 1) or cpad % 4:
         raise ValueError(f"motion_front: records {tuple(records.shape)} / small {tuple(small.shape)} / cpad {cpad} mismatch")
-    return _MotionFrontFunction.apply(records.contiguous(), small.contiguous(), kp_variance, int(cpad))
+    return _MotionFrontFunction.apply(_op.dense(records), _op.dense(small), kp_variance, int(cpad))
 
 
 class _MotionHeadFunction(torch.autograd.Function):
@@ -179,7 +179,7 @@ class _MotionHeadFunction(torch.autograd.Function):
         n, k1, h, w = mask.shape
         k = k1 - 1
         dev = mask.device
-        cont = lambda t: None if t is None else t.contiguous()
+        cont = lambda t: None if t is None else _op.dense(t)
         g_mask, g_defo, g_occ = cont(g_mask), cont(g_defo), cont(g_occ)
         g_lm = torch.empty(n, h, w, ctx.ld, dtype=torch.float32, device=dev)
         g_lo = torch.empty(n, h, w, ctx.ldo, dtype=torch.float32, device=dev) if (occ is not None and not ctx.stacked) else None
@@ -195,7 +195,7 @@ def motion_head(mask_logits: torch.Tensor, occlusion_logits: Optional[torch.Tens
     """dense_motion.py:98-111 on the two 7x7 convolutions' NHWC outputs (channels 0..K of ``mask_logits``, channel 0 of
     ``occlusion_logits``): mask [n,K+1,h,w], deformation [n,h,w,2], occlusion [n,h,w] or None.  ``stacked``: ONE convolution with
     the two filters stacked produced both -- the occlusion logit is channel K + 1 of ``mask_logits``, ``occlusion_logits`` is None."""
-    _op.need_gpu(mask_logits, _MODULE, "motion_head")
+    _op.operands(_MODULE, "motion_head", mask_logits, occlusion_logits, records)
     n, k = records.shape[:2]
     if mask_logits.dim() != 4 or mask_logits.shape[0] != n or mask_logits.shape[3] < k + 1 + int(stacked):
         raise ValueError(f"motion_head: mask logits {tuple(mask_logits.shape)} do not hold {k + 1} motions of {n} frames")
@@ -203,5 +203,5 @@ def motion_head(mask_logits: torch.Tensor, occlusion_logits: Optional[torch.Tens
         raise ValueError("motion_head: stacked logits carry the occlusion logit in channel K + 1; pass occlusion_logits=None")
     if occlusion_logits is not None and tuple(occlusion_logits.shape[:3]) != tuple(mask_logits.shape[:3]):
         raise ValueError("motion_head: occlusion logits and mask logits differ in shape")
-    return _MotionHeadFunction.apply(mask_logits.contiguous(), None if occlusion_logits is None else occlusion_logits.contiguous(),
-                                     records.contiguous(), stacked)
+    return _MotionHeadFunction.apply(_op.dense(mask_logits), None if occlusion_logits is None else _op.dense(occlusion_logits),
+                                     _op.dense(records), stacked)

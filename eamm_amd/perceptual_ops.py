@@ -81,7 +81,7 @@ class _PyramidFunction(torch.autograd.Function):
         for inv, g in zip(ctx.invs, grads):
             if g is None:
                 continue
-            g = g.contiguous()
+            g = _op.dense(g)
             grad = torch.empty(b, 3, hh, ww, dtype=torch.float32, device=g.device)
             if ctx.normalised:
                 _op.call("vgg_input_backward", g.device, g, g.shape[3], None, weight, std, b, hh, ww, inv, grad)
@@ -96,25 +96,21 @@ def vgg_input(image: torch.Tensor, weight: Optional[torch.Tensor], mean: torch.T
     """Per entry of ``inv_scales`` the pyramid level of ``image`` (NCHW [B,3,H,W]; AntiAliasInterpolation2d of the reference's
     modules/util.py:1005-1052 with ``weight`` its [3,1,13,13] buffer; 1: the image itself) normalised as modules/model.py:43 does,
     as NHWC [B,H/inv,W/inv,32] with exact zeros in channels 3..31.  ``mean`` / ``std``: three values each.  Differentiable in ``image``."""
-    _op.need_gpu(image, _MODULE, "vgg_input")
+    _op.operands(_MODULE, "vgg_input", image, weight, mean, std)
     invs = tuple(int(i) if int(i) == i else i for i in inv_scales)
     _check_levels(image, weight, invs, "vgg_input")
     if mean.numel() != 3 or std.numel() != 3:
         raise ValueError(f"vgg_input: mean / std must hold three values, got {tuple(mean.shape)} / {tuple(std.shape)}")
-    if mean.device != image.device or std.device != image.device or (weight is not None and weight.device != image.device):
-        raise RuntimeError("vgg_input: buffers and image are on different devices")
-    return _PyramidFunction.apply(image.contiguous(), None if weight is None else weight.detach().contiguous(),
-                                  mean.detach().reshape(3).contiguous(), std.detach().reshape(3).contiguous(), invs, True)
+    return _PyramidFunction.apply(_op.dense(image), None if weight is None else _op.dense(weight.detach()),
+                                  _op.dense(mean.detach().reshape(3)), _op.dense(std.detach().reshape(3)), invs, True)
 
 
 def pyramid_levels(image: torch.Tensor, weight: torch.Tensor, inv_scales: Sequence[int]) -> Tuple[torch.Tensor, ...]:
     """The un-normalised pyramid levels NCHW [B,3,H/inv,W/inv] of ``image`` -- bit for bit what ``vgg_input`` normalises."""
-    _op.need_gpu(image, _MODULE, "pyramid_levels")
+    _op.operands(_MODULE, "pyramid_levels", image, weight)
     invs = tuple(int(i) if int(i) == i else i for i in inv_scales)
     _check_levels(image, weight, invs, "pyramid_levels")
-    if weight is not None and weight.device != image.device:
-        raise RuntimeError("pyramid_levels: buffer and image are on different devices")
-    return _PyramidFunction.apply(image.contiguous(), None if weight is None else weight.detach().contiguous(), None, None, invs, False)
+    return _PyramidFunction.apply(_op.dense(image), None if weight is None else _op.dense(weight.detach()), None, None, invs, False)
 
 
 class _ReluPoolFunction(torch.autograd.Function):
@@ -124,9 +120,12 @@ class _ReluPoolFunction(torch.autograd.Function):
     def forward(ctx, x, pool):
         b, h, w, c = x.shape
         pooled = torch.empty(b, h // 2, w // 2, c, dtype=torch.float32, device=x.device) if pool else None
-        _op.call("relu_pool", x.device, x, b, h, w, c, pooled)
+        y = _op.dense(x)          # x itself, unless it starts off a 16-byte boundary: then the kernel runs on a copy ...
+        _op.call("relu_pool", x.device, y, b, h, w, c, pooled)
+        if y is not x:
+            x.copy_(y)            # ... and x still ends up holding relu(x)
         ctx.mark_dirty(x)
-        ctx.save_for_backward(x)
+        ctx.save_for_backward(y)
         ctx.set_materialize_grads(False)
         return x, pooled
 
@@ -136,8 +135,8 @@ class _ReluPoolFunction(torch.autograd.Function):
             return None, None
         (y,) = ctx.saved_tensors
         b, h, w, c = y.shape
-        dy = None if dy is None else dy.contiguous()
-        dp = None if dp is None else dp.contiguous()
+        dy = None if dy is None else _op.dense(dy)
+        dp = None if dp is None else _op.dense(dp)
         dx = torch.empty_like(y)
         _op.call("relu_pool_backward", y.device, y, dy, dp, b, h, w, c, dx)
         return dx, None
@@ -176,7 +175,7 @@ class _L1PairFunction(torch.autograd.Function):
         ga = gb = None
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
             ga = torch.empty_like(g)
-            _op.call("l1_pair_backward", g.device, g, g.numel(), grad_value.contiguous(), ga)
+            _op.call("l1_pair_backward", g.device, g, g.numel(), _op.dense(grad_value), ga)
             if ctx.needs_input_grad[1]:
                 gb = -ga
             if not ctx.needs_input_grad[0]:
@@ -188,15 +187,12 @@ def l1_pair(a: torch.Tensor, b: torch.Tensor, weight: float = 1.0) -> torch.Tens
     """``weight * (a - b).abs().mean()`` as a scalar tensor, summed in a fixed order (the same bits on every run); the gradient
     ``(weight / N) * sign(a - b)`` (``sign(0) = 0``, ``torch.abs``'s own subgradient) is written in the same pass.  ``a`` and ``b``:
     equal shapes; NCHW views of NHWC tensors (what ``Vgg19`` returns) are read where they lie."""
-    _op.need_gpu(a, _MODULE, "l1_pair")
-    _op.need_gpu(b, _MODULE, "l1_pair")
+    _op.operands(_MODULE, "l1_pair", a, b)
     if a.shape != b.shape or a.numel() < 1:
         raise ValueError(f"l1_pair: a and b must have one non-empty shape, got {tuple(a.shape)} / {tuple(b.shape)}")
-    if a.device != b.device:
-        raise RuntimeError("l1_pair: a and b are on different devices")
     if a.dim() == 4 and not a.is_contiguous() and a.permute(0, 2, 3, 1).is_contiguous() and b.permute(0, 2, 3, 1).is_contiguous():
         a, b = a.permute(0, 2, 3, 1), b.permute(0, 2, 3, 1)
-    return _L1PairFunction.apply(a.contiguous(), b.contiguous(), float(weight))
+    return _L1PairFunction.apply(_op.dense(a), _op.dense(b), float(weight))
 
 
 class _FrozenConvFunction(torch.autograd.Function):
@@ -212,22 +208,20 @@ class _FrozenConvFunction(torch.autograd.Function):
         if not ctx.needs_input_grad[0]:
             return None, None, None
         (weight,) = ctx.saved_tensors
-        return _Conv2dSameFunction._conv(grad_out.contiguous(), weight, None, transposed=True), None, None
+        return _Conv2dSameFunction._conv(_op.dense(grad_out), weight, None, transposed=True), None, None
 
 
 def frozen_conv3x3(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
     """``F.conv2d(x, weight, bias, padding=1)`` on NHWC x [B,H,W,Cin] -> [B,H,W,Cout] with a FROZEN 3x3 filter (channels multiples
     of 32): differentiable in ``x`` only -- a parameter that requires a gradient is refused."""
-    _op.need_gpu(x, _MODULE, "frozen_conv3x3")
+    _op.operands(_MODULE, "frozen_conv3x3", x, weight, bias)
     if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or x.dim() != 4 or x.shape[3] != weight.shape[1] or \
             weight.shape[1] % CHANNEL_GRANULE or weight.shape[0] % CHANNEL_GRANULE:
         raise ValueError(f"frozen_conv3x3: weight {tuple(weight.shape)} / input {tuple(x.shape)} unsupported "
                          f"(3x3, channels multiples of {CHANNEL_GRANULE})")
     if weight.requires_grad or (bias is not None and bias.requires_grad):
         raise ValueError("frozen_conv3x3: weight and bias must not require a gradient (the weight gradient of VGG is out of scope)")
-    if weight.device != x.device or (bias is not None and bias.device != x.device):
-        raise RuntimeError("frozen_conv3x3: parameters and input are on different devices")
-    return _FrozenConvFunction.apply(x.contiguous(), weight, bias)
+    return _FrozenConvFunction.apply(_op.dense(x), weight, bias)
 
 
 class _VggStemFunction(torch.autograd.Function):
@@ -259,7 +253,7 @@ class _VggStemFunction(torch.autograd.Function):
         for inv, g in zip(ctx.invs, grads):
             if g is None:
                 continue
-            g4 = _Conv2dSameFunction._conv(g.contiguous(), w4, None, transposed=True)      # [B,h,w,4]: channels 0..2 + a zero
+            g4 = _Conv2dSameFunction._conv(_op.dense(g), w4, None, transposed=True)      # [B,h,w,4]: channels 0..2 + a zero
             grad = torch.empty(b, 3, hh, ww, dtype=torch.float32, device=g.device)
             _op.call("vgg_input_backward", g.device, g4, 4, None, aa_weight, std, b, hh, ww, inv, grad)
             total = grad if total is None else total.add_(grad)
@@ -271,7 +265,7 @@ def vgg_stem(image: torch.Tensor, weight: Optional[torch.Tensor], mean: torch.Te
     """``frozen_conv3x3(vgg_input(image, ...)[k], conv_weight, conv_bias)`` per entry of ``inv_scales`` as ONE node: ``conv_weight``
     is conv1_1's filter [Cout,3,3,3] padded with zeros to [Cout,32,3,3]; the image gradient goes through its first four input
     channels only.  Same values as the composition, at 1/8 of its data-gradient arithmetic."""
-    _op.need_gpu(image, _MODULE, "vgg_stem")
+    _op.operands(_MODULE, "vgg_stem", image, weight, mean, std, conv_weight, conv_bias)
     invs = tuple(int(i) if int(i) == i else i for i in inv_scales)
     _check_levels(image, weight, invs, "vgg_stem")
     if mean.numel() != 3 or std.numel() != 3:
@@ -282,8 +276,6 @@ def vgg_stem(image: torch.Tensor, weight: Optional[torch.Tensor], mean: torch.Te
                          f"{tuple(conv_weight.shape)}")
     if conv_weight.requires_grad or conv_bias.requires_grad:
         raise ValueError("vgg_stem: conv_weight and conv_bias must not require a gradient (the weight gradient of VGG is out of scope)")
-    if any(t is not None and t.device != image.device for t in (weight, mean, std, conv_weight, conv_bias)):
-        raise RuntimeError("vgg_stem: parameters and image are on different devices")
-    return _VggStemFunction.apply(image.contiguous(), None if weight is None else weight.detach().contiguous(),
-                                  mean.detach().reshape(3).contiguous(), std.detach().reshape(3).contiguous(),
-                                  conv_weight.contiguous(), conv_bias.contiguous(), invs)
+    return _VggStemFunction.apply(_op.dense(image), None if weight is None else _op.dense(weight.detach()),
+                                  _op.dense(mean.detach().reshape(3)), _op.dense(std.detach().reshape(3)),
+                                  _op.dense(conv_weight), _op.dense(conv_bias), invs)

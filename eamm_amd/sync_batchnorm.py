@@ -26,8 +26,8 @@ import torch
 import torch.distributed as dist
 from torch.nn.modules.batchnorm import _BatchNorm
 
-from . import _lib
-from ._handle import ptr, stream_ptr
+from . import _handle, _lib, _op
+from ._handle import ptr, stream_ptr   # noqa: F401  (importable from here, as before)
 
 BN_SYNC, BN_SINGLE, BN_EVAL = 0, 1, 2
 
@@ -38,6 +38,16 @@ def _check(code: int):
         raise _lib.EammError(code, msg.decode() if msg else "?")
 
 
+def _bn(name: str, dev: torch.device, *args):
+    """``eamm_bn_<name>(*args, stream)`` on ``dev`` and its current stream: tensors (and None) among ``args`` are passed by address
+    through ``_handle.ptr``, like ``_op.call``'s (these entries take no device index and report through eamm_bn_last_error)."""
+    entry = "eamm_bn_" + name
+    to_address = _handle.ptr
+    argv = [to_address(a, entry, i) if a is None or isinstance(a, torch.Tensor) else a for i, a in enumerate(args)]
+    with torch.cuda.device(dev):
+        _check(getattr(_lib.lib(), entry)(*argv, stream_ptr(dev)))
+
+
 class HipBatchNormOps:
     """The three device steps of the forward (C ABI: eamm_bn_local_sums / eamm_bn_finalize / eamm_bn_apply)."""
 
@@ -45,18 +55,25 @@ class HipBatchNormOps:
         if input.device.type != "cuda":
             raise RuntimeError("eamm_amd.SynchronizedBatchNorm2d runs only on a ROCm GPU (there is no CPU fallback)")
         if input.dtype != torch.float32:
-            raise RuntimeError(f"input must be float32, got {input.dtype}")
+            raise RuntimeError(f"SynchronizedBatchNorm2d: input must be float32, got {input.dtype}")
         if mod.running_mean is None or mod.running_mean.device != input.device:
-            raise RuntimeError("module buffers and input are on different devices (move the module with .cuda())")
+            raise RuntimeError("SynchronizedBatchNorm2d: module buffers and input are on different devices (move the module with .cuda())")
+        for name in ("weight", "bias", "running_mean", "running_var"):
+            t = getattr(mod, name)
+            if t is not None and (t.dtype != torch.float32 or t.device != input.device):
+                raise RuntimeError(f"SynchronizedBatchNorm2d: {name} must be float32 on the input's device {input.device}, got "
+                                   f"{t.dtype} on {t.device}")
+        for name in ("running_mean", "running_var"):      # written in place: these cannot be replaced by a copy
+            t = getattr(mod, name)
+            if not t.is_contiguous() or t.data_ptr() % _op.ALIGN:
+                raise RuntimeError(f"SynchronizedBatchNorm2d: {name} must be contiguous and start on a {_op.ALIGN}-byte boundary")
 
     def local_sums(self, x: torch.Tensor) -> torch.Tensor:
         n, c = x.shape[0], x.shape[1]
         hw = x.numel() // (n * c)
-        L = _lib.lib()
         sums = torch.empty(6 * c + 2, dtype=torch.float32, device=x.device)   # [2C+2] exchanged floats + 2C doubles
-        work = torch.empty(max(1, L.eamm_bn_workspace_floats(n, c, hw)), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            _check(L.eamm_bn_local_sums(ptr(x), n, c, hw, ptr(sums), ptr(work), stream_ptr()))
+        work = torch.empty(max(1, _lib.lib().eamm_bn_workspace_floats(n, c, hw)), dtype=torch.float32, device=x.device)
+        _bn("local_sums", x.device, x, n, c, hw, sums, work)
         return sums
 
     def finalize(self, sums: Optional[torch.Tensor], mod: "SynchronizedBatchNorm2d", mode: int):
@@ -64,20 +81,17 @@ class HipBatchNormOps:
         mean = torch.empty(c, dtype=torch.float32, device=dev)
         scale = torch.empty(c, dtype=torch.float32, device=dev)
         inv_std = torch.empty(c, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _check(_lib.lib().eamm_bn_finalize(ptr(sums), c, float(mod.eps), float(mod.momentum), mode, ptr(mod.weight),
-                                               ptr(mod.running_mean), ptr(mod.running_var), ptr(mean), ptr(scale), ptr(inv_std), stream_ptr()))
+        _bn("finalize", dev, sums, c, float(mod.eps), float(mod.momentum), mode, _op.dense(mod.weight), mod.running_mean, mod.running_var,
+            mean, scale, inv_std)
         return mean, scale, inv_std
 
     # ---- backward: eamm_bn_backward_sums / _finalize / _apply ------------------------------------------------------
     def backward_sums(self, x: torch.Tensor, dy: torch.Tensor, mean: torch.Tensor) -> torch.Tensor:
         n, c = x.shape[0], x.shape[1]
         hw = x.numel() // (n * c)
-        L = _lib.lib()
         sums = torch.empty(6 * c + 2, dtype=torch.float32, device=x.device)
-        work = torch.empty(max(1, L.eamm_bn_workspace_floats(n, c, hw)), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            _check(L.eamm_bn_backward_sums(ptr(x), ptr(dy), ptr(mean), n, c, hw, ptr(sums), ptr(work), stream_ptr()))
+        work = torch.empty(max(1, _lib.lib().eamm_bn_workspace_floats(n, c, hw)), dtype=torch.float32, device=x.device)
+        _bn("backward_sums", x.device, x, dy, mean, n, c, hw, sums, work)
         return sums
 
     def backward_finalize(self, local: torch.Tensor, reduced: torch.Tensor, inv_std: torch.Tensor, weight: Optional[torch.Tensor],
@@ -86,25 +100,21 @@ class HipBatchNormOps:
         coef = torch.empty(3 * c, dtype=torch.float32, device=inv_std.device)
         dw = torch.empty(c, dtype=torch.float32, device=inv_std.device) if want_wb else None
         db = torch.empty(c, dtype=torch.float32, device=inv_std.device) if want_wb else None
-        with torch.cuda.device(inv_std.device):
-            _check(_lib.lib().eamm_bn_backward_finalize(ptr(local), ptr(reduced), c, ptr(inv_std), ptr(weight), float(eps), mode,
-                                                        ptr(dw), ptr(db), ptr(coef), stream_ptr()))
+        _bn("backward_finalize", inv_std.device, local, reduced, c, inv_std, _op.dense(weight), float(eps), mode, dw, db, coef)
         return coef, dw, db
 
     def backward_apply(self, x: torch.Tensor, dy: torch.Tensor, mean: torch.Tensor, coef: torch.Tensor) -> torch.Tensor:
         n, c = x.shape[0], x.shape[1]
         hw = x.numel() // (n * c)
         dx = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            _check(_lib.lib().eamm_bn_backward_apply(ptr(x), ptr(dy), ptr(mean), ptr(coef), n, c, hw, ptr(dx), stream_ptr()))
+        _bn("backward_apply", x.device, x, dy, mean, coef, n, c, hw, dx)
         return dx
 
     def apply(self, x: torch.Tensor, mean: torch.Tensor, scale: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
         n, c = x.shape[0], x.shape[1]
         hw = x.numel() // (n * c)
         y = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            _check(_lib.lib().eamm_bn_apply(ptr(x), ptr(mean), ptr(scale), ptr(bias), n, c, hw, ptr(y), stream_ptr()))
+        _bn("apply", x.device, x, mean, scale, _op.dense(bias), n, c, hw, y)
         return y
 
 
@@ -141,7 +151,7 @@ class _BatchNormFunction(torch.autograd.Function):
     def backward(ctx, dy):
         x, mean, inv_std, weight = ctx.saved_tensors
         mod, ops = ctx.mod, ctx.mod._ops
-        dy = dy.contiguous()
+        dy = _op.dense(dy)
         local = ops.backward_sums(x, dy, mean)
         reduced = local
         if ctx.reduce:
@@ -161,28 +171,25 @@ class _BatchNormNHWCFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, mod, relu, pool):
-        L = _lib.lib()
+        x = _op.dense(x)
         b, h, w, c = x.shape
         m = b * h * w
         dev = x.device
-        st = stream_ptr(dev)
         world = mod._replicas()
         parallel = world > 1 if mod.sync is None else bool(mod.sync)
         sums = torch.empty(6 * c + 2, dtype=torch.float32, device=dev)
-        work = torch.empty(max(1, L.eamm_bn_nhwc_workspace_floats(m, c)), dtype=torch.float32, device=dev)
+        work = torch.empty(max(1, _lib.lib().eamm_bn_nhwc_workspace_floats(m, c)), dtype=torch.float32, device=dev)
         mode = BN_SYNC if parallel else BN_SINGLE
-        with torch.cuda.device(dev):
-            if world > 1 and parallel:
-                _check(L.eamm_bn_nhwc_local_sums(ptr(x), m, c, ptr(sums), ptr(work), st))
-                mod._all_reduce(sums[:2 * c + 2])
-                mean, scale, inv_std = mod._ops.finalize(sums, mod, mode)
-            else:   # one replica: nothing to exchange -- the finalize step runs inside the kernel that adds the slices up
-                mean, scale, inv_std = (torch.empty(c, dtype=torch.float32, device=dev) for _ in range(3))
-                _check(L.eamm_bn_nhwc_local_stats(ptr(x), m, c, float(mod.eps), float(mod.momentum), mode, ptr(mod.weight),
-                                                  ptr(mod.running_mean), ptr(mod.running_var), ptr(sums), ptr(mean), ptr(scale),
-                                                  ptr(inv_std), ptr(work), st))
-            y = torch.empty((b, h // 2, w // 2, c) if pool else (b, h, w, c), dtype=torch.float32, device=dev)
-            _check(L.eamm_bn_nhwc_apply(ptr(x), ptr(mean), ptr(scale), ptr(bias), b, h, w, c, int(relu), int(pool), ptr(y), st))
+        if world > 1 and parallel:
+            _bn("nhwc_local_sums", dev, x, m, c, sums, work)
+            mod._all_reduce(sums[:2 * c + 2])
+            mean, scale, inv_std = mod._ops.finalize(sums, mod, mode)
+        else:   # one replica: nothing to exchange -- the finalize step runs inside the kernel that adds the slices up
+            mean, scale, inv_std = (torch.empty(c, dtype=torch.float32, device=dev) for _ in range(3))
+            _bn("nhwc_local_stats", dev, x, m, c, float(mod.eps), float(mod.momentum), mode, _op.dense(mod.weight), mod.running_mean,
+                mod.running_var, sums, mean, scale, inv_std, work)
+        y = torch.empty((b, h // 2, w // 2, c) if pool else (b, h, w, c), dtype=torch.float32, device=dev)
+        _bn("nhwc_apply", dev, x, mean, scale, _op.dense(bias), b, h, w, c, int(relu), int(pool), y)
         ctx.mod, ctx.mode, ctx.relu, ctx.pool = mod, mode, bool(relu), bool(pool)
         ctx.reduce = mode == BN_SYNC and world > 1
         ctx.save_for_backward(x, mean, scale, inv_std, weight, bias)
@@ -192,33 +199,28 @@ class _BatchNormNHWCFunction(torch.autograd.Function):
     def backward(ctx, dy):
         x, mean, scale, inv_std, weight, bias = ctx.saved_tensors
         mod = ctx.mod
-        L = _lib.lib()
         b, h, w, c = x.shape
         dev = x.device
-        dy = dy.contiguous()
-        st = stream_ptr(dev)
+        dy, weight, bias = _op.dense(dy), _op.dense(weight), _op.dense(bias)
+        relu, pool = int(ctx.relu), int(ctx.pool)
         local = torch.empty(6 * c + 2, dtype=torch.float32, device=dev)
-        work = torch.empty(max(1, L.eamm_bn_nhwc_workspace_floats(b * h * w, c)), dtype=torch.float32, device=dev)
+        work = torch.empty(max(1, _lib.lib().eamm_bn_nhwc_workspace_floats(b * h * w, c)), dtype=torch.float32, device=dev)
         want_wb = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
-        with torch.cuda.device(dev):
-            if ctx.reduce:
-                _check(L.eamm_bn_nhwc_backward_sums(ptr(x), ptr(dy), ptr(mean), ptr(scale), ptr(bias), b, h, w, c, int(ctx.relu),
-                                                    int(ctx.pool), ptr(local), ptr(work), st))
-                reduced = local.clone()
-                mod._all_reduce(reduced[:2 * c + 2])
-                coef, dw, db = mod._ops.backward_finalize(local, reduced, inv_std, weight, mod.eps, ctx.mode, want_wb)
-            else:   # one replica: sums and their finalize step in one call
-                coef = torch.empty(3 * c, dtype=torch.float32, device=dev)
-                dw = torch.empty(c, dtype=torch.float32, device=dev) if want_wb else None
-                db = torch.empty(c, dtype=torch.float32, device=dev) if want_wb else None
-                _check(L.eamm_bn_nhwc_backward_local(ptr(x), ptr(dy), ptr(mean), ptr(scale), ptr(bias), b, h, w, c, int(ctx.relu),
-                                                     int(ctx.pool), ptr(inv_std), ptr(weight), float(mod.eps), ctx.mode, ptr(local),
-                                                     ptr(dw), ptr(db), ptr(coef), ptr(work), st))
-            dx = None
-            if ctx.needs_input_grad[0]:
-                dx = torch.empty_like(x)
-                _check(L.eamm_bn_nhwc_backward_apply(ptr(x), ptr(dy), ptr(mean), ptr(scale), ptr(bias), ptr(coef), b, h, w, c,
-                                                     int(ctx.relu), int(ctx.pool), ptr(dx), st))
+        if ctx.reduce:
+            _bn("nhwc_backward_sums", dev, x, dy, mean, scale, bias, b, h, w, c, relu, pool, local, work)
+            reduced = local.clone()
+            mod._all_reduce(reduced[:2 * c + 2])
+            coef, dw, db = mod._ops.backward_finalize(local, reduced, inv_std, weight, mod.eps, ctx.mode, want_wb)
+        else:   # one replica: sums and their finalize step in one call
+            coef = torch.empty(3 * c, dtype=torch.float32, device=dev)
+            dw = torch.empty(c, dtype=torch.float32, device=dev) if want_wb else None
+            db = torch.empty(c, dtype=torch.float32, device=dev) if want_wb else None
+            _bn("nhwc_backward_local", dev, x, dy, mean, scale, bias, b, h, w, c, relu, pool, inv_std, weight, float(mod.eps), ctx.mode,
+                local, dw, db, coef, work)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(x)
+            _bn("nhwc_backward_apply", dev, x, dy, mean, scale, bias, coef, b, h, w, c, relu, pool, dx)
         return dx, (dw if ctx.needs_input_grad[1] else None), (db if ctx.needs_input_grad[2] else None), None, None, None
 
 
@@ -252,7 +254,7 @@ class SynchronizedBatchNorm2d(_BatchNorm):
         if input.shape[1] != self.num_features:
             raise RuntimeError(f"expected {self.num_features} channels, got {input.shape[1]}")
         self._check_device(input)
-        return _BatchNormFunction.apply(input.contiguous(), self.weight, self.bias, self)
+        return _BatchNormFunction.apply(_op.dense(input), self.weight, self.bias, self)
 
     def _check_device(self, input: torch.Tensor):
         self._ops.check(input, self)

@@ -21,6 +21,10 @@ test files that define such cases register them with ``case`` at import: ``CASES
 tests/test_gpu_guarded_ops.py imports every registering module and runs the whole registry; tests/test_guarded_host.py checks that
 every entry of ``OPERATOR_FAMILIES`` that takes a pointer is guarded or exempt.
 
+``Late(device, stream)`` is a third placer and ``run_late`` its driver: the same cases with inputs that exist in a side stream's
+order only, against the plain run's bits (tests/test_gpu_calling_streams.py) -- what an entry launches on another stream than the
+caller's shows there.  No guard bands in that run: the arena runs have looked for stray stores already.
+
 A new handle-less operator family joins by adding its prefix to ``OPERATOR_FAMILIES`` and registering its cases (a new module is
 added to the imports at the end of test_gpu_guarded_ops.py); tests/test_op_entries_host.py's all-zero refusal check then covers it too."""
 import torch
@@ -222,6 +226,191 @@ def case(cid, entries, fn=None, nan_ok=(), unstable=()):
             GUARDED.setdefault(e, []).append(cid)
         return f
     return register if fn is None else register(fn)
+
+
+# ---- the same cases in a side stream's order only ----------------------------------------------------------------------------------
+DELAY_MS = 100.0         # how long the side stream is held before a case's inputs are copied in: an order of magnitude above the host
+                         # work between a case's first placement and its first library call (placements, size queries, pinned copies)
+# cases whose first library call cannot be seen pending (at most 5), with the reason
+UNOBSERVED = {}
+_ticks_per_ms = {}
+
+
+def _non_blocking_stream(device):
+    """torch creates its streams non-blocking; that is confirmed through hipStreamGetFlags, and where it does not hold a
+    hipStreamNonBlocking stream of the runtime's is wrapped instead."""
+    import ctypes as C
+    hip = C.CDLL("libamdhip64.so")
+    non_blocking = 1                                     # hipStreamNonBlocking
+    st = torch.cuda.Stream(device=device)
+    flags = C.c_uint(0xFFFFFFFF)
+    rc = hip.hipStreamGetFlags(C.c_void_p(st.cuda_stream), C.byref(flags))
+    assert rc == 0, ("hipStreamGetFlags", rc)
+    if flags.value & non_blocking:
+        return st
+    raw = C.c_void_p()
+    with torch.cuda.device(device):
+        rc = hip.hipStreamCreateWithFlags(C.byref(raw), C.c_uint(non_blocking))
+    assert rc == 0, ("hipStreamCreateWithFlags", rc)
+    return torch.cuda.ExternalStream(raw.value, device=device)
+
+
+def _holds_up_the_default_stream(stream, hold_ms=20.0):
+    """Whether work on the default stream waits for earlier work on ``stream``.  A non-blocking stream never makes it wait by rule,
+    but the runtime multiplexes its streams onto a few hardware queues (four by default), and a stream that shares the null stream's
+    queue delays it all the same: a ``Late`` placer's NaN fills would then sit out the delay they are meant to precede."""
+    import time
+    default = torch.cuda.default_stream(stream.device)
+    probe = torch.zeros(1, device=stream.device)
+    torch.cuda.synchronize(stream.device)
+    _delay(stream, hold_ms)
+    begun = time.perf_counter()
+    with torch.cuda.stream(default):
+        probe.add_(1)
+    default.synchronize()
+    waited_ms = (time.perf_counter() - begun) * 1e3
+    stream.synchronize()
+    return waited_ms > hold_ms / 2
+
+
+_side_streams = {}
+
+
+def side_stream(device):
+    """THE side stream of ``device`` for these runs (one per process): non-blocking, so that it does not synchronise implicitly with
+    the null stream, and not sharing the null stream's hardware queue either."""
+    device = torch.device(device)
+    if device not in _side_streams:
+        for _ in range(16):
+            st = _non_blocking_stream(device)
+            if not _holds_up_the_default_stream(st):
+                _side_streams[device] = st
+                break
+        else:
+            raise AssertionError("no stream was found that leaves the default stream alone")
+    return _side_streams[device]
+
+
+def _delay(stream, ms=DELAY_MS):
+    """Hold ``stream`` for about ``ms`` with one ``torch.cuda._sleep``, its tick rate measured once per device."""
+    dev = stream.device
+    if dev not in _ticks_per_ms:
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        with torch.cuda.stream(stream):
+            torch.cuda._sleep(1000)                      # (the first launch loads the kernel)
+            a.record()
+            torch.cuda._sleep(2_000_000)
+            b.record()
+        b.synchronize()
+        _ticks_per_ms[dev] = 2_000_000 / max(a.elapsed_time(b), 1e-3)
+    with torch.cuda.stream(stream):
+        torch.cuda._sleep(int(ms * _ticks_per_ms[dev]))
+
+
+class Late(Plain):
+    """``Plain`` for a run in a side stream: every operand is allocated and NaN-filled on the default stream, which is then waited
+    for; on ``stream`` one delay is enqueued in front of the first operand, and the data of every "in" / "inout" operand is copied
+    there (from pinned memory, without waiting).  A case run under ``torch.cuda.stream(stream)`` thus sees its inputs in ``stream``'s
+    order only: work an entry put on another stream reads NaN, or is overwritten.  ``started`` is the event behind the delay."""
+
+    def __init__(self, device, stream):
+        super().__init__(device)
+        self.stream = stream
+        self.started = None
+        self.roles = []
+        self._pinned = []
+
+    def place(self, t_or_shape, role, dtype=torch.float32, skew=0, name=None):
+        assert role in ROLES, role
+        name = name or f"{role}{self.placed}"
+        self.placed += 1
+        data = None
+        if role in ("in", "inout"):
+            data = t_or_shape.detach().contiguous()      # host data, or what an earlier call of the case left on the device
+            dtype = data.dtype
+        default = torch.cuda.default_stream(self.device)
+        with torch.cuda.stream(default):
+            v = torch.empty(_shape_of(t_or_shape), dtype=dtype, device=self.device)
+            v.fill_(_fill_value(dtype))
+        default.synchronize()
+        v.record_stream(self.stream)
+        if self.started is None:
+            _delay(self.stream)
+            self.started = torch.cuda.Event()
+            self.started.record(self.stream)
+        if data is not None:
+            if data.device.type == "cpu":
+                data = data.pin_memory()
+                self._pinned.append(data)
+            with torch.cuda.stream(self.stream):
+                v.copy_(data, non_blocking=True)
+        self.roles.append((name, role, v))
+        if role in ("out", "inout"):
+            self.outs.append((name, v))
+        return v
+
+    __call__ = place
+
+
+class watching:
+    """While active, every entry of ``OPERATOR_FAMILIES`` that takes a pointer notes, immediately before the library is called,
+    its name and whether ``placer.started`` (the event behind a ``Late`` placer's delay) was still pending.  The note is taken on
+    the bound entry itself: every route to the library passes it -- ``_op.call`` and the BatchNorm calls behind ``_handle.ptr``, and
+    the cases that bind an entry themselves."""
+
+    def __init__(self, placer):
+        self.placer = placer
+        self.calls = []
+
+    def __enter__(self):
+        import ctypes as C
+        from eamm_amd import _lib
+        self.lib = _lib.lib()
+        self.saved = {}
+        for name, (_, args) in _lib.SIGNATURES.items():
+            if name.startswith(OPERATOR_FAMILIES) and any(a is C.c_void_p for a in args):
+                fn = getattr(self.lib, name)
+                self.saved[name] = fn
+                setattr(self.lib, name, self._noting(name, fn))
+        return self
+
+    def _noting(self, name, fn):
+        def entry(*args):
+            started = self.placer.started
+            self.calls.append((name, None if started is None else not started.query()))
+            return fn(*args)
+        return entry
+
+    def __exit__(self, *exc):
+        for name, fn in self.saved.items():
+            setattr(self.lib, name, fn)
+        return False
+
+
+def run_late(cid, device="cuda:0"):
+    """The case once on plain tensors and the default stream, once under ``torch.cuda.stream(side)`` with a ``Late`` placer: the same
+    bits in every output (``unstable`` ones excepted), no NaN in an output that may not keep one, and -- or the run proves nothing --
+    the delay still pending at the case's first library call that can read a placed operand."""
+    fn, nan_ok, unstable = CASES[cid]
+    plain = Plain(device)
+    fn(plain)
+    torch.cuda.synchronize()
+    side = side_stream(device)
+    late = Late(device, side)
+    with watching(late) as seen, torch.cuda.stream(side):
+        fn(late)
+    torch.cuda.synchronize()
+    if cid not in UNOBSERVED:
+        # A call in front of the first placement takes no placed operand: the case is still making an input there, with the public
+        # operator on tensors of its own (the motion cases' records, the augmentation cases' aligned video), as it does in an arena
+        # run.  The case's first call in the sense of this check is the first one that can read a placed operand.
+        placed = [(name, pending) for name, pending in seen.calls if pending is not None]
+        assert placed, (cid, "the case reached no operator entry after its first placement: nothing was observed")
+        assert placed[0][1], (cid, f"the delay was over at the first library call, {placed[0][0]}: the run proves nothing")
+    nan = [n for n, role, v in late.roles if role == "out" and n not in nan_ok and v.dtype.is_floating_point and bool(torch.isnan(v).any())]
+    assert not nan, (cid, "outputs hold NaN (unwritten, or computed before the inputs arrived)", nan)
+    differ = [n for n in same_outputs(plain, late) if n not in unstable]
+    assert not differ, (cid, "outputs of the side-stream run differ from the plain call", differ)
 
 
 def run_three(cid, device="cuda:0"):

@@ -482,7 +482,8 @@ def _motion_front_case(name, cpad, place):
     n, k, h, w = inp["n"], inp["k"], inp["h"], inp["w"]
     want, floor = ms._front_reference(name)
     kdd, ksd, rec_leaf = _records_on_device(inp)
-    rec, small = place(rec_leaf.detach(), "in", name="records"), place(ms._small_nhwc(inp), "in", name="small")
+    small_dev = ms._small_nhwc(inp)      # (sent to the device in front of the first placement: a side-stream run must not wait for it after)
+    rec, small = place(rec_leaf.detach(), "in", name="records"), place(small_dev, "in", name="small")
     hg, sdef = place((n, h, w, cpad), "out", name="hourglass input"), place((n, k + 1, 3, h, w), "out", name="sparse_deformed")
     _call("eamm_op_motion_front", rec, small, n, k, h, w, ms.VAR, cpad, hg, sdef)
     g_hg, g_sd = place(ms._hg_line(inp["g_hg"], cpad, 1), "in", name="grad hourglass input"), place(inp["g_sd"], "in", name="grad sparse_deformed")
