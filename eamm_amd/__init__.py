@@ -25,10 +25,13 @@ from .disc_ops import conv4_valid, norm_act_pool  # noqa: F401
 from .gan_loss import discriminator_gan_loss, generator_gan_loss  # noqa: F401
 from .equivariance import Transform, equivariance_loss  # noqa: F401
 from .equivariance_ops import tps_warp_frame, tps_warp_points  # noqa: F401
+from .optim import Adam  # noqa: F401
+from .optim_ops import adam_step  # noqa: F401
 from .config import kp_detector_config, kp_detector_a_config, tiny_kp_config, emotion_detector_config, emotion_augmentation_config  # noqa: F401
 
 __all__ = ["OcclusionAwareGenerator", "Engine", "EngineBackend", "animate_clip", "animate_from_features", "animate_from_audio", "mfcc", "mfcc_reference", "mfcc_windows", "prepare_pose", "read_wav", "EmotionVideo", "align_video", "crop_source", "crop_source_reference", "draw_augmentation", "emotion_video_reference", "perspective_params", "similarity_transform", "emotion_augmentation_config", "driving_keypoints", "shard_bounds", "normalize_kp", "apply_emotion_offsets", "smooth_keypoints", "one_euro_smooth", "KPDetector", "KPDetector_a", "EmotionDetector", "AudioFeatureNet", "DeconvTail", "SplitFeatureMap", "SynchronizedBatchNorm2d",
            "Vgg19", "ImagePyramide", "PerceptualLoss", "vgg_input", "pyramid_levels", "relu_pool", "l1_pair", "frozen_conv3x3",
            "Discriminator", "MultiScaleDiscriminator", "conv4_valid", "norm_act_pool", "generator_gan_loss", "discriminator_gan_loss",
            "Transform", "equivariance_loss", "tps_warp_frame", "tps_warp_points",
+           "Adam", "adam_step",
            "all_reduce_gradients", "hot_path_config", "tiny_config"]

@@ -299,6 +299,13 @@ SIGNATURES = {
                                             C.c_void_p, C.c_void_p]),
     "eamm_equi_tps_warp_points_backward": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # the optimiser step, a family of its own (optim_ops.py): Adam over a list of tensors; its arrays are HOST arrays; additive
+    "eamm_optim_adam": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong),
+                                  C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]),
+    "eamm_optim_adam_plan": (C.c_int, [C.c_int, C.POINTER(C.c_longlong), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                       C.POINTER(C.c_longlong)]),
+    "eamm_optim_adam_table_capacity": (C.c_int, []),
+    "eamm_optim_adam_block_elems": (C.c_int, []),
 }
 for _prefix, _config in FAMILIES.items():
     SIGNATURES.update({

@@ -465,6 +465,35 @@ hipError_t tps_warp_points_launch(const float* coords, int Bc, const float* thet
 hipError_t tps_warp_points_backward_launch(const float* coords, int Bc, const float* theta, const float* params, int P, int B, int N,
                                            const float* gout, const float* gjac, float* gcoords, hipStream_t s);
 
+// optim.hip: Adam over a LIST of tensors, a few launches for the whole list.  A launch carries its tensors BY VALUE in the kernel
+// arguments (AdamTable: no device-side table, nothing that depends on host memory staying alive); a workgroup owns one chunk of
+// `chunk` elements of one tensor and finds the tensor by a wave-uniform search over the table's prefix of workgroup counts.
+constexpr int ADAM_TABLE = 64;             // tensors per launch: 64 x 52 bytes + the scalars stay below the 4 KiB of kernel arguments
+constexpr int ADAM_BLOCK_ELEMS = 4096;     // E, the elements of a workgroup's chunk at multiplier 1: 256 threads x 4 float4
+constexpr int ADAM_GRID_CAP = 8192;        // a launch whose chunks at E would be more than this many gets larger ones ...
+constexpr int ADAM_MAX_MULT = 8;           // ... of up to 8 E elements
+constexpr long long ADAM_MAX_NUMEL = 1ll << 36;   // per tensor: a full table's workgroup count stays below 2^31
+struct AdamTable {
+    float* p[ADAM_TABLE];
+    const float* g[ADAM_TABLE];
+    float* m[ADAM_TABLE];
+    float* v[ADAM_TABLE];
+    long long n[ADAM_TABLE];
+    float step_size[ADAM_TABLE];           // lr / (1 - beta1^step), per tensor
+    float bc2_sqrt[ADAM_TABLE];            // sqrt(1 - beta2^step), per tensor
+    int first_block[ADAM_TABLE + 1];       // prefix of workgroup counts; entries beyond `count` repeat the total
+    int count;
+    int chunk;                             // elements per workgroup in this launch, a multiple of E
+};
+struct AdamLaunch {
+    int first, count, blocks, chunk;       // tensors [first, first + count) of the list, `blocks` workgroups of `chunk` elements
+};
+// How a list of n lengths (each 0 .. ADAM_MAX_NUMEL) is cut into launches, in list order: at most ADAM_TABLE tensors each, a length-0
+// tensor takes a table slot and no workgroup.  Writes at most `cap` launches; returns how many the list needs.
+int adam_plan(int n, const long long* numel, AdamLaunch* launches, int cap);
+hipError_t adam_launch(const AdamTable& table, float beta1, float one_minus_beta1, float beta2, float one_minus_beta2, float eps,
+                       float weight_decay, hipStream_t s);
+
 hipError_t one_euro_launch(const float* x, int T, int E, float mincutoff, float beta, float dcutoff, float freq, float scale,
                            float* out, hipStream_t stream, float* state = nullptr, int resume = 0);
 

@@ -1005,6 +1005,39 @@ int eamm_equi_tps_warp_points_backward(int device, const float* coords, int coor
                                        int points, int B, int N, const float* grad_out, const float* grad_jac, float* grad_coords,
                                        void* stream);
 
+/*
+ * The optimiser step (the reference's torch.optim.Adam, train.py), a family of its own: eamm_optim_* (optim.hip).  Adam over a LIST of
+ * fp32 tensors in as few launches as the list needs; per element, in torch's single-tensor order,
+ *       g' = g + weight_decay p            (only when weight_decay != 0: L2 as torch.optim.Adam, not AdamW)
+ *       m  = lerp(m, g', 1 - beta1)
+ *       v  = beta2 v + (1 - beta2) g' g'
+ *       p  = p - step_size m / (sqrt(v) / bc2_sqrt + eps)
+ * with step_size = lr / (1 - beta1^step) and bc2_sqrt = sqrt(1 - beta2^step) PER TENSOR, computed by the caller (torch computes them
+ * in Python floats) and handed over as fp32.
+ *   eamm_optim_adam   p, g, m, v: HOST arrays of n device addresses, numel / step_size / bc2_sqrt: host arrays of n values.  Tensor i is
+ *                     numel[i] contiguous floats at each of its four addresses; p, m and v are updated in place, g is only read.  The
+ *                     addresses need 4-byte alignment only: a tensor whose four addresses are all 16-byte aligned is accessed four
+ *                     floats at a time, any other one float at a time.  A tensor of length 0 is skipped (its addresses may be NULL).
+ *                     The host arrays are copied into the launches' kernel arguments before the entry returns; it allocates nothing,
+ *                     synchronises nothing and reads nothing back, and enqueues on `stream` only.  Refused by name: a NULL array, n < 0,
+ *                     numel[i] outside 0 .. 2^36, a NULL or not 4-byte-aligned address of a tensor with elements, hyper-parameters that
+ *                     are not finite, betas outside [0, 1), negative eps / weight_decay, bc2_sqrt[i] <= 0.  No two tensors may overlap.
+ *   eamm_optim_adam_plan   HOST ONLY (touches no device): how eamm_optim_adam cuts a list of n lengths into launches, in list order.
+ *                     Returns the number of launches (negative: an error) and fills, for the first max_launches of them,
+ *                     launch_first / launch_count (tensors [first, first + count) of the list; count is at most the table capacity) and
+ *                     launch_blocks (workgroups); elems_per_block[n] (may be NULL) gets per tensor the elements one workgroup covers, a
+ *                     multiple of eamm_optim_adam_block_elems(), 0 for a length-0 tensor, which takes a table slot and no workgroup.
+ *                     Tensor i is covered by ceil(numel[i] / elems_per_block[i]) workgroups, each element by exactly one.
+ *   eamm_optim_adam_table_capacity   tensors per launch.   eamm_optim_adam_block_elems   E, the smallest elements-per-workgroup.
+ */
+int eamm_optim_adam(int device, int n, float* const* p, const float* const* g, float* const* m, float* const* v, const long long* numel,
+                    const float* step_size, const float* bc2_sqrt, double beta1, double beta2, double eps, double weight_decay,
+                    void* stream);
+int eamm_optim_adam_plan(int n, const long long* numel, int max_launches, int* launch_first, int* launch_count, int* launch_blocks,
+                         long long* elems_per_block);
+int eamm_optim_adam_table_capacity(void);
+int eamm_optim_adam_block_elems(void);
+
 #ifdef __cplusplus
 }
 #endif
